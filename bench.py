@@ -22,6 +22,11 @@ back through the host-mapped record.  (`--collective torch`: torch.distributed.a
 torch.distributed is otherwise only used for the barriers around the timed region and to gather the ranks' timings.)
 Total work is fixed -> "strong".  `--single-process --gpus N [--combine host|rccl]` is the other form (one host thread
 drives N devices, HyPhy proper): shard partials combined on the host (Neumaier) or by one RCCL group all-reduce.
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (`value`, `ms_per_step`, ...).  `--full` adds
+everything else the line can carry: value_cold, the event-timed expm / reduction kernels, the CPU baseline and its parity
+check, the HBM traffic counter passes under rocprofv3, and (N > 1) the collective A/B.  `--dump-outputs DIR` writes the
+last timed step's log-likelihood to DIR/logl.npy (float64); the inputs depend only on the arguments.
 """
 import argparse
 import json
@@ -453,10 +458,16 @@ def main():
     ap.add_argument("--combine", choices=["host", "rccl"], default="host",
                     help="--single-process: shard partials summed on the host (Neumaier) or by one RCCL group all-reduce")
     ap.add_argument("--cold-s", type=float, default=0.25,
-                    help="idle seconds before the un-preheated measurement that is reported as value_cold (0: skip it)")
+                    help="idle seconds before the un-preheated W + K steps that --full reports as value_cold (0: skip them)")
     ap.add_argument("--fel", action="store_true",
                     help="with --site-fits: also run the whole FEL-style analysis (alternative + null fit of every "
                          "pattern, hyphy_amd/fel.py) and report its wall time")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: value_cold, the event-timed expm / "
+                         "reduction kernels, the CPU baseline with its parity check, the rocprofv3 HBM traffic passes and (N > 1) "
+                         "the collective A/B.  Without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (its log-likelihood) to DIR/logl.npy, float64")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -718,7 +729,9 @@ def main():
     import gc
     gc.collect()
     gc.disable()
-    # value_cold: the driver's exact protocol (W warm-up steps, K timed steps) on a chip that has just idled — no preheat
+    # value_cold: the driver's exact protocol (W warm-up steps, K timed steps) on a chip that has just idled — no preheat.
+    # A plain run walks the same idle gap and steps too, untimed: the headline window has always come after them, and without
+    # them it measured ~1 % more per step.  Only --full reports the figure.
     value_cold = None
     if args.cold_s > 0:
         time.sleep(args.cold_s)
@@ -746,7 +759,7 @@ def main():
             tcm = torch.tensor([dtc], dtype=torch.float64, device=ctl)
             dist.all_reduce(tcm, op=dist.ReduceOp.MAX)
             dtc = float(tcm.item())
-        value_cold = args.steps / dtc
+        value_cold = args.steps / dtc if args.full else None
     n_pre = int(min(20000, max(0.0, args.preheat_s) / max(per, 1e-6)))
     if multi:
         cnt = torch.tensor([n_pre], dtype=torch.int64, device=ctl)
@@ -774,6 +787,10 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the log-likelihood (all ranks' sum when N > 1)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logl.npy"), np.array([last], dtype=np.float64))
     if step_marks is not None and rank == 0:
         marks = np.diff(np.array([t0] + step_marks)) * 1e6
         sys.stderr.write("[bench] per-step us: " + " ".join(f"{x:.0f}" for x in marks) + "\n")
@@ -782,7 +799,7 @@ def main():
     pt = part.prune_timings(min(max(1, args.steps // TIMING_EVERY), 1024))
     t_prune = float(pt.sum()) * (args.steps / max(1, len(pt)))
     t_exp = t_red = None
-    if n_classes == 1 and not n_mix:
+    if args.full and n_classes == 1 and not n_mix:
         # expm (incl. the fused rate-matrix build) and reduction kernels: event-timed on a few extra steps AFTER the
         # timed region (two more event records per step would perturb it)
         part.set_all_timings(True)
@@ -803,7 +820,7 @@ def main():
     if multi:
         dt = max_over_ranks(dist, ctl, dt)
         per_rank = gather_per_rank(dist, ctl, N, hi - lo, t_prune / max(1, args.steps), t_exp, t_red, t_ar)
-        if ar_step is not None and n_classes == 1 and not share:
+        if args.full and ar_step is not None and n_classes == 1 and not share:
             # both collectives in ONE run (which of the two costs less per step on this node?): 8 + 8 more steps
             # behind the timed region, the library's in-stream all-reduce and torch.distributed's on the same stream
             collective_ab = {}
@@ -935,7 +952,7 @@ def main():
         roof["alg_bytes_per_step"] = bytes_
         # HBM traffic per launch: measured now (two rocprofv3 counter passes of this same script), else the value of the
         # round's committed profile of the same workload and kernel, else null
-        if N == 1 and not args.no_traffic and not args.no_cpu_baseline:
+        if args.full and N == 1 and not args.no_traffic and not args.no_cpu_baseline:
             tr_ = measure_traffic(args.workload, kernels)
             if tr_:
                 roof["traffic"] = tr_["bytes_per_launch"]
@@ -992,7 +1009,7 @@ def main():
                 out["collective_choice"] = collective_choice
         if pipelined:
             out["value_pipelined_no_host_sync"] = pipelined
-        if not args.no_cpu_baseline and N == 1 and n_mix:
+        if args.full and not args.no_cpu_baseline and N == 1 and n_mix:
             try:
                 cb, ref = cpu_baseline_mixture(wl, syn, t_branch, args.steps)
             except Exception as e:
@@ -1008,7 +1025,7 @@ def main():
                     par["timed_points_checked"] = int(n)
                     par["timed_points_max_rel_err"] = float(rel.max())
                 out["parity"] = par
-        elif not args.no_cpu_baseline and N == 1 and n_classes == 1:
+        elif args.full and not args.no_cpu_baseline and N == 1 and n_classes == 1:
             cb = ref = sweep = None
             try:
                 from oracle import hbl

@@ -1,5 +1,5 @@
 import os, sys, tempfile
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import hbl
 from tests.test_hyphy_integration import _case, HIP_BIN, ENV
 case = _case("codon", 8, 40, 11)

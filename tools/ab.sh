@@ -6,7 +6,7 @@ OUT=gpurun_out/ab; mkdir -p $OUT
 for rep in $(seq 1 ${REPS:-1}); do
 echo "$SPECS" | tr ';' '\n' | while IFS='|' read -r tag envs wl steps; do
   [ -z "$tag" ] && continue
-  env HYPHY_HIP_VERBOSE=1 $envs timeout 300 python bench.py --workload $wl --steps ${steps:-200} --warmup 10 --no-cpu-baseline --no-traffic > $OUT/$tag.json 2> $OUT/$tag.err
+  env HYPHY_HIP_VERBOSE=1 $envs timeout 300 python bench.py --workload $wl --steps ${steps:-200} --warmup 10 --full --no-cpu-baseline --no-traffic > $OUT/$tag.json 2> $OUT/$tag.err
   python - "$tag" $OUT/$tag.json $OUT/$tag.err <<'PY'
 import json, sys, re
 tag, path, err = sys.argv[1:4]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs on the GPU box (via gpurun): the round's evidence.  Usage: tools/profile_round.sh <tag> [parts]   (parts: default "all";
 # any of: line workloads stats pmc nuc adapter phases ubench)
-#   bench_driver_line.json   the driver's exact command (CPU baseline with thread sweep, parity, live PMC traffic, value_cold)
+#   bench_driver_line.json   bench.py --full at the headline's step counts (CPU baseline with thread sweep, parity, live PMC traffic, value_cold)
 #   all_workloads.txt        one line per workload with the schedule tuner's report
 #   stats/                   rocprofv3 --kernel-trace --stats, tuner off: subtree repeats on and the trunk's production cut forced
 #                            (steady-state averages)
@@ -15,11 +15,11 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/$R
 mkdir -p $OUT
 has() { [ "$PARTS" = all ] || echo "$PARTS" | grep -qw "$1"; }
 cd $GRAFT_REPO_ROOT
-if has line; then timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_line.json 2> $OUT/bench.err; fi
+if has line; then timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_line.json 2> $OUT/bench.err; fi
 if has workloads; then
 for wl in mg94_64x10k mg94_32x5k busted3_64x10k mix3_64x10k mg94_128x100k mg94_64x5000 mg94_64x2500 mg94_64x1250 gtr_32x50k gtr_32x1m hky_8x1k; do
   steps=200; [ $wl = mg94_128x100k ] && steps=30
-  HYPHY_HIP_VERBOSE=1 timeout 300 python bench.py --workload $wl --steps $steps --warmup 10 --no-cpu-baseline --no-traffic > $OUT/wl_$wl.json 2> $OUT/wl_$wl.err
+  HYPHY_HIP_VERBOSE=1 timeout 300 python bench.py --workload $wl --steps $steps --warmup 10 --full --no-cpu-baseline --no-traffic > $OUT/wl_$wl.json 2> $OUT/wl_$wl.err
   grep "schedule tuner" $OUT/wl_$wl.err | tail -1
   python - $wl $OUT/wl_$wl.json <<'PY'
 import json, sys
