@@ -531,7 +531,7 @@ int enqueue_eval(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch, boo
       pa.n_prog = p->levels[lv].count;
       pa.do_root = (lv + 1 == p->levels.size()) ? 1 : 0;
       pa.red_out = pa.do_root ? red_out : nullptr;
-      launch_prune_mfma(pa, s.stream);
+      if (launch_prune_mfma(pa, s.stream)) return fail("internal: no pruning kernel for this launch form (variant " + std::to_string(p->variant) + ", " + std::to_string(p->NW) + " row blocks)");
     }
     }
     if (pa.timeline) {  // tracing only: synchronous dump of the per-entry s_memtime stamps
@@ -1214,6 +1214,16 @@ int eval_common(hyphy_hip_partition *p, int64_t cat, const int64_t *update_nodes
     p->rep_report = std::string("repeats: no measurement (HYPHY_HIP_TUNE=0), static rule -> ") + (p->rep_enabled ? "on" : "off");
     if (getenv("HYPHY_HIP_VERBOSE")) fprintf(stderr, "[hyphy_hip] %s\n", p->rep_report.c_str());
   }
+  // New root frequencies and nothing to update: ComputeBlock applies theProbs at the root on every call, while the stored per-pattern
+  // values hold the old ones — one child of the root is listed, so the root is combined again from all of its children.  (Per class:
+  // the frequencies are shared, each class's stored values are its own.)
+  if (p->cached_pi.size() != (size_t)p->D || memcmp(p->cached_pi.data(), root_freqs, p->D * sizeof(double))) p->pi_stale.assign(p->C, 1);
+  const int64_t root_child = p->children[p->I - 1].front();
+  if (n_update == 0 && p->initialized[cat] && !p->pi_stale.empty() &&
+      (batch ? std::find(p->pi_stale.begin(), p->pi_stale.end(), 1) != p->pi_stale.end() : p->pi_stale[cat] != 0)) {
+    update_nodes = &root_child;
+    n_update = 1;
+  }
   switch_mode(p, (p->rep_on && p->rep_enabled && p->pin_node < 0 && !force_persist) ? 1 : 0);
   bool changed = false;
   const int64_t bc = batch ? p->C : 1;
@@ -1270,6 +1280,8 @@ int eval_common(hyphy_hip_partition *p, int64_t cat, const int64_t *update_nodes
   p->initialized[cat] = 1;
   if (p->sched_full) res_here[cat] = p->sched_persist ? 1 : 0;
   if (!res_other.empty()) res_other[cat] = 0;
+  if (batch) std::fill(p->pi_stale.begin(), p->pi_stale.end(), 0);  // (every pass reaches the root)
+  else p->pi_stale[cat] = 0;
   return 0;  // (coefficients staged by hyphy_hip_build_q stay valid — and pending — until the next hyphy_hip_build_q)
 }
 
@@ -1752,7 +1764,7 @@ int hyphy_hip_branch_cache_build(hyphy_hip_partition *p, int64_t cat, int64_t no
     pa.n_prog = 1;
     pa.do_root = 0;
     pa.n_prog_total = 1;
-    launch_prune_mfma(pa, s.stream);
+    if (launch_prune_mfma(pa, s.stream)) return fail("internal: branch cache: no pruning kernel for this launch form");
     HIPCHK(hipGetLastError());
   }
   p->bc_node[cat] = node;

@@ -325,7 +325,7 @@ bool launch_expm(const ExpmArgs &a, hipStream_t stream);  // true: fused-constru
 void launch_mix_images(const double *P, const int *off, const double *w, const int32_t *slots, int n, int D, double *Pfrag,
                        double *PTg, double *Prow, hipStream_t stream, double *PTrow = nullptr);
 void launch_site_fit(const SiteFitArgs &a, hipStream_t stream);
-void launch_prune_mfma(const PruneArgs &a, hipStream_t stream);
+int launch_prune_mfma(const PruneArgs &a, hipStream_t stream);  // -1: no instantiation serves this launch form (nothing launched)
 void launch_prune_nuc(const NucArgs &a, hipStream_t stream, const ExpmArgs *ex = nullptr);  // ex: matrix exponentials folded into the launch
 bool prune_nuc_folds_expm(int L, int S_pad, int n_ops);
 bool prune_nuc_fuses_reduce(const NucArgs &a, bool folded);  // launch_prune_nuc will run the instantiation that carries the fused final combine

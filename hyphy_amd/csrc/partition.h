@@ -320,6 +320,7 @@ struct hyphy_hip_partition {
   std::vector<char> resident, last_full;
   bool cached_persist = true, sched_persist = true, sched_full = true;
   std::vector<double> cached_pi;             // root frequencies currently on the device
+  std::vector<char> pi_stale;                // [C] the class's stored per-pattern values were combined under other root frequencies
   std::vector<double> cached_weights;        // category weights currently on the device
   std::vector<std::vector<int64_t>> cached_slots;  // per class: q_nodes list currently on the device
   int root_slot = 0;
@@ -402,7 +403,7 @@ void reroot_path(hyphy_hip_partition *p);
 void sort_patterns(hyphy_hip_partition *p, const int64_t *leaf_codes, int64_t L, int64_t S);
 // tuner.hip
 int upload_schedule(hyphy_hip_partition *p, Shard &s);
-void launch_prune_current(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch);
+int launch_prune_current(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch);  // -1: nothing launched (fail() set)
 int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch);
 // api.hip
 void refresh_twins(hyphy_hip_partition *p, Shard &s);
@@ -427,6 +428,7 @@ int rep_launch(hyphy_hip_partition *p, Shard &s, int cat0);
 // the trunk's lazy full pass as one row-split walk per tile (trunk_walk_kernel); false: not applicable to this pass — the caller runs the
 // pruning kernels.  `timeline`: HYPHY_HIP_WALK_TIMELINE diagnostics allowed (evaluations, not the tuner's passes)
 bool trunk_walk_applies(const hyphy_hip_partition *p, const Shard &s);
+int trunk_walk_backing(const hyphy_hip_partition *p);  // the trunk's kernel for the passes the walk does not serve (variant)
 bool trunk_walk_fuses_reduce(const hyphy_hip_partition *p);  // its launch can carry the fused final combine (PruneArgs::red_*)
 int launch_trunk_walk(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch, bool timeline, const hyhip::PruneArgs *red = nullptr);
 int rep_decide(hyphy_hip_partition *p, int cat, int n_classes);

@@ -2135,7 +2135,7 @@ __global__ void unpack_partials_kernel(const double *__restrict__ partials, int 
 }
 
 template <int NW, bool CLDS>
-void launch_prune_T(const PruneArgs &a, hipStream_t stream) {
+int launch_prune_T(const PruneArgs &a, hipStream_t stream) {
   // Chain grids (tiles, classes, sources): workgroup b runs on XCD b mod 8 and the grid is linearised x-fastest, so with the
   // tile dimension padded to a multiple of 8 (the surplus workgroups retire at once) every chain of a tile — and so every
   // join of its trunk — sits on ONE XCD: deposits and arrival counters are then L2 hits instead of trips to memory.
@@ -2153,72 +2153,72 @@ void launch_prune_T(const PruneArgs &a, hipStream_t stream) {
     if (a.leaf_tab && a.timeline && NW == 4 && CLDS) {  // tracing build of the trunk (HYPHY_HIP_TIMELINE with HYPHY_HIP_REPEATS=1)
       if (a.n_slots <= 3) hipLaunchKernelGGL((prune_wave_kernel<4, 1, true, true, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       else hipLaunchKernelGGL((prune_wave_kernel<4, 2, true, true, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      return;
+      return 0;
     }
     if (a.leaf_tab && NW == 4 && CLDS && (a.wave_variant == 2 || a.wave_variant == 3) && a.n_slots <= 2) {  // three waves per SIMD, see below
       if (a.wave_variant == 2) hipLaunchKernelGGL((prune_wave_kernel<4, 0, true, false, true, 3, false, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       else hipLaunchKernelGGL((prune_wave_kernel<4, 0, true, false, true, 3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      return;
+      return 0;
     }
     if (a.leaf_tab) {  // the trunk of a class-compressed partition
       if (a.n_slots <= 2) hipLaunchKernelGGL((prune_wave_kernel<NW, 0, CLDS, false, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       else if (a.n_slots == 3) hipLaunchKernelGGL((prune_wave_kernel<NW, 1, CLDS, false, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       else hipLaunchKernelGGL((prune_wave_kernel<NW, 2, CLDS, false, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      return;
+      return 0;
     }
     if (a.timeline && NW == 4 && CLDS) {  // tracing build (HYPHY_HIP_TIMELINE)
       if (a.n_slots <= 3) hipLaunchKernelGGL((prune_wave_kernel<4, 1, true, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       else hipLaunchKernelGGL((prune_wave_kernel<4, 2, true, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      return;
+      return 0;
     }
     // three waves per SIMD (the tuner's second stage): finalised node in LDS instead of 32 registers, no parking slot; 2 without,
     // 3 with the deposit prefetch
     if (NW == 4 && CLDS && a.wave_variant == 2 && a.n_slots <= 2) {
       hipLaunchKernelGGL((prune_wave_kernel<4, 0, true, false, true, 3, false>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      return;
+      return 0;
     }
     if (NW == 4 && CLDS && a.wave_variant == 3 && a.n_slots <= 2) {
       hipLaunchKernelGGL((prune_wave_kernel<4, 0, true, false, true, 3, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      return;
+      return 0;
     }
     // production: two waves per SIMD, 0 / 1 / 2 parking slots in LDS (the schedule was compiled for a.n_slots - 2 of them)
     if (a.n_slots <= 2) hipLaunchKernelGGL((prune_wave_kernel<NW, 0, CLDS>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
     else if (a.n_slots == 3) hipLaunchKernelGGL((prune_wave_kernel<NW, 1, CLDS>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
     else hipLaunchKernelGGL((prune_wave_kernel<NW, 2, CLDS>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-    return;
+    return 0;
   }
   if (a.leaf_tab && a.variant != 1) {  // the trunk of a class-compressed partition under the row-split workgroup kernel (r06)
     if constexpr (NW == 4 && CLDS) {
       if (a.T == 1 && a.chain) {
         hipLaunchKernelGGL((prune_mfma_kernel<4, 1, true, false, 0, true, false, true>), grid, block, lds, stream, a.ops, a);
-        return;
+        return 0;
       }
       if (a.T == 1) {
         hipLaunchKernelGGL((prune_mfma_kernel<4, 1, true, false, 0, false, false, true>), grid, block, lds, stream, a.ops, a);
-        return;
+        return 0;
       }
     }
-    return;  // (no other form of this mode exists: the tuner only offers the two above)
+    return -1;  // (no other form of this mode exists: the caller reports it — a skipped launch would leave the trunk stale)
   }
   if (a.variant == 2 && a.chain && a.T == 1) {  // row-split workgroups on a chain schedule: grid = (tiles, classes, sources)
     if constexpr (NW == 4 && CLDS) {
       if (a.red_out) {
         hipLaunchKernelGGL((prune_mfma_kernel<4, 1, true, false, 0, true, true>), grid, block, lds, stream, a.ops, a);
-        return;
+        return 0;
       }
     }
     hipLaunchKernelGGL((prune_mfma_kernel<NW, 1, CLDS, false, 0, true>), grid, block, lds, stream, a.ops, a);
-    return;
+    return 0;
   }
   if (a.timeline) {  // tracing build of the kernel (HYPHY_HIP_TIMELINE), T = 1 only
     hipLaunchKernelGGL((prune_mfma_kernel<NW, 1, CLDS, true>), grid, block, lds, stream, a.ops, a);
-    return;
+    return 0;
   }
   if (NW == 4 && CLDS && a.T == 1 && a.ablate) {  // diagnostic ablation builds (results invalid)
 #define ABL_CASE(v)                                                                                     \
   case v:                                                                                               \
     hipLaunchKernelGGL((prune_mfma_kernel<4, 1, true, false, v>), grid, block, lds, stream, a.ops, a); \
-    return;
+    return 0;
     switch (a.ablate) {
       ABL_CASE(1) ABL_CASE(2) ABL_CASE(4) ABL_CASE(16) ABL_CASE(62) ABL_CASE(63) ABL_CASE(127)
       default: break;
@@ -2245,31 +2245,23 @@ void launch_prune_T(const PruneArgs &a, hipStream_t stream) {
       hipLaunchKernelGGL((prune_mfma_kernel<NW, 4, CLDS, false>), grid, block, lds, stream, a.ops, a);
       break;
   }
+  return 0;
 }
 
 template <int NW>
-void launch_prune_NW(const PruneArgs &a, hipStream_t stream) {
-  if (a.codes_in_lds) launch_prune_T<NW, true>(a, stream);
-  else launch_prune_T<NW, false>(a, stream);
+int launch_prune_NW(const PruneArgs &a, hipStream_t stream) {
+  return a.codes_in_lds ? launch_prune_T<NW, true>(a, stream) : launch_prune_T<NW, false>(a, stream);
 }
 
 }  // namespace
 
-void launch_prune_mfma(const PruneArgs &a, hipStream_t stream) {
-  if (a.n_ops <= 0) return;
+int launch_prune_mfma(const PruneArgs &a, hipStream_t stream) {
+  if (a.n_ops <= 0) return 0;
   switch (a.NW) {
-    case 1:
-      launch_prune_NW<1>(a, stream);
-      break;
-    case 2:
-      launch_prune_NW<2>(a, stream);
-      break;
-    case 3:
-      launch_prune_NW<3>(a, stream);
-      break;
-    default:
-      launch_prune_NW<4>(a, stream);
-      break;
+    case 1: return launch_prune_NW<1>(a, stream);
+    case 2: return launch_prune_NW<2>(a, stream);
+    case 3: return launch_prune_NW<3>(a, stream);
+    default: return launch_prune_NW<4>(a, stream);
   }
 }
 

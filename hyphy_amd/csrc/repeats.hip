@@ -1874,16 +1874,17 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
   }
   ms.trunk_walk = false;
   {
-    // HYPHY_HIP_TRUNK_WALK=1: the walk without asking the tuner (tests, A/B runs).  No tuner at all (HYPHY_HIP_TUNE=0): the walk too —
-    // it is the faster form wherever the static rule turns compression on, and with the one-workgroup-per-tile kernel behind it for
-    // the other passes nothing in this mode depends on an order of arrival: the same bits on every run (tested)
+    // HYPHY_HIP_TRUNK_WALK=1: the walk without asking the tuner (tests, A/B runs), at every NW it has a plan for.  No tuner at all
+    // (HYPHY_HIP_TUNE=0): the walk at NW = 4 — it is the faster form wherever the static rule turns compression on, and with the
+    // one-workgroup-per-tile kernel behind it for the other passes nothing in this mode depends on an order of arrival: the same
+    // bits on every run (tested).  (NW 2 / 3: the walk's speed is unmeasured; without the switch only the tuner offers it.)
     const char *tw = getenv("HYPHY_HIP_TRUNK_WALK");
     const bool tune_off = getenv("HYPHY_HIP_TUNE") && atoi(getenv("HYPHY_HIP_TUNE")) == 0;
     const hyphy_hip_partition::View &tv = p->views[1];
-    if ((tw ? atoi(tw) == 1 : tune_off) && p->NW == 4 && !p->rep_walk_host.empty() && (size_t)tv.L * 32 + (size_t)(tv.L + tv.I) * 16 <= 24576) {
+    if ((tw ? atoi(tw) == 1 : tune_off && p->NW == 4) && !p->rep_walk_host.empty() && (size_t)tv.L * 32 + (size_t)(tv.L + tv.I) * 16 <= 24576) {
       ms.trunk_walk = true;
-      ms.variant = 0;
-      ms.n_slots = lds_slots(1);
+      ms.variant = trunk_walk_backing(p);
+      ms.n_slots = ms.variant == 1 ? p->n_slots_wave : lds_slots(1);
     }
   }
   if (p->C == 1 && !p->nuc) {  // the trunk's own height-minimising roots (the tuner's third stage times the re-rooted schedules)
@@ -2369,6 +2370,13 @@ static bool trunk_walk_allowed() {  // (per call: tests and A/B runs switch it)
 bool trunk_walk_applies(const hyphy_hip_partition *p, const Shard &s) {
   return p->mode == 1 && p->trunk_walk && !p->nuc && s.rep_walk && s.T == 1 && p->sched_full && !p->sched_persist && p->pin_node < 0 &&
          (size_t)p->views[1].L * 32 <= 32768 && trunk_walk_allowed();
+}
+// The kernel that serves the trunk's passes the walk does not (persisting passes, partial updates, the restore of the copies): the
+// row-split workgroup kernel where its trunk form exists (NW = 4, leaf codes in LDS), else the wave-per-tile kernel, which has a trunk
+// form at every NW.  (launch_prune_mfma has no other form of the trunk: it reports a launch it cannot serve.)
+int trunk_walk_backing(const hyphy_hip_partition *p) {
+  const hyphy_hip_partition::View &tv = p->views[1];
+  return p->NW == 4 && (size_t)tv.L * 32 + (size_t)(tv.L + tv.I) * 16 <= 24576 ? 0 : 1;
 }
 bool trunk_walk_fuses_reduce(const hyphy_hip_partition *p) { return p->NW == 4; }
 int launch_trunk_walk(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch, bool timeline, const PruneArgs *red) {

@@ -27,7 +27,7 @@ int upload_schedule(hyphy_hip_partition *p, Shard &s) {
   return 0;
 }
 
-void launch_prune_current(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch) {
+int launch_prune_current(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch) {
   if (p->rr_active && p->chain && s.twins_dirty) refresh_twins(p, s);
   PruneArgs pa = base_prune_args(p, s, cat, n_cat_batch);
   int n_ops = 0;
@@ -40,16 +40,15 @@ void launch_prune_current(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_b
   pa.deposits = s.deposits;
   pa.cs_deposits = s.deposits_class_stride;
   if (const char *ab = getenv("HYPHY_HIP_ABLATE")) pa.ablate = atoi(ab);
-  if (trunk_walk_applies(p, s)) {  // (the trunk of a class-compressed partition as one row-split walk per tile, repeats.hip)
-    launch_trunk_walk(p, s, cat, n_cat_batch, false);
-    return;
-  }
+  if (trunk_walk_applies(p, s))  // (the trunk of a class-compressed partition as one row-split walk per tile, repeats.hip)
+    return launch_trunk_walk(p, s, cat, n_cat_batch, false);
   for (size_t lv = 0; lv < p->levels.size(); lv++) {
     pa.prog = s.prog + p->levels[lv].first;
     pa.n_prog = p->levels[lv].count;
     pa.do_root = (lv + 1 == p->levels.size()) ? 1 : 0;
-    launch_prune_mfma(pa, s.stream);
+    if (launch_prune_mfma(pa, s.stream)) return fail("internal: no pruning kernel for this launch form (variant " + std::to_string(p->variant) + ")");
   }
+  return 0;
 }
 
 // Schedule tuner.  How a full pass is best cut (level-peeled fragments, or chains with sources of at most m nodes)
@@ -64,7 +63,7 @@ int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch) {
   Shard &s = p->shards[0];
   const int T0 = s.T;
   // a candidate: kernel (0 row-split workgroups / 1 wave per tile / 2 row-split workgroups on a chain schedule / 3 (trunks) the
-  // row-split walk, trunk_walk_kernel, with kernel 0 behind it for the passes it does not serve), cut
+  // row-split walk, trunk_walk_kernel, with trunk_walk_backing's kernel behind it for the passes it does not serve), cut
   // (m > 0: chain schedule with sources of at most m nodes, -1: level-peeled fragments, 0: the kernel's own heuristic),
   // instantiation of the wave kernel (0 / 2: three waves per SIMD), re-rooting candidate (-1: the given root)
   struct Cand { int kernel, m, wv, rr; };
@@ -75,10 +74,10 @@ int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch) {
     return std::string(b);
   };
   auto apply = [&](const Cand &c) -> bool {  // build the candidate's schedule; false: not applicable
-    p->variant = c.kernel == 3 ? 0 : c.kernel;
+    p->variant = c.kernel == 3 ? trunk_walk_backing(p) : c.kernel;
     p->trunk_walk = c.kernel == 3;
     p->wave_variant = c.kernel == 1 ? c.wv : 0;
-    p->n_slots = c.kernel == 1 ? (c.wv == 2 ? 2 : p->n_slots_wave) : lds_slots(T0);
+    p->n_slots = p->variant == 1 ? (c.wv == 2 ? 2 : p->n_slots_wave) : lds_slots(T0);
     p->chain_m_forced = c.m;
     if (c.rr >= 0 && p->rr_path != p->rr_cands[(size_t)c.rr]) {
       p->rr_path = p->rr_cands[(size_t)c.rr];
@@ -100,12 +99,16 @@ int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch) {
       return -1.;
     }
     float ms = 0.f, ms2 = 0.f;
-    launch_prune_current(p, s, cat, n_cat_batch);  // warm-up (instruction cache, schedule in L2)
+    bool launched = launch_prune_current(p, s, cat, n_cat_batch) == 0;  // warm-up (instruction cache, schedule in L2)
     if (hipEventRecord(s.ev[0], s.stream) != hipSuccess) return -1.;
-    launch_prune_current(p, s, cat, n_cat_batch);
+    launched = launched && launch_prune_current(p, s, cat, n_cat_batch) == 0;
     if (hipEventRecord(s.ev[1], s.stream) != hipSuccess) return -1.;
-    launch_prune_current(p, s, cat, n_cat_batch);
+    launched = launched && launch_prune_current(p, s, cat, n_cat_batch) == 0;
     if (hipEventRecord(s.ev[2], s.stream) != hipSuccess) return -1.;
+    if (!launched) {
+      err = -1;  // (fail() has the message)
+      return -1.;
+    }
     if (hipStreamSynchronize(s.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
       err = fail("schedule tuner: a candidate launch failed");
       return -1.;

@@ -789,7 +789,7 @@ def test_error_paths():
         hip.expm_batch(Q)
 
 
-@pytest.mark.parametrize("script,n_cases,seed", [("stress_codon.py", 30, 1), ("stress_generic.py", 50, 1)])
+@pytest.mark.parametrize("script,n_cases,seed", [("stress_codon.py", 30, 1), ("stress_generic.py", 50, 1), ("stress_repeats.py", 16, 1)])
 def test_randomised_stress_with_poisoned_allocations(script, n_cases, seed):
     """Random trees / sizes / kernels / fragment cuts and random sequences of full passes, partial updates, pinned
     evaluations, branch-cache line searches and downloads against the oracle, in ONE process (recycled device memory)
