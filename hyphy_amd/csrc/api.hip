@@ -27,7 +27,8 @@ void free_shard(Shard &s) {
                  s.weights, s.templates, s.templates_pad, s.coeffs, s.wg_sum, s.wg_cnt, s.wg_flag, s.prog, s.frag_ctr, s.hand_cnt, s.pi_ones, s.codes_tile,
                  s.bc_ops, s.bc_prog, s.bc_slot, s.bc_q, s.pin, s.jn, s.deposits, s.mix_q, s.mix_p, s.mix_w, s.mix_off, s.ar_buf, s.fit_Timg, s.fit_bcoef, s.fit_smult, s.fit_smix, s.fit_out, s.fit_scratch,
                  s.fit_pi, s.fit_bgroup, s.fit_scratch_cnt, s.fit_ops, s.rep_tab, s.rep_cnt, s.rep_map, s.rep_desc, s.rep_sync,
-                 s.rep_codes_tile, s.rep_leaf, s.rep_walk, s.d_inv, s.expm_need};
+                 s.rep_codes_tile, s.rep_leaf, s.rep_walk, s.d_inv, s.expm_need, s.marg_U, s.marg_work, s.marg_PT, s.marg_pi, s.marg_Ucnt,
+                 s.marg_wcnt, s.marg_prog};
   for (void *d : dev)
     if (d) pool_free(d);  // (the stream was synchronised above)
   void *host[] = {s.h_ops, s.h_out, s.h_slots, s.h_small, s.h_coeffs, s.h_prog, s.h_jn, s.h_tstage, s.h_site, s.h_export};
@@ -1162,6 +1163,21 @@ int hyphy_hip_repeat_stats(const hyphy_hip_partition *p, int64_t out[8]) {
 
 namespace hyhip {
 
+// The persisted conditionals of class `cat` are stale (the last full pass ran with lazy persistence): re-run
+// the pruning pass over the resident transition matrices with every node stored.
+int ensure_resident(hyphy_hip_partition *p, int64_t cat) {
+  if (p->resident[cat]) return 0;
+  if (!p->initialized[cat] || p->cached_pi.size() != (size_t)p->D) return fail("conditionals not resident: evaluate first");
+  std::vector<int64_t> all(p->B);
+  for (int64_t k = 0; k < p->B; k++) all[k] = k;
+  const std::vector<double> pi = p->cached_pi;
+  const std::vector<char> lf = p->last_full;
+  if (eval_common(p, cat, all.data(), p->B, nullptr, 0, nullptr, false, 0, pi.data(), nullptr, true, false, false, true))
+    return -1;
+  p->last_full = lf;  // (an internal pass: the caller's own sequence of evaluations is what the policy looks at)
+  return collect_status(p);
+}
+
 // An uncollected hyphy_hip_evaluate_async owns the host-mapped result record: every entry point that is about to write it
 // (or to wait on it) finishes the pending evaluation first (include/hyphy_hip.h: "any other evaluation entry point ...").
 int finish_pending_async(hyphy_hip_partition *p) {
@@ -1551,8 +1567,6 @@ int hyphy_hip_evaluate_categories_built(hyphy_hip_partition *p, const int64_t *u
   return hyphy_hip_evaluate_categories_built_sites(p, update_nodes, n_update, q_nodes, n_q, weights, root_freqs, logl_out, nullptr, nullptr);
 }
 
-static int ensure_resident(hyphy_hip_partition *p, int64_t cat);
-
 int hyphy_hip_download_partials(hyphy_hip_partition *p, int64_t cat, double *inode_cache, int64_t *scaler_counts) {
   if (!p) return fail("partition == NULL");
   if (cat < 0) cat = 0;
@@ -1645,21 +1659,6 @@ int hyphy_hip_set_pinned_states(hyphy_hip_partition *p, int64_t node, const int6
 // (tree.cpp:3383-3936) then evaluates L(t) with one [D x D] x [D x S] contraction per call while the
 // optimiser's line search varies the branch length (policy code likefunc.cpp:10886-10948, 11125-11258).
 // ---------------------------------------------------------------------------------------------------
-// The persisted conditionals of class `cat` are stale (the last full pass ran with lazy persistence): re-run
-// the pruning pass over the resident transition matrices with every node stored.
-static int ensure_resident(hyphy_hip_partition *p, int64_t cat) {
-  if (p->resident[cat]) return 0;
-  if (!p->initialized[cat] || p->cached_pi.size() != (size_t)p->D) return fail("conditionals not resident: evaluate first");
-  std::vector<int64_t> all(p->B);
-  for (int64_t k = 0; k < p->B; k++) all[k] = k;
-  const std::vector<double> pi = p->cached_pi;
-  const std::vector<char> lf = p->last_full;
-  if (eval_common(p, cat, all.data(), p->B, nullptr, 0, nullptr, false, 0, pi.data(), nullptr, true, false, false, true))
-    return -1;
-  p->last_full = lf;  // (an internal pass: the caller's own sequence of evaluations is what the policy looks at)
-  return collect_status(p);
-}
-
 int hyphy_hip_branch_cache_build(hyphy_hip_partition *p, int64_t cat, int64_t node) {
   if (!p) return fail("partition == NULL");
   if (p->nuc) {

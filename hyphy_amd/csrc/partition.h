@@ -243,6 +243,11 @@ struct Shard {
   bool last_nucgen = false;          // the last 4-state pruning launch ran a generated kernel (hyphy_hip_prune_kernel_name)
   bool rep_team = false;             // its static launches run the row-split walk (class_table_team_kernel), one workgroup per item
   bool rep_sync_dirty = false;       // a lower-phase launch has run and no trunk launch has reset rep_sync behind it yet
+  // marginal ancestral reconstruction (marginal.hip), allocated on first use: outside vectors [I][node] and their exponents, the
+  // per-tile work area of the children of the node being walked, transposed matrix images of one class (MFMA path), the program
+  double *marg_U = nullptr, *marg_work = nullptr, *marg_PT = nullptr, *marg_pi = nullptr;
+  int32_t *marg_Ucnt = nullptr, *marg_wcnt = nullptr;
+  int4 *marg_prog = nullptr;
 };
 
 }  // namespace hyhip
@@ -374,6 +379,8 @@ struct hyphy_hip_partition {
   bool fit_spills = false;                   // ... some node goes through the scratch copy
   double fit_kernel_ms = 0.;                 // duration of the last site-fit kernel (max over shards)
   double timings[3] = {0, 0, 0};
+  std::vector<int4> marg_prog;                // marginal reconstruction: pre-order program over the tree (marginal.hip), compiled once
+  int marg_maxk = 0;                         // ... most children of a node
   double allreduce_ms = 0.;                  // duration of the last in-stream all-reduce (timing detail on; else 0)
 };
 
@@ -414,6 +421,7 @@ int eval_common(hyphy_hip_partition *p, int64_t cat, const int64_t *update_nodes
                 double *d_logl_out, bool reduce, bool floor_log, bool batch = false, bool force_persist = false,
                 const MixSpec *mix = nullptr);
 int finish_pending_async(hyphy_hip_partition *p);
+int ensure_resident(hyphy_hip_partition *p, int64_t cat);  // persisted conditionals of class cat current (re-runs a persisting pass)
 int collect_status(hyphy_hip_partition *p);
 int publish_and_collect(hyphy_hip_partition *p, const double *d_value, double *value_out);  // (single-shard partitions)
 void record_timings(hyphy_hip_partition *p);
@@ -435,6 +443,8 @@ int rep_decide(hyphy_hip_partition *p, int cat, int n_classes);
 bool rep_static_decision(const hyphy_hip_partition *p);  // on / off without a measurement (tuner disabled, forced cut)
 size_t rep_sync_words(const hyphy_hip_partition *p);
 int rep_sync_stride();
+// marginal.hip
+std::vector<int4> plan_marginal_program(int64_t L, int64_t I, const int64_t *parents, int *maxk_out);
 // comm.hip
 int combine_shards(hyphy_hip_partition *p, double *logl_out);
 

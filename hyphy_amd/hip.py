@@ -23,7 +23,7 @@ EXPORTS = [
     "hyphy_hip_expm_batch", "hyphy_hip_set_q_templates", "hyphy_hip_build_q", "hyphy_hip_q_buffer",
     "hyphy_hip_evaluate_built", "hyphy_hip_evaluate_built_sites", "hyphy_hip_update_q_templates", "hyphy_hip_evaluate_categories_built", "hyphy_hip_evaluate_categories_built_sites", "hyphy_hip_prune_timings", "hyphy_hip_prune_launches",
     "hyphy_hip_prune_kernel_name", "hyphy_hip_branch_cache_build", "hyphy_hip_branch_cache_evaluate",
-    "hyphy_hip_set_pinned_states", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
+    "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
     "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
     "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error",
     "hyphy_hip_version",
@@ -141,6 +141,10 @@ def load():
     lib.hyphy_hip_prune_kernel_name.argtypes = [vp]
     lib.hyphy_hip_set_repeats.restype = C.c_int
     lib.hyphy_hip_set_repeats.argtypes = [vp, C.c_int]
+    lib.hyphy_hip_marginal_ancestral.restype = C.c_int
+    lib.hyphy_hip_marginal_ancestral.argtypes = [vp, C.c_int64, dp, dp, lp, dp]
+    lib.hyphy_hip_plan_marginal.restype = C.c_int64
+    lib.hyphy_hip_plan_marginal.argtypes = [C.c_int64, C.c_int64, lp, lp, C.c_int64]
     lib.hyphy_hip_plan_trunk_walk.restype = C.c_int64
     lib.hyphy_hip_plan_trunk_walk.argtypes = [C.c_int64, C.c_int64, lp, lp, C.c_int64]
     lib.hyphy_hip_plan_repeats.restype = C.c_int64
@@ -246,6 +250,24 @@ def plan_trunk_walk(parents, L: int):
     inputs = [int(x) for x in out[10 + 4 * nn: 10 + 4 * nn + ni]]
     return {"nodes": nodes, "inputs": inputs, "depth": depth, "one": (int(out[4]), int(out[5])),
             "two": ((int(out[6]), int(out[7])), (int(out[8]), int(out[9]))) if two else None}
+
+
+def plan_marginal(flat_parents, L: int) -> dict:
+    """Host-only: the pre-order program of the marginal-reconstruction pass over a tree (``flat_parents[c]`` = internal index of c's
+    parent, internal node i has code L + i, the root last).  Returns ``entries`` [(kind, a, b, c)]: a node header (0, internal
+    index, children, is root) followed by its children (1, node code, internal index or -1, position), and ``maxk``."""
+    lib = load()
+    par = np.ascontiguousarray(flat_parents, dtype=np.int64)
+    I = len(par) - int(L)
+    need = lib.hyphy_hip_plan_marginal(int(L), I, _l(par), None, 0)
+    if need >= 0 or need == -1:
+        raise HipError("plan_marginal: " + lib.hyphy_hip_last_error().decode())
+    out = np.zeros(-need, dtype=np.int64)
+    n = lib.hyphy_hip_plan_marginal(int(L), I, _l(par), _l(out), len(out))
+    if n < 0:
+        raise HipError("plan_marginal: " + lib.hyphy_hip_last_error().decode())
+    ne = int(out[0])
+    return {"entries": [tuple(int(x) for x in out[2 + 4 * k: 6 + 4 * k]) for k in range(ne)], "maxk": int(out[1])}
 
 
 def plan_nucgen(flat_parents, L: int, leaf_has_ambig=None, compile_it: bool = True, small: bool = False):
@@ -646,6 +668,27 @@ class HipPartition:
         st = np.ascontiguousarray(states, dtype=np.int64)
         assert st.shape == (self.S,)
         _check(self._lib.hyphy_hip_set_pinned_states(self._h, int(node), _l(st)))
+
+    def marginal_ancestral(self, which: str = "internal", weights=None, support: bool = True, map: bool = False):
+        """Marginal ancestral reconstruction in one pass over the resident conditionals (call after an evaluation of every
+        class).  ``which``: "internal" (rows = internal nodes) or "leaves" (rows = leaves, unnormalised L_s(leaf = x) / L_s).
+        ``weights``: class weights when C > 1.  Returns the support [rows, S, D] (``support``), and with ``map`` also the MAP
+        state [rows, S] and its support [rows, S]: a single array, or a tuple of those asked for."""
+        if which not in ("internal", "leaves"):
+            raise ValueError("which must be 'internal' or 'leaves'")
+        rows = self.I if which == "internal" else self.L
+        w = None
+        if self.C > 1:
+            if weights is None:
+                raise ValueError("weights are required when C > 1")
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            assert w.shape == (self.C,)
+        sup = np.zeros((rows, self.S, self.D)) if support else None
+        ms = np.zeros((rows, self.S), dtype=np.int64) if map else None
+        mv = np.zeros((rows, self.S)) if map else None
+        _check(self._lib.hyphy_hip_marginal_ancestral(self._h, 0 if which == "internal" else 1, _d(w), _d(sup), _l(ms), _d(mv)))
+        out = tuple(x for x in (sup, ms, mv) if x is not None)
+        return out[0] if len(out) == 1 else out
 
     # -- branch cache (one-branch line searches) --------------------------------------------------
     def branch_cache_build(self, node: int, cat: int = 0):

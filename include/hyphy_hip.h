@@ -394,6 +394,30 @@ int hyphy_hip_set_timing_detail(hyphy_hip_partition *p, int on);
  * AddBranchToForcedRecomputeList (src/core/likefunc2.cpp:932-1040). */
 int hyphy_hip_set_pinned_states(hyphy_hip_partition *p, int64_t node, const int64_t *states /* [S] */);
 
+/* ---- marginal ancestral reconstruction in one pass --------------------------------------------------------
+ * Replaces the I*(D-1) pinned evaluations of RecoverAncestralSequencesMarginal (src/core/likefunc2.cpp:932-1120) with one
+ * pre-order ("outside") pass over the resident conditionals: U_root = pi, U_c = P_c^T (U_p * prod of the other children's edge
+ * products); the support of internal node n is in_n * U_n / L_s, that of a leaf U_l / L_s.
+ *   which = 0: internal nodes (row i = internal index i, node code L + i); 1: leaves (row l, the DOLEAVES form).
+ *   weights [C] (NULL when C == 1): the class weights of the last evaluation; classes are mixed by weight (the reference's
+ *                   weighted-sum mode, likefunc2.cpp:772-859).
+ *   support_out     [rows][S][D] or NULL.  Internal nodes: Pr(state | pattern), all D columns (the reference stores D-1, then
+ *                   1 - sum); leaves: L_s(leaf = x) / L_s, unnormalised, as the reference stores it.
+ *   map_state_out   [rows][S] or NULL: state of largest support (the first one on ties); map_support_out [rows][S] or NULL.
+ * Call after an evaluation of every class; the pass uses the matrices, root frequencies and patterns of the last evaluation
+ * of each class (persisted copies are restored first if the last full pass kept them on chip).  Patterns in the caller's order.
+ * Returns < 0 when a pin is active, a class was never evaluated, or C > 1 without weights.  Leaves no state behind: later
+ * evaluations, partial updates and a branch cache built before the call give what they give without it. */
+int hyphy_hip_marginal_ancestral(hyphy_hip_partition *p, int64_t which, const double *weights /* [C] or NULL */,
+                                 double *support_out, int64_t *map_state_out, double *map_support_out);
+/* Host-only: the pre-order program the pass walks.  flat_parents [L+I]: internal index of each node's parent (internal i = node
+ * code L + i, the root last with -1), as hyphy_hip_create takes it.
+ * out[0] = entries n, out[1] = most children of a node, then n entries of 4 words: a node header (0, internal index, children,
+ * 1 for the root) followed by one entry per child (1, child node code, child internal index or -1 for a leaf, position).  Every
+ * internal node's header comes after its parent's.  Returns the words written, -(words needed) when cap is too small (out may be
+ * NULL), -1 on bad arguments. */
+int64_t hyphy_hip_plan_marginal(int64_t L, int64_t I, const int64_t *flat_parents, int64_t *out, int64_t cap);
+
 /* ---- branch cache ---------------------------------------------------------------------
  * Replaces _TheTree::ComputeBranchCache (src/core/tree_evaluator.cpp:4286-4845) and
  * _TheTree::ComputeLLWithBranchCache (src/core/tree.cpp:3383-3936), driven by the policy code of

@@ -130,6 +130,10 @@ static _HyHipCatBatch _hyhip_cb;
 static bool _hyhip_cat_block = false;  // this ComputeBlock call builds / uses a branch cache behind its evaluation: it must really run
 static std::map<const void *, std::pair<const void *, long>> _hyhip_tree_owner;  // _TheTree* -> (lf, partition index)
 long _hyhip_calls = 0L, _hyhip_cached_calls = 0L, _hyhip_deferred = 0L;
+static long _hyhip_marginal_calls = 0L;  // marginal reconstructions answered by hyphy_hip_marginal_ancestral (HYPHY_HIP_MARGINAL=1)
+// class weights the weighted-sum loop of PopulateConditionalProbabilities passed for (lf, partition) last: the weights of the baseline
+// evaluation of RecoverAncestralSequencesMarginal (recorded by _hyphy_hip_cat_begin whether or not it batches the classes)
+static std::map<std::pair<const void *, long>, std::vector<double>> _hyhip_class_weights;
 static double _hyhip_compute_seconds = 0.;  // wall time inside _hyphy_hip_compute (coefficients, library call incl. its wait, downloads)
 // > 0: ExponentiateMatrices hands the queued rate matrices to the adapter instead of exponentiating them on the host.
 // On while Optimize runs (nothing but ComputeBlock reads the transition matrices there; they are brought up to date
@@ -182,6 +186,10 @@ static void _hyphy_hip_teardown(const void *lf) {
   _hyhip_lfs.erase(it);
   for (auto o = _hyhip_tree_owner.begin(); o != _hyhip_tree_owner.end();)
     o = o->second.first == lf ? _hyhip_tree_owner.erase(o) : std::next(o);
+  for (auto w = _hyhip_class_weights.begin(); w != _hyhip_class_weights.end();)
+    w = w->first.first == lf ? _hyhip_class_weights.erase(w) : std::next(w);
+  if (getenv("HYPHY_HIP_VERBOSE") && _hyhip_marginal_calls)
+    fprintf(stderr, "[hyphy_hip] %ld marginal reconstructions ran on the device\n", _hyhip_marginal_calls);
   if (getenv("HYPHY_HIP_VERBOSE")) fprintf(stderr, "[hyphy_hip] %ld ComputeBlock evaluations ran on the device so far (+ %ld through the branch cache); %ld matrix exponentials moved to the device; adapter mode: %.3f s of wall clock inside the adapter's ComputeBlock calls (coefficients, library call and its wait, per-pattern downloads)\n", _hyhip_calls, _hyhip_cached_calls, _hyhip_deferred, _hyhip_compute_seconds);
 }
 
@@ -1616,6 +1624,7 @@ static void _hyhip_cat_flush(_HyHipPart &hp) {
 
 // (extern: called from the likefunc2.cpp copy)
 bool _hyphy_hip_cat_begin(const void *lf, long index, long n_classes, const hyFloat *weights, hyFloat *buffer, long *scalers, long block_length) {
+  if (weights && n_classes >= 1) _hyhip_class_weights[std::make_pair(lf, index)].assign(weights, weights + n_classes);
   _HyHipCatBatch &cb = _hyhip_cb;
   cb.active = false;
   cb.logl_valid = false;
@@ -1844,6 +1853,43 @@ struct _HyHipOptimizeScope {  // Optimize: device exponentials inside, host matr
     if (on && --_hyhip_defer_depth == 0) _hyphy_hip_flush(lf);
   }
 };
+// Marginal ancestral reconstruction (HYPHY_HIP_MARGINAL=1, opt-in): RecoverAncestralSequencesMarginal (likefunc2.cpp:932-1120) asks
+// here, right behind its baseline evaluation, before it would run its I*(D-1) (DOLEAVES: L*D) pinned evaluations.  0: supportValues
+// is filled exactly as the pinned loop fills it (rows in in-order position through postToIn; internal nodes: columns 0..D-2, column
+// D-1 left at 0 for the reference's 1 - sum; leaves: all D columns, unnormalised) and the pinned loop is skipped; > 0: declined.
+int _hyphy_hip_marginal(const void *lf, long index, bool do_leaves, hyFloat *support, long rows, long S, long D, const long *post_to_in) {
+  static const bool on = getenv("HYPHY_HIP_MARGINAL") && atoi(getenv("HYPHY_HIP_MARGINAL")) == 1;
+  if (!on || !_hyphy_hip_enabled()) return 1;
+  auto it = _hyhip_lfs.find(lf);
+  if (it == _hyhip_lfs.end() || index < 0 || index >= (long)it->second.size()) return 1;
+  _HyHipPart &hp = it->second[index];
+  if (!hp.part || hp.spmd || hp.pending || !support || !post_to_in || rows < 1 || S < 1 || D < 2) return 1;
+  const long C = std::max<long>(1, (long)hp.cat_seen.size());
+  const double *w = nullptr;
+  if (C > 1) {  // (rate classes: the weights the baseline evaluation mixed with; none recorded -> the pinned loop)
+    auto wi = _hyhip_class_weights.find(std::make_pair(lf, index));
+    if (wi == _hyhip_class_weights.end() || (long)wi->second.size() != C) return 1;
+    for (long c = 0; c < C; c++)
+      if (!hp.cat_seen[c] || !(wi->second[c] >= 0.)) return 1;
+    w = wi->second.data();
+  }
+  for (long c = 0; c < C && c < (long)hp.mix_state.size(); c++)
+    if (hp.mix_state[c] > 0) return 1;  // (explicit-form mixtures: left to the pinned loop)
+  std::vector<double> tmp((size_t)rows * S * D);
+  if (hyphy_hip_marginal_ancestral(hp.part, do_leaves ? 1 : 0, w, tmp.data(), nullptr, nullptr) != 0) {
+    if (getenv("HYPHY_HIP_VERBOSE")) fprintf(stderr, "[hyphy_hip] marginal reconstruction declined: %s\n", hyphy_hip_last_error());
+    return 1;
+  }
+  const long cols = do_leaves ? D : D - 1;
+  for (long r = 0; r < rows; r++) {
+    hyFloat *dst = support + post_to_in[r] * S * D;
+    const double *src = tmp.data() + (size_t)r * S * D;
+    for (long s = 0; s < S; s++)
+      for (long x = 0; x < cols; x++) dst[s * D + x] = src[s * D + x];
+  }
+  _hyhip_marginal_calls++;
+  return 0;
+}
 #endif
 '''
 
@@ -2048,4 +2094,25 @@ CAT_END_ANCHOR = "#ifdef __HYPHYMPI__\n  DeleteObject(computedWeights);\n#endif\
 CAT_END = r"""#ifdef HYPHY_HIP
   if (hip_cat_batch) _hyphy_hip_cat_end(this, index);
 #endif
+"""
+
+
+# ---- block 8: marginal ancestral reconstruction in one device pass (HYPHY_HIP_MARGINAL=1) --------------------------------------------
+# likefunc2.cpp copy, RecoverAncestralSequencesMarginal: right behind the baseline evaluation, the adapter may fill supportValues and
+# the pinned loops are skipped; the reference's own post-processing below them runs unchanged
+MARG_DECL = r"""
+#ifdef HYPHY_HIP
+int _hyphy_hip_marginal(const void *lf, long index, bool do_leaves, hyFloat *support, long rows, long S, long D, const long *post_to_in);
+#endif
+"""
+MARG_ANCHOR = "  ComputeSiteLikelihoodsForABlock(index, siteLikelihoods, scalersBaseline);\n  // establish a baseline likelihood for each site\n\n  if (doLeaves) {\n"
+MARG_NEW = r"""  ComputeSiteLikelihoodsForABlock(index, siteLikelihoods, scalersBaseline);
+  // establish a baseline likelihood for each site
+
+#ifdef HYPHY_HIP
+  if (_hyphy_hip_marginal(this, index, doLeaves, supportValues.theData, matrixSize, patternCount, alphabetDimension,
+                          postToIn.list_data) == 0) {
+  } else
+#endif
+  if (doLeaves) {
 """

@@ -74,6 +74,9 @@ def main():
     l2 = replace_once(l2, AB.CAT_BEGIN_ANCHOR, AB.CAT_BEGIN + AB.CAT_BEGIN_ANCHOR[len("  scalers.Populate(arrayDim, 0, 0);\n\n"):])
     l2 = replace_once(l2, AB.CAT_SKIP_ANCHOR, AB.CAT_SKIP)
     l2 = splice(l2, AB.CAT_END_ANCHOR, AB.CAT_END, before=True)
+    # marginal ancestral reconstruction in one device pass (HYPHY_HIP_MARGINAL=1)
+    l2 = splice(l2, '#include "likefunc.h"\n', AB.MARG_DECL) if '#include "likefunc.h"\n' in l2 else splice(l2, "using namespace hy_global;\n", AB.MARG_DECL)
+    l2 = replace_once(l2, AB.MARG_ANCHOR, AB.MARG_NEW)
     l2src = os.path.join(OUT, "likefunc2_hip.cpp")
     open(l2src, "w").write(l2)
     # 3. compile that one file with the reference's flags (oracle/Makefile.ref) + -DHYPHY_HIP
