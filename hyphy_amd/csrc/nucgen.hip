@@ -6,9 +6,9 @@
 // (_handle4x4_pruning_case_direct, src/core/tree_evaluator.cpp:2253-2273; the loop it sits in, :3556-4171).  Here the schedule
 // compiler's entries (common.h: entry format; schedule.hip: emit_program) are turned into the source of ONE kernel per (topology,
 // update set, persistence flags): node order fixed, every leaf number, branch slot and plane offset an immediate, a pending node a
-// named value the register allocator places (no parking slots), a branch's matrix twelve scalar-load constants, the first factor of
+// named value the register allocator places (no parking slots), a branch's matrix sixteen scalar-load constants, the first factor of
 // a node an assignment instead of a multiplication by one, all leaf codes of a pattern requested up front.  What stays exactly as
-// in the interpreter: the order of the factors inside a node, the row-stochastic 12-multiply-add form of an internal edge, the
+// in the interpreter: the order of the factors inside a node, the four-term product of an internal edge, the
 // leaf lookups in the transposed leaf matrices (LDS), the per-node 2^64 rescale test, the epilogue — the two forms are held to each
 // other bit for bit in tests/test_gpu_nucgen.py.
 //
@@ -132,7 +132,7 @@ struct Src {
 // a later entry of the SAME pass re-reads for want of a parking slot, and here such a node is a named value: no store, no re-read.
 // Returns an empty string when the program has a form the generator does not cover.
 // small (the form for shards of at most two workgroups per CU, where a wave is alone on its SIMD and every latency is exposed):
-//   * EVERY branch's matrix sits in LDS (n_branches of them) and an internal edge reads its twelve entries from there — LDS reads
+//   * EVERY branch's matrix sits in LDS (n_branches of them) and an internal edge reads its sixteen entries from there — LDS reads
 //     return in order after ~100 cycles where a scalar load that misses the scalar cache takes several hundred and returns out of order;
 //   * this evaluation's matrix exponentials are computed inside the launch by the first threads of every workgroup, straight into
 //     the LDS copy (expm4.h, the library's own source), workgroup 0 leaves the global copies for later partial updates;
@@ -186,16 +186,7 @@ std::string nucgen_source(const int4 *ops, int n_ops, int L, bool lazy, bool sma
   }
   o("  __syncthreads();\n");
   std::vector<char> have;  // node finalised earlier in this program: its values are n<node>_0..3, c<node>
-  // Rescale tests only where underflow is possible (the rule of the codon kernels, schedule.hip: thin_rescale_tests): a node whose
-  // internal children were all TESTED in this pass (their per-pattern sums are >= 2^-64 behind the test) and that has at most four
-  // factors cannot fall below 2^-256 times the spread of a conditional vector — hundreds of binary orders above the denormals; its
-  // parent tests again, the last node of the program always does.  A rescale is an exact power of 2^64 and conditionals only shrink
-  // on the way up, so the (value, exponent) pair the root ends with is the same wherever the steps were taken.
-  static const bool thin = !(getenv("HYPHY_HIP_SCALE_THIN") && atoi(getenv("HYPHY_HIP_SCALE_THIN")) == 0);
-  std::vector<char> tested;
-  int last_closing = -1;
-  for (int q = 0; q < n_ops; q++)
-    if (ops[q].x & OPF_LAST) last_closing = q;
+  // Every node tests for rescaling (schedule.hip: build_schedule says why the tests are no longer thinned out).
   int last_node = -1;
   int e = 0;  // factor counter
   int k = 0;
@@ -204,7 +195,7 @@ std::string nucgen_source(const int4 *ops, int n_ops, int L, bool lazy, bool sma
     std::vector<std::string> f[4];
     std::vector<std::string> cterms;
     int par = -1;
-    bool closed = false, kids_tested = true;
+    bool closed = false;
     for (; k < n_ops && !closed; k++) {
       const int4 op = ops[k];
       const int kind = op.x & 3;
@@ -234,8 +225,6 @@ std::string nucgen_source(const int4 *ops, int n_ops, int L, bool lazy, bool sma
         const int c = op.w, br = op.z;
         if (c < 0) return std::string();
         if ((size_t)c >= have.size()) have.resize((size_t)c + 1, 0);
-        if ((size_t)c >= tested.size()) tested.resize((size_t)c + 1, 0);
-        if (!(have[c] && tested[c])) kids_tested = false;  // (a child read back from its persisted copy counts as untested)
         std::string v[4], vc;
         if (have[c]) {
           for (int j = 0; j < 4; j++) v[j] = "n" + std::to_string(c) + "_" + std::to_string(j);
@@ -248,13 +237,13 @@ std::string nucgen_source(const int4 *ops, int n_ops, int L, bool lazy, bool sma
           for (int j = 0; j < 4; j++) v[j] = "g" + std::to_string(e) + "_" + std::to_string(j);
           vc = "gc" + std::to_string(e);
         }
-        // (P v)_i = (d0 P_i0 + d1 P_i1) + (v3 + d2 P_i2), d_j = v_j - v3: rows of P sum to one.  PT = [state j][row i]
+        // (P v)_i = (v0 P_i0 + v1 P_i1) + (v2 P_i2 + v3 P_i3), the interpreter's form and order (prune.hip says why not the
+        // row-stochastic form with differences).  PT = [state j][row i]
         if (small && br >= n_branches) return std::string();
         o("  const double *P%d = %s + %d;\n", e, small ? "L_" : "PT", br * 16);
-        o("  const double d%d_0 = %s - %s, d%d_1 = %s - %s, d%d_2 = %s - %s;\n", e, v[0].c_str(), v[3].c_str(), e, v[1].c_str(), v[3].c_str(), e, v[2].c_str(),
-          v[3].c_str());
         for (int i = 0; i < 4; i++)
-          o("  const double f%d_%d = fma(d%d_1, P%d[%d], d%d_0 * P%d[%d]) + fma(d%d_2, P%d[%d], %s);\n", e, i, e, e, 4 + i, e, e, i, e, e, 8 + i, v[3].c_str());
+          o("  const double f%d_%d = fma(%s, P%d[%d], %s * P%d[%d]) + fma(%s, P%d[%d], %s * P%d[%d]);\n", e, i, v[1].c_str(), e, 4 + i, v[0].c_str(), e, i,
+            v[3].c_str(), e, 12 + i, v[2].c_str(), e, 8 + i);
         for (int i2 = 0; i2 < 4; i2++) f[i2].push_back("f" + std::to_string(e) + "_" + std::to_string(i2));
         cterms.push_back(vc);
         e++;
@@ -270,19 +259,10 @@ std::string nucgen_source(const int4 *ops, int n_ops, int L, bool lazy, bool sma
         std::string csum = "0";
         for (const std::string &t : cterms) csum += " + " + t;
         o("  int c%d = %s;\n", par, csum.c_str());
-        if ((size_t)par >= tested.size()) tested.resize((size_t)par + 1, 0);
-        const bool test_here = !thin || k == last_closing || !kids_tested || f[0].size() > 4;
-        tested[par] = test_here ? 1 : 0;
-        if (test_here) {
-          o("  {\n    const double tot = (n%d_0 + n%d_1) + (n%d_2 + n%d_3);\n", par, par, par, par);
-          o("    if (__any(!(tot >= T_ && tot <= U_))) {   /* rare: some pattern of the wave needs (or cannot have) a rescale */\n");
-          o("      double sc;\n      const int m = rescale_(tot, sc);\n");
-          o("      if (m != 0) { n%d_0 *= sc; n%d_1 *= sc; n%d_2 *= sc; n%d_3 *= sc; c%d += m; }\n    }\n  }\n", par, par, par, par, par);
-        } else {
-          // (no test: keep the node's products apart from what reads them — under -ffp-contract=fast the differences d = v - v3 of the
-          //  parent's edge would fuse with them into multiply-adds the interpreter, where the test's branch sits in between, never forms)
-          o("  asm(\"\" : \"+v\"(n%d_0), \"+v\"(n%d_1), \"+v\"(n%d_2), \"+v\"(n%d_3));\n", par, par, par, par);
-        }
+        o("  {\n    const double tot = (n%d_0 + n%d_1) + (n%d_2 + n%d_3);\n", par, par, par, par);
+        o("    if (__any(!(tot >= T_ && tot <= U_))) {   /* rare: some pattern of the wave needs (or cannot have) a rescale */\n");
+        o("      double sc;\n      const int m = rescale_(tot, sc);\n");
+        o("      if (m != 0) { n%d_0 *= sc; n%d_1 *= sc; n%d_2 *= sc; n%d_3 *= sc; c%d += m; }\n    }\n  }\n", par, par, par, par, par);
         if (!(op.x & OPF_NOPERSIST_NUC) && !lazy) {
           o("  {\n    const size_t b = (size_t)%d * 4 * SP + s;\n", par);
           o("    a.partials[b] = n%d_0; a.partials[b + SP] = n%d_1; a.partials[b + 2 * SP] = n%d_2; a.partials[b + 3 * SP] = n%d_3;\n", par, par, par, par);

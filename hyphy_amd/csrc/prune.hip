@@ -1058,7 +1058,7 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
           for (int r = 0; r < 4; r++) acc[w][r] = (16 * w + 4 * r + g == ps) ? acc[w][r] : 0.;
       }
       double sc = 1.0;
-      if (!(op.x & OPF_NOSCALE)) {  // (the host thins the tests out where underflow is impossible: api.hip thin_rescale_tests)
+      {  // rescaling test, at every node (schedule.hip: build_schedule)
         double s = 0.;
 #pragma unroll
         for (int w = 0; w < NW; w++) s += (acc[w][0] + acc[w][1]) + (acc[w][2] + acc[w][3]);
@@ -1572,9 +1572,12 @@ __global__ __launch_bounds__(256) void prune_nuc_kernel(const int4 *__restrict__
 //  * a leaf edge is a LOOKUP: the transposed leaf matrices sit in LDS ([leaf][state][row], 128 bytes per leaf, filled once per
 //    workgroup) and a thread fetches the four entries of its pattern's column with two 16-byte reads — the four possible
 //    columns of a leaf cover all 32 banks exactly once, so any mix of states in a wave is conflict-free;
-//  * an internal edge uses the row-stochastic form of the reference's 4-state path (_handle4x4_pruning_case_direct,
-//    tree_evaluator.cpp:2253-2273): (P v)_i = (c0 P_i0 + c1 P_i1) + (v_3 + c2 P_i2), c_j = v_j - v_3 — 12 multiply-adds and
-//    3 subtractions, the matrix arriving through scalar loads one entry ahead (loop unrolled by two: no register moves);
+//  * an internal edge is the plain product (P v)_i = (v_0 P_i0 + v_1 P_i1) + (v_2 P_i2 + v_3 P_i3), the matrix arriving through
+//    scalar loads one entry ahead (loop unrolled by two: no register moves).  (NOT the row-stochastic form of the reference's
+//    4-state path, (c0 P_i0 + c1 P_i1) + (v_3 + c2 P_i2) with c_j = v_j - v_3, which this kernel used at first: it cancels — where
+//    the child's conditionals are peaked on state 3 and the branch is short, (P v)_i = eps v_3 comes out of v_3 - v_3 (1 - eps) with
+//    an absolute error of an ulp of v_3, a relative one of 1e-16 / eps, and negative likelihoods below eps = 1e-16:
+//    tests/test_gpu_rescale.py, the 4-state conflict trees);
 //  * NP patterns per thread share every scalar instruction, branch and wait of an entry and give the vector unit NP
 //    independent chains;
 //  * the rescaling test costs one wave ballot per finalisation unless some pattern really is out of range;
@@ -1679,27 +1682,27 @@ __global__ __launch_bounds__(256) void prune_nuc2_kernel(const int4 *__restrict_
       }
     }
   };
-  // columns 0..2 of a child's matrix = the first 12 doubles of its TRANSPOSED copy (PTm: [branch][state j][row i]): uniform
-  // address, three 32-byte scalar loads, requested one entry ahead.  (Tried and measured slower: the same through vector
+  // a child's matrix = the 16 doubles of its TRANSPOSED copy (PTm: [branch][state j][row i]): uniform
+  // address, four 32-byte scalar loads, requested one entry ahead.  (Tried and measured slower: the same through vector
   // loads — 96 bytes x 64 lanes per entry made the kernel TA-bound, 205 vs 120 us at 10^6 sites; schedule words through
   // vector loads + readfirstlane, 38 vs 27 us at 50 000 sites.)
-  auto load_P = [&](const int4 &o, double (&P)[12]) {
+  auto load_P = [&](const int4 &o, double (&P)[16]) {
     const int br = (o.x & 3) == OPK_LEAF ? (o.z & 0xffff) : o.z;
     if constexpr (LP) {
       const f64x2 *src = reinterpret_cast<const f64x2 *>(PT + (size_t)br * 16);
 #pragma unroll
-      for (int e = 0; e < 6; e++) {
+      for (int e = 0; e < 8; e++) {
         const f64x2 v = src[e];
         P[2 * e] = v[0], P[2 * e + 1] = v[1];
       }
     } else {
       const double *src = PTm + (size_t)br * 16;
 #pragma unroll
-      for (int e = 0; e < 12; e++) P[e] = src[e];
+      for (int e = 0; e < 16; e++) P[e] = src[e];
     }
   };
-  // one schedule entry: `code` = this thread's leaf codes (leaf entries), P = columns 0..2 of the child's transition matrix
-  auto entry = [&](const int4 &op, const double (&P)[12], const int (&code)[2][NP]) {
+  // one schedule entry: `code` = this thread's leaf codes (leaf entries), P = the child's transition matrix, transposed
+  auto entry = [&](const int4 &op, const double (&P)[16], const int (&code)[2][NP]) {
     const int kind = op.x & 3, parent = op.y;
     if (kind == OPK_LEAF) {
       const int nl = (op.x >> 8) & 0x7f;
@@ -1776,11 +1779,10 @@ __global__ __launch_bounds__(256) void prune_nuc2_kernel(const int4 *__restrict_
 #pragma unroll
       for (int q = 0; q < NP; q++) {
         cnt[q] += bcnt[q];
-        const double c0 = b[q][0] - b[q][3], c1 = b[q][1] - b[q][3], c2 = b[q][2] - b[q][3], c3 = b[q][3];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-          const double t0 = fma(c1, P[4 + i], c0 * P[i]);
-          const double t1 = fma(c2, P[8 + i], c3);
+          const double t0 = fma(b[q][1], P[4 + i], b[q][0] * P[i]);
+          const double t1 = fma(b[q][3], P[12 + i], b[q][2] * P[8 + i]);
           acc[q][i] *= t0 + t1;
         }
       }
@@ -1836,7 +1838,7 @@ __global__ __launch_bounds__(256) void prune_nuc2_kernel(const int4 *__restrict_
   // Programs are padded to an even entry count and followed by two no-op entries.
   // (schedule words two entries ahead: their scalar load has returned by the time they address the matrix / code loads)
   int4 opA = fetch_op(0), opB = fetch_op(1);
-  double PA[12], PB[12];
+  double PA[16], PB[16];
   int cA[2][NP], cB[2][NP];
   load_P(opA, PA);
   codes_of(opA, cA);

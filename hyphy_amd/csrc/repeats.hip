@@ -1484,7 +1484,7 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
     if (s.T != 1) return 0;
   if (!p->nuc && p->variant != 1 && !(env && atoi(env) == 2)) return 0;  // (tiny shards: the workgroup-per-tile kernel keeps the whole tree)
   // 4 states: only on request (HYPHY_HIP_REPEATS=1 / 2).  Measured, it loses: a class row is 36 bytes gathered past the L2 per pattern
-  // and generalised leaf, where prune_nuc2_kernel computes a whole node from registers for 12 multiply-adds — gtr_32x50k 35.0 us plain
+  // and generalised leaf, where prune_nuc2_kernel computes a whole node from registers for 16 multiply-adds — gtr_32x50k 35.0 us plain
   // against 16.5 (walks) + 26.0 (trunk of 5 nodes) compressed, gtr_32x1m 123.8 against 14.5 + 238.9
   if (p->nuc && !env) return 0;
   const int L = (int)p->L, I = (int)p->I, DP = p->DP;

@@ -460,37 +460,20 @@ void build_schedule_impl(hyphy_hip_partition *p, const int64_t *update_nodes, in
   }
 }
 
-// Rescaling tests only where they are needed (wave-per-tile kernel, full passes).  A rescale multiplies by an exact power
-// of 2^64, so WHERE a node is tested does not change any mantissa — only underflow has to be excluded.  A node whose
-// internal children were all tested (their per-pattern sums are >= 2^-64 after the test) and that has at most four children
-// cannot fall below 2^-256 times the spread of a conditional vector, hundreds of binary orders above the denormals: its
-// own test is skipped (OPF_NOSCALE) and its parent tests again.  The root is always tested.  Saves the cross-lane sum,
-// the ballot and their latency in front of the next product at every other level (HYPHY_HIP_SCALE_THIN=0: test everywhere).
-void thin_rescale_tests(hyphy_hip_partition *p) {
-  static const bool on = !(getenv("HYPHY_HIP_SCALE_THIN") && atoi(getenv("HYPHY_HIP_SCALE_THIN")) == 0);
-  if (!on) return;
-  const hyphy_hip_partition::View &v = p->vw();
-  const int L = v.L, I = v.I;
-  std::vector<char> tested(I, 1);
-  for (int n = 0; n < I; n++) {  // children before parents
-    bool kids_tested = true;
-    for (int c : v.children[n])
-      if (c >= L && !tested[c - L]) kids_tested = false;
-    // (mode 1: the class-table kernel tests every compressed node, so a generalised leaf counts like a tested child;
-    //  pinned states only exist in mode 0)
-    tested[n] = (n == I - 1 || !kids_tested || v.children[n].size() > 4 || (p->mode == 0 && n == p->pin_node - L)) ? 1 : 0;
-  }
-  if (p->rr_active)  // (re-rooted schedule: the nodes whose children differ from the given topology — and the new root — always test)
-    for (int n : p->rr_path) tested[n] = 1;
-  for (int4 &op : p->ops_host)
-    if ((op.x & OPF_LAST) && op.y >= 0 && op.y < I && !tested[op.y]) op.x |= OPF_NOSCALE;
-}
-
 }  // namespace
 
+// Every node of every schedule tests for rescaling when it is finalised.  (The wave-per-tile kernel's full passes used to skip the
+// test at nodes of at most four children whose internal children had all been tested, on the argument that such a node "cannot fall
+// below 2^-256 times the spread of a conditional vector".  A tested child only has its SUM at 2^-64 or more: across a branch whose
+// matrix has off-diagonal entries eps, the entries it hands up can sit at 2^-64 * eps, an untested node at (2^-64 * eps)^4, and its
+// tested parent multiplies four of those BEFORE it tests.  Observed on the kernel, balanced trees of four children per node, 61
+// states, near-identity matrices: 64 taxa at eps = 1e-30 and 256 taxa at eps = 1e-15 came back as -inf (18 of 24 and 8 of 20
+// patterns zero), 64 taxa at eps = 1e-20 with 4e-12 relative error (denormals); with a test at every node each is exact to 3e-16.
+// The reference's own scheme fails on those three trees as well, so they are not among the cases of tests/test_gpu_rescale.py; on
+// every case that is, thinned passes were correct.  No rule that skips a test is safe for every row-stochastic matrix, and on the
+// headline workload the tests cost nothing outside the run-to-run spread: profiles/rescale_thin_ab.md.)
 void build_schedule(hyphy_hip_partition *p, const int64_t *update_nodes, int64_t n_update, bool full) {
   build_schedule_impl(p, update_nodes, n_update, full);
-  if (full && !p->nuc && p->variant == 1 && !p->shards.empty() && p->shards[0].T == 1) thin_rescale_tests(p);
 }
 
 // Pattern order on the device.  A leaf edge is a per-site column gather from the leaf branch's matrix (prune.hip: leaf_gather),
