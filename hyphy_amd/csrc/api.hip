@@ -2103,6 +2103,43 @@ static int site_fits_common(hyphy_hip_partition *p, int64_t n_sets, int64_t n_gr
       }
     }
   }
+  {
+    // reach: the largest finite distance between two states in the sparsity graph of ANY non-empty subset of the templates
+    // (one BFS per state and subset: at most 15 x D sweeps).  A site whose multiplier of a template is zero, or negligible,
+    // sees the graph of the remaining templates, and taking a template away can LENGTHEN finite distances, not only cut
+    // paths (MG94: 3 in the union, 5 with the synonymous template off: ACC -> CCT).  An entry of exp(Q) first reached after d
+    // steps of R is built by the terms d, d + 1, ... of the series alone; the kernel's relative stopping criterion looks
+    // `reach` terms back (sitefit.hip).
+    int reach = 0;
+    std::vector<uint8_t> adj((size_t)D * D);
+    std::vector<int> dist(D), queue(D);
+    for (int mask = 1; mask < (1 << K); mask++) {
+      std::fill(adj.begin(), adj.end(), 0);
+      for (int64_t k = 0; k < K; k++) {
+        if (!(mask >> k & 1)) continue;
+        const double *T = p->templates_host.data() + (size_t)k * D * D;
+        for (int64_t i = 0; i < D; i++)
+          for (int64_t j = 0; j < D; j++)
+            if (j != i && T[i * D + j] > 0.) adj[i * D + j] = 1;
+      }
+      for (int64_t src = 0; src < D; src++) {
+        std::fill(dist.begin(), dist.end(), -1);
+        int head = 0, tail = 0;
+        dist[src] = 0;
+        queue[tail++] = (int)src;
+        while (head < tail) {
+          const int u = queue[head++];
+          for (int64_t v = 0; v < D; v++)
+            if (adj[(size_t)u * D + v] && dist[v] < 0) {
+              dist[v] = dist[u] + 1;
+              queue[tail++] = (int)v;
+            }
+        }
+        for (int64_t v = 0; v < D; v++) reach = std::max(reach, dist[v]);
+      }
+    }
+    fa.reach = reach;
+  }
   std::vector<int> grp(B);
   for (int64_t b = 0; b < B; b++) grp[b] = (int)branch_group[b];
   {

@@ -243,6 +243,8 @@ struct SiteFitArgs {
   int NW, L, I, ntiles, S_pad;
   int K, G, n_sets;          // templates, branch groups, parameter sets (grid.y)
   double dmax[4];            // max_i |T_k[i][i]|: the uniformisation rate of site s on branch b is sum_k x_k dmax_k
+  int reach;                 // largest finite graph distance in the sparsity pattern of any non-empty subset of the templates
+                             // (<= D - 1): the series' relative stopping criterion looks this many terms back
   const double *Timg;        // [K][NW][NKK*64] A-operand images of the templates, diagonal = -(row sum)
   const double *bcoef;       // [B][K] branch coefficients
   const int *bgroup;         // [B]    multiplier group of each branch

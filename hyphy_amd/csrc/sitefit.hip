@@ -12,9 +12,21 @@
 //       R^j v    = t_j,   t_j = t_{j-1} + (sum_k T_k (x_k o t_{j-1})) / mu      (x_k = per-site coefficient)
 // For a tile of 16 sites `T_k (x_k o t)` is a [DP x DP] x [DP x 16] product on the FP64 matrix cores with the
 // template image as the A operand — the same MFMA shape, register images and L2-resident operand stream as the
-// pruning kernel (prune.hip), only the B operand is scaled per site.  All terms are non-negative (R is a
-// stochastic matrix): no cancellation, componentwise relative accuracy — better conditioned than Taylor +
-// squaring of the full matrix, and ~D/(2 terms) times less arithmetic than sites x branches exponentials.
+// pruning kernel (prune.hip), only the B operand is scaled per site.  The terms of the sum are non-negative (R is a
+// stochastic matrix), so nothing cancels between them — better conditioned than Taylor + squaring of the full
+// matrix, and ~D/(2 terms) times less arithmetic than sites x branches exponentials.
+// What is guaranteed, and tested (tests/test_gpu_sitefit.py against tests/sitefit_ref.py): an entry of exp(Q) v keeps a
+// RELATIVE tail below kRelTailEps, however short the branch and whichever templates a site has switched off.  An entry
+// first reached after d steps of R (d substitutions: AAA -> CCC needs 3 under MG94) is of size mu^d / d! and is built
+// by the terms d, d + 1, ... alone, of which the terms d + k carry the share Pois(k; mu): stopping after term j leaves
+// it the relative tail P(Pois(mu) > j - d).  A criterion on the neglected Poisson mass alone is absolute: at mu = 1e-7
+// it fires after two terms and such an entry comes out exactly zero.  The series therefore stops when the mass beyond
+// term j is below kTailEps AND the mass beyond term j - reach is below kRelTailEps, reach = the largest finite graph
+// distance in the sparsity pattern of any non-empty subset of the templates (found by the host: api.hip; a zero or
+// negligible multiplier takes a template out of a site's graph, which can lengthen distances: 5 for MG94 without its
+// synonymous template, 3 with it).  At ordinary rates the second condition is met at once or a term or two later; on
+// short branches it keeps the series going for up to reach + 1 terms.  Exact zeros remain only where the graph of the
+// templates a site uses has no path.
 // One wave owns a 16-site tile of one parameter set and walks the whole post-order schedule; nodes flow child ->
 // parent through registers / wave-private LDS parking slots exactly as in prune_wave_kernel.
 #include "common.h"
@@ -63,7 +75,10 @@ __device__ __forceinline__ int rescale_decision(double tot, double &sc) {
 }
 
 constexpr double kMuStep = 64.0;      // uniformisation rate handled by one Poisson series (e^-64 is a normal double)
-constexpr double kTailEps = 1e-18;    // neglected Poisson mass (relative to total mass 1)
+constexpr double kTailEps = 1e-18;    // neglected Poisson mass (of total mass 1): the absolute tail of the whole vector
+constexpr double kRelTailEps = 1e-13; // Poisson mass beyond term j - reach: the relative tail of an entry up to `reach` steps of R
+                                      // away.  600 edges (a 300-taxon tree) x 1e-13 stay well inside the 1e-9 the entry point
+                                      // is held to on a site log-likelihood.
 
 template <int NW, int NP, bool MIX>
 __global__ __launch_bounds__(64, 2) void site_fit_kernel(const int4 *__restrict__ ops, const double *__restrict__ Timg,
@@ -130,9 +145,11 @@ __global__ __launch_bounds__(64, 2) void site_fit_kernel(const int4 *__restrict_
     const double mu_sub = mu / (double)n_sub, mu_sub_max = mu_max / (double)n_sub;
     const double inv_mu = mu > 0. ? 1.0 / mu : 0.;
     const double w0 = exp(-mu_sub);
+    const double w0_max = exp(-mu_sub_max);  // (uniform) Pois(0) of the tile's fastest lane: its tails bound the other lanes'
     f64x4 sum[NW];
     for (int sub = 0; sub < n_sub; sub++) {
       double wgt = w0;
+      double wlag = w0_max;  // (uniform) Pois(max(j - reach, 0); mu_sub_max)
 #pragma unroll
       for (int w = 0; w < NW; w++) sum[w] = term[w] * wgt;
       for (int j = 1;; j++) {
@@ -171,10 +188,17 @@ __global__ __launch_bounds__(64, 2) void site_fit_kernel(const int4 *__restrict_
           sum[w] += term[w] * wgt;
         }
         // remaining Poisson mass <= wgt * r / (1 - r), r = mu_sub / (j + 1) (geometric bound past the mode);
-        // uniform decision on the tile's largest rate (its weights dominate the others' from the mode on)
+        // uniform decision on the tile's largest rate (its weights dominate the others' from the mode on; its Poisson tails
+        // bound those of every slower lane).  Absolute: the mass beyond term j below kTailEps.  Relative: the mass beyond term
+        // j - reach below kRelTailEps (header) — without it a short branch loses its multi-substitution entries, and a slow
+        // site's value would depend on how fast its tile neighbours are.
         const double r = mu_sub_max / (double)(j + 1);
         double wmax = wave_max(wgt);
-        if (r < 0.5 && wmax * r / (1.0 - r) < kTailEps) break;
+        if (j > a.reach) wlag *= mu_sub_max / (double)(j - a.reach);
+        if (r < 0.5 && wmax * r / (1.0 - r) < kTailEps && j >= a.reach) {
+          const double rl = mu_sub_max / (double)(j - a.reach + 1);
+          if (rl < 0.5 && wlag * rl / (1.0 - rl) < kRelTailEps) break;
+        }
         if (j > 4096) break;  // (cannot happen: mu_sub_max <= kMuStep)
       }
 #pragma unroll

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from tests import common
+from tests.sitefit_ref import oracle_site_fit_reference as _site_fit_reference  # the oracle route of the per-site fits
 
 pytestmark = pytest.mark.gpu
 
@@ -851,26 +852,6 @@ def _site_fit_case(D, taxa, sites, K, G, n_sets, seed, caterpillar=False, balanc
     smult[0, :3] = 0.0          # sites whose every rate is zero
     smult[-1, 3:6, :, 0] = 0.0  # alpha = 0
     return flat, codes, ambig, pi, T, bgroup, bcoef, smult
-
-
-def _site_fit_reference(D, flat, codes, ambig, pi, T, bgroup, bcoef, smult):
-    """The reference's way (FEL.bf:609+): one single-site likelihood function per site — exponentiate every branch's
-    own rate matrix (oracle restatement of _Matrix::Exponentiate), then prune that one pattern."""
-    from oracle import oracle
-    n_sets, S, G, K = smult.shape
-    B = flat.n_branches
-    nodes = np.arange(B, dtype=np.int64)
-    out = np.zeros((n_sets, S))
-    idx = np.arange(D)
-    for st in range(n_sets):
-        for s in range(S):
-            x = smult[st, s][bgroup] * bcoef  # [B][K]
-            Q = np.einsum("bk,kij->bij", x, T)
-            Q[:, idx, idx] = -Q.sum(2)
-            op = oracle.OraclePartition(D, flat.flat_parents, flat.L, codes[:, s:s + 1], ambig, np.ones(1, dtype=np.int64))
-            op.set_P(nodes, oracle.expm(Q, True))
-            out[st, s] = op.site_log_likelihoods(nodes, pi)[0]
-    return out
 
 
 @pytest.mark.parametrize("name,kw", [
