@@ -387,6 +387,7 @@ int enqueue_eval(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch, boo
     if (p->nuc && p->mode == 0 && (!use_gen || p->nucgen_small) && prune_nuc_folds_expm((int)p->L, s.S_pad, n_ops_planned) && !(q_from_templates && !ea.coeffs)) {
       folded_expm = ea;  // (4 states, small shard: the pruning launch computes the exponentials itself)
       have_folded = true;
+      set_last_expm_kernel("");
     } else {
       coeffs_consumed = launch_expm(ea, s.stream);
     }
@@ -815,6 +816,8 @@ extern "C" {
 const char *hyphy_hip_last_error(void) { return g_last_error.c_str(); }
 
 int hyphy_hip_prune_launches(hyphy_hip_partition *p) { return p ? (int)std::max<size_t>(1, p->levels.size()) : 0; }
+
+const char *hyphy_hip_last_expm_kernel(void) { return last_expm_kernel(); }
 
 const char *hyphy_hip_prune_kernel_name(const hyphy_hip_partition *p) {
   if (!p) return "";

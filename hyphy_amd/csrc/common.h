@@ -323,6 +323,8 @@ struct BcArgs {
 void launch_transpose_frag(const double *src_image, double *dst_image, const double *row_scale, int NW, hipStream_t stream);
 void launch_bc_eval(const BcArgs &a, hipStream_t stream);
 bool launch_expm(const ExpmArgs &a, hipStream_t stream);  // true: fused-construction coefficients were copied at launch
+const char *last_expm_kernel();                 // the kernel the calling thread's last launch_expm ran
+void set_last_expm_kernel(const char *name);    // ("" when the exponentials are folded into a pruning launch)
 void launch_mix_images(const double *P, const int *off, const double *w, const int32_t *slots, int n, int D, double *Pfrag,
                        double *PTg, double *Prow, hipStream_t stream, double *PTrow = nullptr);
 void launch_site_fit(const SiteFitArgs &a, hipStream_t stream);

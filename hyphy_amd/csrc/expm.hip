@@ -4,7 +4,8 @@
 //
 // Same numerical contract as the reference (scaling by a power of two, Taylor series,
 // diag_populator forcing row sums to 1 before AND after the squarings, restart with a 100x
-// larger scale when a diagonal exceeds 1, early exit from the squarings), re-designed for the
+// larger scale when a diagonal exceeds 1 — unless the rate matrix itself has a positive diagonal entry, which no scale mends: that
+// fails at once, where the reference restarts its way to the identity —, early exit from the squarings), re-designed for the
 // matrix cores: one workgroup per matrix, everything resident in LDS/registers, every product a
 // DPxDP FP64 MFMA GEMM (v_mfma_f64_16x16x4_f64).  The degree-12 Taylor polynomial is evaluated
 // by Paterson-Stockmeyer in 5 products instead of the reference's one sparse product per term
@@ -279,6 +280,23 @@ __global__ __launch_bounds__(64 * NT * CS) void expm_mfma_kernel(ExpmArgs a) {
           if (c0 + c == w && sl == 4 * r + g) f.t[c][r] += v;
     };
 
+    // (cold path, behind a failed verification) a positive diagonal entry is no rate: exp(Q_ii / 2^p) > 1 at every scale until it rounds
+    // to 1 — the restarts would end, like the reference's, at the identity.  Workgroup-wide OR through `flag`; called uniformly.
+    auto positive_diagonal = [&]() -> bool {
+      bool pos = false;
+#pragma unroll
+      for (int c = 0; c < NTW; c++)
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+          if (c0 + c == w && sl == 4 * r + g && Qr.t[c][r] > 0.) pos = true;
+      __syncthreads();
+      if (threadIdx.x == 0) *flag = 0;
+      __syncthreads();
+      if (pos) atomicOr(flag, 1);
+      __syncthreads();
+      return *flag != 0;
+    };
+
     Frag<NTW> R;
     bool done = false, failed = nan_in || !(mnorm < 1e300);
     for (int attempt = 0; attempt < 48 && !done && !failed; attempt++) {
@@ -314,7 +332,7 @@ __global__ __launch_bounds__(64 * NT * CS) void expm_mfma_kernel(ExpmArgs a) {
       if (prof) g_expm_prof[3] = clock64();
       if (!diag_fix<NT, CS>(R, w, h, c0, g, sl, flag, rowpart)) {  // matrix.cpp:5854-5864: restart, scale_to *= 100
         p += 7;
-        if (p > 900) failed = true;
+        if (p > 900 || positive_diagonal()) failed = true;
         continue;
       }
       double last_diff = 0.;
@@ -341,7 +359,7 @@ __global__ __launch_bounds__(64 * NT * CS) void expm_mfma_kernel(ExpmArgs a) {
       }
       if (p > 0 && !diag_fix<NT, CS>(R, w, h, c0, g, sl, flag, rowpart)) {
         p += 7;
-        if (p > 900) failed = true;
+        if (p > 900 || positive_diagonal()) failed = true;
         continue;
       }
       done = true;
@@ -618,6 +636,20 @@ __global__ __launch_bounds__(512) void expm64_kernel(ExpmArgs a, CoefInline ci) 
       // ================= one workgroup, whole matrix: scaling, Taylor, squarings, restarts =================
       bool done = false;
       f64x4 Rf[2];
+      auto positive_diagonal = [&]() -> bool {  // (cold path, see expm_mfma_kernel: such a matrix fails at once instead of restarting its way to the identity)
+        bool pos = false;
+#pragma unroll
+        for (int c = 0; c < 2; c++)
+#pragma unroll
+          for (int r = 0; r < 4; r++)
+            if (fc0 + c == fw && sl == 4 * r + g && Qf[c][r] > 0.) pos = true;
+        __syncthreads();
+        if (tid == 0) *flag = 0;
+        __syncthreads();
+        if (pos) atomicOr(flag, 1);
+        __syncthreads();
+        return *flag != 0;
+      };
       for (int attempt = 0; attempt < 48 && !done && !failed; attempt++) {
         const double scale = ldexp(1.0, -p);
         f64x4 Xr[2], X2[2], X3[2], acc[2];
@@ -693,7 +725,7 @@ __global__ __launch_bounds__(512) void expm64_kernel(ExpmArgs a, CoefInline ci) 
         };
         if (!fix()) {  // matrix.cpp:5854-5864: restart, scale_to *= 100
           p += 7;
-          if (p > 900) failed = true;
+          if (p > 900 || positive_diagonal()) failed = true;
           continue;
         }
         double last_diff = 0.;
@@ -722,7 +754,7 @@ __global__ __launch_bounds__(512) void expm64_kernel(ExpmArgs a, CoefInline ci) 
         }
         if (p > 0 && !fix()) {
           p += 7;
-          if (p > 900) failed = true;
+          if (p > 900 || positive_diagonal()) failed = true;
           continue;
         }
         done = true;
@@ -1052,9 +1084,15 @@ bool fill_coef_inline(ExpmArgs &b, CoefInline &ci) {
   return b.coef_inline != 0;
 }
 
+// name of the kernel the calling thread's last launch_expm ran (hyphy_hip_last_expm_kernel); "": none, or folded into a pruning launch
+static thread_local const char *t_last_expm_kernel = "";
+const char *last_expm_kernel() { return t_last_expm_kernel; }
+void set_last_expm_kernel(const char *name) { t_last_expm_kernel = name; }
+
 bool launch_expm(const ExpmArgs &a, hipStream_t stream) {
   if (a.n <= 0) return false;
   if (a.D == 4 && !a.Pfrag && !a.PTg) {
+    t_last_expm_kernel = "expm_nuc_kernel";
     hipLaunchKernelGGL(expm_nuc_kernel, dim3((a.n + 63) / 64), dim3(64), 0, stream, a);
     return false;
   }
@@ -1068,9 +1106,11 @@ bool launch_expm(const ExpmArgs &a, hipStream_t stream) {
   const size_t lds = (size_t)(3 * DP * LD + 2 * DP + 8 + 2 * DP) * sizeof(double);
   switch (NT) {
     case 1:
+      t_last_expm_kernel = "expm_mfma_kernel<1,1>";
       hipLaunchKernelGGL((expm_mfma_kernel<1, 1>), dim3(a.n), dim3(64), lds, stream, a);
       break;
     case 2:
+      t_last_expm_kernel = "expm_mfma_kernel<2,2>";
       hipLaunchKernelGGL((expm_mfma_kernel<2, 2>), dim3(a.n), dim3(256), lds, stream, a);
       break;
     case 3:
@@ -1079,6 +1119,7 @@ bool launch_expm(const ExpmArgs &a, hipStream_t stream) {
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_done[dev][3] = true;
       }
+      t_last_expm_kernel = "expm_mfma_kernel<3,1>";
       hipLaunchKernelGGL((expm_mfma_kernel<3, 1>), dim3(a.n), dim3(192), lds, stream, a);
       break;
     default: {
@@ -1089,6 +1130,7 @@ bool launch_expm(const ExpmArgs &a, hipStream_t stream) {
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
           attr_done[dev][4] = true;
         }
+        t_last_expm_kernel = "expm_mfma_kernel<4,2>";
         hipLaunchKernelGGL((expm_mfma_kernel<4, 2>), dim3(a.n), dim3(512), lds, stream, a);
         break;
       }
@@ -1119,6 +1161,7 @@ bool launch_expm(const ExpmArgs &a, hipStream_t stream) {
       b.fixed_degree = fixed12 ? 1 : 0;
       CoefInline ci;
       if (b.templates_pad) fill_coef_inline(b, ci);
+      t_last_expm_kernel = H == 4 ? "expm64_kernel<4>" : (H == 2 ? "expm64_kernel<2>" : "expm64_kernel<1>");
       switch (H) {
         case 4: hipLaunchKernelGGL((expm64_kernel<4>), dim3(4 * b.n), dim3(512), lds64, stream, b, ci); break;
         case 2: hipLaunchKernelGGL((expm64_kernel<2>), dim3(2 * b.n), dim3(512), lds64, stream, b, ci); break;

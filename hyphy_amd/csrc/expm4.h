@@ -1,6 +1,6 @@
 // 4-state matrix exponential: one thread, everything in registers (shared by expm_nuc_kernel and — folded into the pruning
 // launch of small shards — prune_nuc2_kernel).  Same contract as the MFMA kernels: scaling by a power of two, Taylor polynomial of
-// degree 12 / 9 / 6 by the scaled norm (Paterson-Stockmeyer), diag_populator before and after the squarings, restart with a 2^7 larger scale when a diagonal exceeds 1, early
+// degree 12 / 9 / 6 by the scaled norm (Paterson-Stockmeyer), diag_populator before and after the squarings, restart with a 2^7 larger scale when a diagonal exceeds 1 (failure at once when the rate matrix has a positive diagonal entry), early
 // exit from the squarings, sticky status + NaN matrix on failure (matrix.cpp:5537-5951).
 // (also compiled as embedded source by the run-time generated kernels of nucgen.hip — the Makefile turns this file into a string
 //  constant: nothing in it may need more than the names hyhip::ExpmArgs gives it there)
@@ -108,7 +108,8 @@ __device__ __forceinline__ void expm4_one(const ExpmArgs &a, int m, double (&R)[
       }
       if (!diag_fix4(R)) {
         p += 7;
-        if (p > 900) failed = true;
+        // a positive diagonal entry is no rate: exp(Q_ii / 2^p) > 1 at every scale until it rounds to 1, and the restarts would end at the identity
+        if (p > 900 || Q[0] > 0. || Q[5] > 0. || Q[10] > 0. || Q[15] > 0.) failed = true;
         continue;
       }
       double last_diff = 0.;
@@ -125,7 +126,7 @@ __device__ __forceinline__ void expm4_one(const ExpmArgs &a, int m, double (&R)[
       }
       if (p > 0 && !diag_fix4(R)) {
         p += 7;
-        if (p > 900) failed = true;
+        if (p > 900 || Q[0] > 0. || Q[5] > 0. || Q[10] > 0. || Q[15] > 0.) failed = true;
         continue;
       }
       done = true;

@@ -25,7 +25,7 @@ EXPORTS = [
     "hyphy_hip_prune_kernel_name", "hyphy_hip_branch_cache_build", "hyphy_hip_branch_cache_evaluate",
     "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
     "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
-    "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error",
+    "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error", "hyphy_hip_last_expm_kernel",
     "hyphy_hip_version",
 ]
 
@@ -166,6 +166,8 @@ def load():
     lib.hyphy_hip_plan_nucgen.restype = C.c_int64
     lib.hyphy_hip_plan_nucgen.argtypes = [C.c_int64, C.c_int64, lp, lp, C.c_int64, C.c_char_p, C.c_int64, lp]
     lib.hyphy_hip_last_error.restype = C.c_char_p
+    lib.hyphy_hip_last_expm_kernel.restype = C.c_char_p
+    lib.hyphy_hip_last_expm_kernel.argtypes = []
     lib.hyphy_hip_version.restype = C.c_char_p
     _lib = lib
     return lib
@@ -319,6 +321,12 @@ def expm_batch(Q: np.ndarray) -> np.ndarray:
     P = np.empty_like(Qb)
     _check(load().hyphy_hip_expm_batch(Qb.shape[1], Qb.shape[0], _d(Qb), _d(P)))
     return P[0] if single else P
+
+
+def last_expm_kernel() -> str:
+    """The matrix-exponential kernel this thread's last launch ran ("expm64_kernel<2>", "expm_mfma_kernel<4,2>", "expm_nuc_kernel",
+    ...); "" before the first launch and when the exponentials were folded into a pruning launch."""
+    return load().hyphy_hip_last_expm_kernel().decode()
 
 
 class HipPartition:

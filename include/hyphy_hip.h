@@ -114,6 +114,9 @@ void hyphy_hip_destroy(hyphy_hip_partition *p);
  *                   (likefunc.cpp:11123).  -INFINITY if a pattern has likelihood 0
  *                   (tree_evaluator.cpp:4094-4112); NaN propagates (adapter then calls
  *                   _TerminateAndDump as tree_evaluator.cpp:4142 does).
+ *                   A matrix the device cannot exponentiate (NaN, overflow, or a rate matrix with a POSITIVE diagonal entry —
+ *                   which the reference restarts its way to the identity for, matrix.cpp:5854-5864) is a hard error (< 0,
+ *                   "Failed to compute a valid transition matrix"); an asynchronous evaluation's log-L is then NaN.
  *   site_lik_out    optional [S], pattern-indexed == storageVec (tree_evaluator.cpp:4080):
  *                   per-pattern likelihood l_s (NOT log), scaled so that the true value is
  *                   l_s * 2^(-64*c_s)
@@ -451,6 +454,12 @@ int hyphy_hip_prune_launches(hyphy_hip_partition *p);
  * "class_table_team_kernel" in front of it, and answer "trunk_walk_kernel" once their full passes run the trunk as one
  * row-split walk per tile (r06; first passes, partial updates and pinned states keep the pruning kernels). */
 const char *hyphy_hip_prune_kernel_name(const hyphy_hip_partition *p);
+/* Name of the matrix-exponential kernel the calling thread's last launch ran, as it appears in a rocprofv3 kernel trace:
+ * "expm_nuc_kernel" (4 states, row-major images), "expm_mfma_kernel<1,1>" / "<2,2>" / "<3,1>" (up to 16 / 32 / 48 states),
+ * "expm64_kernel<1>" / "<2>" / "<4>" (49-64 states: 1, 2 or 4 workgroups per matrix, by batch size and compute-unit count) or
+ * "expm_mfma_kernel<4,2>" (49-64 states under HYPHY_HIP_EXPM=0).  "" before the first launch and when the exponentials
+ * were folded into a 4-state pruning launch.  Static string. */
+const char *hyphy_hip_last_expm_kernel(void);
 
 /* What the schedule tuner measured for this partition ("" before it ran): on the first steady-state full pass the
  * library times the (idempotent) pruning pass under each candidate cut of the tree — level-peeled fragments, or chains

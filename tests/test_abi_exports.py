@@ -23,6 +23,18 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), n
     assert sorted(hip.EXPORTS) == names
+    assert "hyphy_hip_last_expm_kernel" in names
+
+
+def test_last_expm_kernel_is_empty_before_any_launch():
+    """A fresh thread has launched nothing: the name is the empty string, never a null pointer."""
+    import threading
+    from hyphy_amd import hip
+    got = []
+    t = threading.Thread(target=lambda: got.append(hip.last_expm_kernel()))
+    t.start()
+    t.join()
+    assert got == [""]
 
 
 def test_no_device_means_hard_error_not_fallback():
