@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests import scalefree as sf
+from tests.hold import _hold, _site  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -32,29 +33,6 @@ def _mk(cs, C=1):
 
 def _nodes(cs):
     return np.arange(len(cs["flat_parents"]) - 1, dtype=np.int64)
-
-
-def _site(lik, sc):
-    with np.errstate(divide="ignore"):
-        return np.log(lik) - sc * LOG_SCALER
-
-
-def _hold(what, got, want_site, want_total):
-    """got = (log-L, likelihoods, exponents) of an evaluation with per_site=True."""
-    ll, lik, sc = got
-    assert sc.dtype == np.int64 and np.all(np.abs(sc) < 4096), (what, sc)
-    assert np.all(np.isfinite(lik)) and np.all(lik >= 0), (what, lik)
-    site = _site(lik, sc)
-    assert np.array_equal(np.isneginf(site), np.isneginf(want_site)), (what, np.flatnonzero(np.isneginf(site) != np.isneginf(want_site)))
-    fin = np.isfinite(want_site)
-    dev = np.abs(site[fin] - want_site[fin])
-    worst = float(np.max(dev / (RTOL * np.abs(want_site[fin]) + ATOL))) if fin.any() else 0.0
-    print(f"{what}: largest per-pattern deviation / allowance = {worst:.3f}; log-L {ll!r} against {want_total!r}")
-    assert worst <= 1.0, (what, worst, int(np.argmax(dev)))
-    if np.isneginf(want_total):
-        assert ll == -np.inf, (what, ll)
-    else:
-        assert abs(ll - want_total) <= RTOL * abs(want_total) + ATOL, (what, ll, want_total)
 
 
 _refs = {}
