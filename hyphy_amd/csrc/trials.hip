@@ -1,0 +1,606 @@
+// Every branch's trial likelihoods from one outside pass — the device counterpart of the finite-difference gradient of
+// _LikelihoodFunction::ComputeGradient (likefunc.cpp:7025-7109), which re-evaluates the partition once per independent parameter.
+// A parameter local to one branch changes that branch's transition matrix only, and with the branch's outside vector in hand
+//   V_c = U_p * prod_{s in children(p), s != c} E_s        (U_root = pi, U_c = P_c^T V_c: the walk of marginal.hip)
+// the likelihood under ANY replacement M of the matrix of branch c is one contraction per pattern,
+//   L_s(P_c -> M) = sum_i V_c[i] (M in_c)[i],    2^64 exponent = exponent(V_c) + exponent(in_c),
+// in_c the stored conditional of an internal child, the state indicator / ambiguity vector of a leaf.
+//
+// Phase 1 (outside_store_kernel<NW>, outside_store_nuc_kernel): the pre-order walk of marginal_mfma_kernel over the same program
+// (plan_marginal_program), one wave per 16-pattern tile, with the same prefix / suffix sibling products, rescaling and transposed
+// images (outside.h).  It keeps V_c and its exponent of EVERY child, leaves included, and accumulates no support.
+// Phase 2 (branch_trials_kernel<NW>, branch_trials_nuc_kernel): one wave per (branch with at least one trial, tile), the tile the
+// fastest grid index — the workgroups that run together read the same trial images.  V_c and in_c are loaded once; every trial of
+// the branch is one [D x D] x [D x 16] product on the FP64 MFMA and a weighted row sum.  Classes run one launch after another and
+// are mixed by weight with their exponents aligned; the last class's launch leaves one partial sum per (trial, tile).
+// Reduction (trials_reduce_kernel): one wave per trial, combine.h's fixed-order compensated sum over the partial sums.
+// Nothing here joins by order of arrival: two identical calls give identical bits.
+//
+// Tiles are independent in both phases: phases 1-2 run over chunks of tiles so that the V scratch ([B][tiles of the chunk][TILE]
+// doubles) stays within HYPHY_HIP_TRIALS_MB (default 1024, read at every call, never less than one tile).  All scratch comes from the
+// pool and goes back before the call returns.  The partition's matrices, images, schedules and caches are not written.
+// 4 states: one thread per pattern over the plane layout and row-major matrices; a "tile" of the chunking is then one wave's
+// 64 patterns.
+#include "combine.h"
+#include "devutil.h"
+#include "outside.h"
+#include "partition.h"
+
+using namespace hyhip;
+
+namespace hyhip {
+namespace {
+
+struct OutsideStore {  // where phase 1 keeps what it computes: blocks of one chunk of tiles, indexed by the tile within the chunk
+  int tile0, ct;       // first tile of the chunk, tiles of the scratch blocks
+  double *V;           // [B][ct][TILE]
+  int32_t *Vcnt;       // [B][ct][16]
+};
+
+// marginal_mfma_kernel's walk (a.U, a.Ucnt, a.work, a.wcnt: chunk-sized blocks), keeping the outside vector of every branch
+template <int NW>
+__global__ __launch_bounds__(64) void outside_store_kernel(MargArgs a, OutsideStore o) {
+  constexpr int NKK = 4 * NW, TILE = NKK * 64;
+  const int lane = threadIdx.x, g = lane >> 4, sl = lane & 15;
+  const int lt = blockIdx.x, tile = o.tile0 + lt;
+  double *work = a.work + (size_t)lt * 2 * a.maxk * TILE;
+  int32_t *wcnt = a.wcnt + (size_t)lt * 2 * a.maxk * 16;
+  for (int pc = 0; pc < a.n_prog;) {
+    const int4 h = a.prog[pc];
+    const int node = h.y, k = h.z;
+    double pre[NKK];
+    int pcnt = 0;
+    if (h.w) {  // the root: U = pi
+#pragma unroll
+      for (int kk = 0; kk < NKK; kk++) pre[kk] = a.pi[4 * kk + g];
+    } else {
+      ld_vec<NKK>(a.U + ((size_t)node * o.ct + lt) * TILE, lane, pre);
+      pcnt = a.Ucnt[((size_t)node * o.ct + lt) * 16 + sl];
+    }
+    // prefix pass: slot 2i = U_p * prod_{j < i} E_j, slot 2i + 1 = E_i
+    for (int i = 0; i < k; i++) {
+      const int4 ce = a.prog[pc + 1 + i];
+      double E[NKK];
+      int ecnt;
+      edge_product<NW>(a, ce, tile, lane, E, ecnt);
+      st_vec<NKK>(work + (size_t)(2 * i) * TILE, lane, pre);
+      st_vec<NKK>(work + (size_t)(2 * i + 1) * TILE, lane, E);
+      wcnt[(2 * i) * 16 + sl] = pcnt;  // (every lane of the pattern stores the same word: each reads back its own store)
+      wcnt[(2 * i + 1) * 16 + sl] = ecnt;
+#pragma unroll
+      for (int kk = 0; kk < NKK; kk++) pre[kk] *= E[kk];
+      pcnt += ecnt;
+      rescale_vec<NKK>(pre, pcnt);
+    }
+    // suffix pass, children in reverse order
+    double suf[NKK];
+#pragma unroll
+    for (int kk = 0; kk < NKK; kk++) suf[kk] = 1.;
+    int scnt = 0;
+    for (int i = k - 1; i >= 0; i--) {
+      const int4 ce = a.prog[pc + 1 + i];
+      double V[NKK];
+      ld_vec<NKK>(work + (size_t)(2 * i) * TILE, lane, V);
+#pragma unroll
+      for (int kk = 0; kk < NKK; kk++) V[kk] *= suf[kk];
+      int vcnt = wcnt[(2 * i) * 16 + sl] + scnt;
+      rescale_vec<NKK>(V, vcnt);
+      st_vec<NKK>(o.V + ((size_t)ce.y * o.ct + lt) * TILE, lane, V);
+      o.Vcnt[((size_t)ce.y * o.ct + lt) * 16 + sl] = vcnt;
+      if (ce.z >= 0) {
+        double U[NKK];
+        mfma_product<NW>(a.PT + (size_t)ce.y * 16 * NW * 16 * NW, V, lane, U);
+        rescale_vec<NKK>(U, vcnt);
+        st_vec<NKK>(a.U + ((size_t)ce.z * o.ct + lt) * TILE, lane, U);
+        a.Ucnt[((size_t)ce.z * o.ct + lt) * 16 + sl] = vcnt;
+      }
+      if (i > 0) {
+        double E[NKK];
+        ld_vec<NKK>(work + (size_t)(2 * i + 1) * TILE, lane, E);
+#pragma unroll
+        for (int kk = 0; kk < NKK; kk++) suf[kk] *= E[kk];
+        scnt += wcnt[(2 * i + 1) * 16 + sl];
+        rescale_vec<NKK>(suf, scnt);
+      }
+    }
+    pc += 1 + k;
+  }
+}
+
+// 4 states: marginal_nuc_kernel's walk over patterns [s0, s0 + n) (a.U, a.Ucnt, a.work, a.wcnt, V, Vcnt: planes of `cs` patterns)
+__global__ __launch_bounds__(256) void outside_store_nuc_kernel(MargNucArgs a, int s0, int n, int cs, double *__restrict__ Vout,
+                                                                int32_t *__restrict__ Vcnt) {
+  const int ls = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ls >= n) return;
+  const size_t s = (size_t)s0 + ls, SP = a.S_pad, CS = (size_t)cs;
+  for (int pc = 0; pc < a.n_prog;) {
+    const int4 h = a.prog[pc];
+    const int node = h.y, k = h.z;
+    double pre[4];
+    int pcnt = 0;
+    if (h.w) {
+      for (int j = 0; j < 4; j++) pre[j] = a.pi[j];
+    } else {
+      for (int j = 0; j < 4; j++) pre[j] = a.U[((size_t)node * 4 + j) * CS + ls];
+      pcnt = a.Ucnt[(size_t)node * CS + ls];
+    }
+    for (int i = 0; i < k; i++) {
+      const int4 ce = a.prog[pc + 1 + i];
+      const double *P = a.P + (size_t)ce.y * 16;
+      double in[4], E[4];
+      int ecnt = 0;
+      if (ce.z >= 0) {
+        for (int j = 0; j < 4; j++) in[j] = a.partials[((size_t)ce.z * 4 + j) * SP + s];
+        ecnt = a.counts[(size_t)ce.z * SP + s];
+      } else {
+        nuc_leaf_vec(a, (int)a.codes[(size_t)ce.y * SP + s], in);
+      }
+      for (int x = 0; x < 4; x++) E[x] = P[4 * x] * in[0] + P[4 * x + 1] * in[1] + P[4 * x + 2] * in[2] + P[4 * x + 3] * in[3];
+      for (int j = 0; j < 4; j++) {
+        a.work[((size_t)(2 * i) * 4 + j) * CS + ls] = pre[j];
+        a.work[((size_t)(2 * i + 1) * 4 + j) * CS + ls] = E[j];
+        pre[j] *= E[j];
+      }
+      a.wcnt[(size_t)(2 * i) * CS + ls] = pcnt;
+      a.wcnt[(size_t)(2 * i + 1) * CS + ls] = ecnt;
+      pcnt += ecnt;
+      rescale4(pre, pcnt);
+    }
+    double suf[4] = {1., 1., 1., 1.};
+    int scnt = 0;
+    for (int i = k - 1; i >= 0; i--) {
+      const int4 ce = a.prog[pc + 1 + i];
+      const double *P = a.P + (size_t)ce.y * 16;
+      double V[4];
+      for (int j = 0; j < 4; j++) V[j] = a.work[((size_t)(2 * i) * 4 + j) * CS + ls] * suf[j];
+      int vcnt = a.wcnt[(size_t)(2 * i) * CS + ls] + scnt;
+      rescale4(V, vcnt);
+      for (int j = 0; j < 4; j++) Vout[((size_t)ce.y * 4 + j) * CS + ls] = V[j];
+      Vcnt[(size_t)ce.y * CS + ls] = vcnt;
+      if (ce.z >= 0) {
+        double U[4];
+        for (int y = 0; y < 4; y++) U[y] = P[y] * V[0] + P[4 + y] * V[1] + P[8 + y] * V[2] + P[12 + y] * V[3];
+        rescale4(U, vcnt);
+        for (int j = 0; j < 4; j++) a.U[((size_t)ce.z * 4 + j) * CS + ls] = U[j];
+        a.Ucnt[(size_t)ce.z * CS + ls] = vcnt;
+      }
+      if (i > 0) {
+        for (int j = 0; j < 4; j++) suf[j] *= a.work[((size_t)(2 * i + 1) * 4 + j) * CS + ls];
+        scnt += a.wcnt[(size_t)(2 * i + 1) * CS + ls];
+        rescale4(suf, scnt);
+      }
+    }
+    pc += 1 + k;
+  }
+}
+
+struct TrialArgs {
+  int NW, L, S_pad, ntiles, tile0, ct;  // (4 states: tiles of 64 patterns, ntiles unused)
+  int C, cls, first, last, b0;          // classes of a trial, class of this launch, it is the first / the last one, first branch of the grid
+  double w;                             // weight of this class (1 when C == 1)
+  const int *branch;                    // [branches with a trial] node codes
+  const int *tr_off, *tr_idx;           // trials of branch k: tr_idx[tr_off[k] .. tr_off[k + 1])
+  const double *img;                    // [n_trials][C] trial matrices: A-operand images (4 states: [16] row-major)
+  const double *V;                      // phase 1's blocks of this chunk
+  const int32_t *Vcnt;
+  const double *partials;               // this class
+  const int32_t *counts;
+  const int16_t *codes_tile, *codes;    // [ntiles][L][16] / (4 states) [L][S_pad]
+  const double *ambig, *freq;
+  double *lik;                          // [n_trials][S_pad] per pattern: classes mixed so far
+  int32_t *cnt;
+  double *part_sum;                     // [n_trials][part_stride] per (trial, tile): sum_s f_s log l_s, sum_s f_s c_s, flags
+  long long *part_cnt;
+  int *part_flag;
+  int part_stride;
+};
+
+// this class's value (l, exponent e) of pattern q into the mix of the classes before it, aligned on the smaller exponent (the larger
+// scale), as accumulate() of marginal.hip aligns its numerators
+__device__ __forceinline__ void mix_in(const TrialArgs &a, size_t q, double &l, int &e) {
+  l *= a.w;
+  if (a.first) return;
+  const int e_old = a.cnt[q], e_new = min(e_old, e);
+  l = a.lik[q] * ldexp(1.0, -64 * (e_old - e_new)) + l * ldexp(1.0, -64 * (e - e_new));
+  e = e_new;
+}
+
+// the pattern's term of the trial's total (bc_eval_kernel's rule: 1 a zero likelihood, 2 not a number)
+__device__ __forceinline__ void site_term(double l, int e, double f, double &wsum, long long &wcnt, int &wflag) {
+  if (f == 0.) return;
+  if (l != l || isinf(l)) wflag |= 2;
+  else if (l <= 0.) wflag |= 1;
+  else {
+    wsum += log(l) * f;
+    wcnt += (long long)e * (long long)f;
+  }
+}
+
+template <int NW>
+__global__ __launch_bounds__(64) void branch_trials_kernel(TrialArgs a) {
+  constexpr int NKK = 4 * NW, DP = 16 * NW, TILE = NKK * 64;
+  const int lane = threadIdx.x, g = lane >> 4, sl = lane & 15;
+  const int lt = blockIdx.x, tile = a.tile0 + lt, site = tile * 16 + sl;
+  const int bi = a.b0 + blockIdx.y, node = a.branch[bi];
+  double V[NKK], in[NKK];
+  ld_vec<NKK>(a.V + ((size_t)node * a.ct + lt) * TILE, lane, V);
+  int bcnt = a.Vcnt[((size_t)node * a.ct + lt) * 16 + sl];
+  int c = 0;
+  bool gather = false;
+  if (node >= a.L) {
+    ld_vec<NKK>(a.partials + ((size_t)(node - a.L) * a.ntiles + tile) * TILE, lane, in);
+    bcnt += a.counts[(size_t)(node - a.L) * a.S_pad + site];
+  } else {
+    c = (int)a.codes_tile[((size_t)tile * a.L + node) * 16 + sl];
+    gather = !__any(c < 0);
+#pragma unroll
+    for (int kk = 0; kk < NKK; kk++) in[kk] = c >= 0 ? (4 * kk + g == c ? 1. : 0.) : a.ambig[(size_t)(-c - 1) * DP + 4 * kk + g];
+  }
+  const double f = a.freq[site];
+  for (int k = a.tr_off[bi]; k < a.tr_off[bi + 1]; k++) {
+    const int t = a.tr_idx[k];
+    const double *M = a.img + ((size_t)t * a.C + a.cls) * DP * DP;
+    double E[NKK];
+    if (gather) {  // column M[.][code] out of the A-operand image: M[r][c] sits in row block r >> 4 at k-step c >> 2, lane (c & 3) * 16 + (r & 15)
+#pragma unroll
+      for (int w = 0; w < NW; w++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) E[4 * w + r] = M[w * TILE + frag_index(c >> 2, (c & 3) * 16 + 4 * r + g)];
+    } else {
+      mfma_product<NW>(M, in, lane, E);
+    }
+    double s = 0.;
+#pragma unroll
+    for (int kk = 0; kk < NKK; kk++) s += V[kk] * E[kk];
+    s = row_sum4(s);
+    double wsum = 0.;
+    long long wcnt = 0;
+    int wflag = 0;
+    if (g == 0) {
+      const size_t q = (size_t)t * a.S_pad + site;
+      int e = bcnt;
+      mix_in(a, q, s, e);
+      a.lik[q] = s;
+      a.cnt[q] = e;
+      if (a.last) site_term(s, e, f, wsum, wcnt, wflag);
+    }
+    if (a.last) {
+#pragma unroll
+      for (int off = 8; off > 0; off >>= 1) {
+        wsum += __shfl_xor(wsum, off);
+        wcnt += __shfl_xor(wcnt, off);
+        wflag |= __shfl_xor(wflag, off);
+      }
+      if (lane == 0) {
+        const size_t pq = (size_t)t * a.part_stride + tile;
+        a.part_sum[pq] = wsum;
+        a.part_cnt[pq] = wcnt;
+        a.part_flag[pq] = wflag;
+      }
+    }
+  }
+}
+
+// 4 states: one thread per pattern, one wave per (branch, 64 patterns)
+__global__ __launch_bounds__(64) void branch_trials_nuc_kernel(TrialArgs a) {
+  const int lane = threadIdx.x;
+  const int lt = blockIdx.x, tile = a.tile0 + lt;
+  const size_t ls = (size_t)lt * 64 + lane, s = (size_t)tile * 64 + lane, CS = (size_t)a.ct * 64, SP = a.S_pad;
+  const int bi = a.b0 + blockIdx.y, node = a.branch[bi];
+  double V[4], in[4];
+  for (int j = 0; j < 4; j++) V[j] = a.V[((size_t)node * 4 + j) * CS + ls];
+  int bcnt = a.Vcnt[(size_t)node * CS + ls];
+  if (node >= a.L) {
+    for (int j = 0; j < 4; j++) in[j] = a.partials[((size_t)(node - a.L) * 4 + j) * SP + s];
+    bcnt += a.counts[(size_t)(node - a.L) * SP + s];
+  } else {
+    const int c = (int)a.codes[(size_t)node * SP + s];
+    for (int j = 0; j < 4; j++) in[j] = c >= 0 ? (j == c ? 1. : 0.) : a.ambig[(size_t)(-c - 1) * 4 + j];
+  }
+  const double f = a.freq[s];
+  for (int k = a.tr_off[bi]; k < a.tr_off[bi + 1]; k++) {
+    const int t = a.tr_idx[k];
+    const double *M = a.img + ((size_t)t * a.C + a.cls) * 16;
+    double l = 0.;
+    for (int x = 0; x < 4; x++) l += V[x] * (M[4 * x] * in[0] + M[4 * x + 1] * in[1] + M[4 * x + 2] * in[2] + M[4 * x + 3] * in[3]);
+    const size_t q = (size_t)t * SP + s;
+    int e = bcnt;
+    mix_in(a, q, l, e);
+    a.lik[q] = l;
+    a.cnt[q] = e;
+    if (a.last) {
+      double wsum = 0.;
+      long long wcnt = 0;
+      int wflag = 0;
+      site_term(l, e, f, wsum, wcnt, wflag);
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        wsum += __shfl_xor(wsum, off);
+        wcnt += __shfl_xor(wcnt, off);
+        wflag |= __shfl_xor(wflag, off);
+      }
+      if (lane == 0) {
+        const size_t pq = (size_t)t * a.part_stride + tile;
+        a.part_sum[pq] = wsum;
+        a.part_cnt[pq] = wcnt;
+        a.part_flag[pq] = wflag;
+      }
+    }
+  }
+}
+
+// log-L of trial blockIdx.x = sum_s f_s log l_s - 64 ln2 sum_s f_s c_s from its per-tile partial sums: one wave, fixed order, compensated
+__global__ __launch_bounds__(64) void trials_reduce_kernel(double *part_sum, long long *part_cnt, int *part_flag, int n, int stride,
+                                                           double *__restrict__ out) {
+  const size_t o = (size_t)blockIdx.x * stride;
+  double sum, comp;
+  long long c;
+  int fl;
+  combine_range(part_sum + o, part_cnt + o, part_flag + o, n, 0, n, (int)threadIdx.x, sum, comp, c, fl);
+  if (threadIdx.x == 0) {
+    double r = (sum - comp) - kLogScaler * (double)c;
+    if (fl & 2) r = NAN;
+    else if (fl & 1) r = -INFINITY;
+    out[blockIdx.x] = r;
+  }
+}
+
+// device blocks of one call: from the pool, back to it when the call returns (on every path)
+struct Blocks {
+  std::vector<void *> held;
+  ~Blocks() { release(); }
+  void release() {
+    for (void *b : held) pool_free_sync(b);
+    held.clear();
+  }
+  template <typename T>
+  hipError_t get(T **out, size_t n) {
+    void *b = nullptr;
+    const hipError_t e = pool_malloc(&b, std::max<size_t>(1, n) * sizeof(T));
+    if (e == hipSuccess) held.push_back(b);
+    *out = (T *)b;
+    return e;
+  }
+};
+
+int trials_common(const char *what, hyphy_hip_partition *p, int64_t n_trials, const int64_t *nodes, const double *q_dense,
+                  const double *coeffs, int q_is_probability, const double *weights, double *logl_out, double *site_lik_out,
+                  int64_t *site_scaler_out) {
+  const std::string pre = std::string(what) + ": ";
+  if (!p) return fail(pre + "partition == NULL");
+  if (n_trials < 0) return fail(pre + "n_trials < 0");
+  if (p->pin_node >= 0) return fail(pre + "a node's states are pinned (clear the pin first)");
+  const int C = (int)p->C;
+  if (C > 1 && !weights) return fail(pre + "class weights are required when C > 1");
+  for (int c = 0; c < C; c++)
+    if (!p->initialized[c] || p->cached_pi.size() != (size_t)p->D)
+      return fail(pre + "rate class " + std::to_string(c) + " has not been evaluated");
+  if (n_trials == 0) return 0;
+  if (!nodes || !logl_out || (!q_dense && !coeffs)) return fail(pre + "null argument");
+  if (coeffs && !p->K) return fail(pre + "templates not set (hyphy_hip_set_q_templates)");
+  if (n_trials * (int64_t)C > 0x3fffffff) return fail(pre + "too many trials");
+  const int64_t D = p->D, L = p->L, I = p->I, B = p->B, S = p->S;
+  for (int64_t t = 0; t < n_trials; t++)
+    if (nodes[t] < 0 || nodes[t] >= B)
+      return fail(pre + "trial " + std::to_string(t) + ": node code out of range (the root has no branch)");
+  if (finish_pending_async(p)) return -1;
+  for (int c = 0; c < C; c++)
+    if (ensure_resident(p, c)) return -1;
+  // (the pass reads the plain tree's persisted copies; when ensure_resident has to restore them it switches to the plain view, as
+  //  before a marginal reconstruction or a branch-cache build, and the next evaluation switches back)
+  const int DP = p->DP, NW = p->NW;
+  const bool nuc = p->nuc;
+  if (p->marg_prog.empty()) p->marg_prog = plan_marginal_program(L, I, p->parents.data(), &p->marg_maxk);
+  const std::vector<int4> &prog = p->marg_prog;
+  const int maxk = p->marg_maxk;
+  std::vector<double> pi_pad((size_t)(nuc ? 4 : DP), 0.);
+  for (int64_t j = 0; j < D; j++) pi_pad[(size_t)j] = p->cached_pi[(size_t)j];
+  // trials grouped by branch, branches in ascending node code, the trials of a branch in the caller's order
+  std::vector<int> order((size_t)n_trials), branch, tr_off;
+  for (int64_t t = 0; t < n_trials; t++) order[(size_t)t] = (int)t;
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return nodes[x] < nodes[y]; });
+  for (int64_t k = 0; k < n_trials; k++)
+    if (k == 0 || nodes[order[(size_t)k]] != nodes[order[(size_t)k - 1]]) {
+      branch.push_back((int)nodes[order[(size_t)k]]);
+      tr_off.push_back((int)k);
+    }
+  tr_off.push_back((int)n_trials);
+  const int n_branch = (int)branch.size();
+  const char *mb_env = getenv("HYPHY_HIP_TRIALS_MB");  // (read per call)
+  const double budget = (mb_env && atof(mb_env) > 0. ? atof(mb_env) : 1024.) * 1048576.;
+  const size_t MS = nuc ? 16 : (size_t)DP * DP;     // doubles of a trial matrix on the device
+  const size_t TILE = nuc ? 256 : (size_t)16 * DP;  // doubles of one tile of one node
+  const int TP = nuc ? 64 : 16;                     // its patterns
+  std::vector<double> totals((size_t)n_trials), h_l;
+  std::vector<std::vector<double>> parts((size_t)n_trials);
+  std::vector<int32_t> h_c;
+  for (Shard &s : p->shards) {
+    HIPCHK(hipSetDevice(s.device));
+    HIPCHK(hipStreamSynchronize(s.stream));
+    Blocks blk;
+    const int ntiles = s.S_pad / TP;
+    const int ct = (int)std::min<double>(ntiles, std::max(1., floor(budget / ((double)B * TILE * sizeof(double)))));
+    const int part_stride = (ntiles + 3) / 4 * 4 + 4;  // (combine_range reads whole 16-byte words)
+    const size_t nm = (size_t)n_trials * C;
+    double *img = nullptr, *src = nullptr, *lik = nullptr, *part_sum = nullptr, *d_tot = nullptr, *d_pi = nullptr, *PT = nullptr;
+    double *V = nullptr, *U = nullptr, *work = nullptr;
+    int32_t *cnt = nullptr, *status = nullptr, *Vcnt = nullptr, *Ucnt = nullptr, *wcnt = nullptr;
+    long long *part_cnt = nullptr;
+    int *part_flag = nullptr, *d_branch = nullptr, *d_off = nullptr, *d_idx = nullptr;
+    int4 *d_prog = nullptr;
+    HIPCHK(blk.get(&img, nm * MS));
+    HIPCHK(blk.get(&src, q_dense ? nm * D * D : nm * p->K));
+    HIPCHK(blk.get(&lik, (size_t)n_trials * s.S_pad));
+    HIPCHK(blk.get(&cnt, (size_t)n_trials * s.S_pad));
+    HIPCHK(blk.get(&part_sum, (size_t)n_trials * part_stride));
+    HIPCHK(blk.get(&part_cnt, (size_t)n_trials * part_stride));
+    HIPCHK(blk.get(&part_flag, (size_t)n_trials * part_stride));
+    HIPCHK(blk.get(&d_tot, (size_t)n_trials));
+    HIPCHK(blk.get(&status, 1));
+    HIPCHK(blk.get(&d_pi, pi_pad.size()));
+    HIPCHK(blk.get(&d_prog, prog.size()));
+    HIPCHK(blk.get(&d_branch, (size_t)n_branch));
+    HIPCHK(blk.get(&d_off, (size_t)n_branch + 1));
+    HIPCHK(blk.get(&d_idx, (size_t)n_trials));
+    if (!nuc) HIPCHK(blk.get(&PT, (size_t)B * DP * DP));
+    HIPCHK(blk.get(&V, (size_t)B * ct * TILE));
+    HIPCHK(blk.get(&Vcnt, (size_t)B * ct * TP));
+    HIPCHK(blk.get(&U, (size_t)I * ct * TILE));
+    HIPCHK(blk.get(&Ucnt, (size_t)I * ct * TP));
+    HIPCHK(blk.get(&work, (size_t)ct * 2 * maxk * TILE));
+    HIPCHK(blk.get(&wcnt, (size_t)ct * 2 * maxk * TP));
+    HIPCHK(hipMemsetAsync(status, 0, sizeof(int32_t), s.stream));
+    HIPCHK(hipMemcpyAsync(src, q_dense ? q_dense : coeffs, (q_dense ? nm * D * D : nm * p->K) * sizeof(double), hipMemcpyHostToDevice,
+                          s.stream));
+    HIPCHK(hipMemcpyAsync(d_pi, pi_pad.data(), pi_pad.size() * sizeof(double), hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(d_prog, prog.data(), prog.size() * sizeof(int4), hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(d_branch, branch.data(), branch.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(d_off, tr_off.data(), tr_off.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(d_idx, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
+    // trial images: one launch of the exponential kernels into the call's own slots (slot = trial * C + class)
+    ExpmArgs ea;
+    ea.Q = q_dense ? src : nullptr;
+    ea.slots = nullptr;
+    ea.n = (int)nm;
+    ea.D = (int)D;
+    ea.is_prob = q_dense ? q_is_probability : 0;
+    ea.Prow = nuc ? img : nullptr;
+    ea.Pfrag = nuc ? nullptr : img;
+    ea.PTg = nullptr;
+    ea.status = status;
+    ea.templates = coeffs ? s.templates : nullptr;
+    ea.templates_pad = coeffs ? s.templates_pad : nullptr;
+    ea.coeffs = coeffs ? src : nullptr;
+    ea.K = coeffs ? (int)p->K : 0;
+    ea.prof = 0;
+    const char *expm_before = last_expm_kernel();
+    launch_expm(ea, s.stream);
+    set_last_expm_kernel(expm_before);
+    HIPCHK(hipGetLastError());
+    for (int tile0 = 0; tile0 < ntiles; tile0 += ct) {
+      const int nt = std::min(ct, ntiles - tile0);
+      for (int c = 0; c < C; c++) {
+        TrialArgs ta;
+        ta.NW = NW, ta.L = (int)L, ta.S_pad = s.S_pad, ta.ntiles = s.ntiles, ta.tile0 = tile0, ta.ct = ct;
+        ta.C = C, ta.cls = c, ta.first = c == 0, ta.last = c == C - 1, ta.b0 = 0;
+        ta.w = C > 1 ? weights[c] : 1.0;
+        ta.branch = d_branch, ta.tr_off = d_off, ta.tr_idx = d_idx;
+        ta.img = img;
+        ta.V = V, ta.Vcnt = Vcnt;
+        ta.partials = s.partials + (size_t)c * s.partial_stride;
+        ta.counts = s.counts + (size_t)c * I * s.S_pad;
+        ta.codes_tile = s.codes_tile, ta.codes = s.codes;
+        ta.ambig = s.ambig, ta.freq = s.freq;
+        ta.lik = lik, ta.cnt = cnt;
+        ta.part_sum = part_sum, ta.part_cnt = part_cnt, ta.part_flag = part_flag, ta.part_stride = part_stride;
+        if (nuc) {
+          MargNucArgs a;
+          a.prog = d_prog;
+          a.n_prog = (int)prog.size();
+          a.L = (int)L, a.S = (int)s.S, a.S_pad = s.S_pad, a.maxk = maxk, a.which = 0, a.first = 0;
+          a.w = ta.w;
+          a.P = s.Prow + (size_t)c * B * 16;
+          a.codes = s.codes;
+          a.ambig = s.ambig;
+          a.pi = d_pi;
+          a.partials = ta.partials;
+          a.counts = ta.counts;
+          a.U = U, a.Ucnt = Ucnt, a.work = work, a.wcnt = wcnt;
+          a.acc = nullptr, a.den = nullptr, a.aexp = nullptr;
+          hipLaunchKernelGGL(outside_store_nuc_kernel, dim3((unsigned)((nt * 64 + 255) / 256)), dim3(256), 0, s.stream, a, tile0 * 64,
+                             nt * 64, ct * 64, V, Vcnt);
+        } else {
+          MargArgs a;
+          a.prog = d_prog;
+          a.n_prog = (int)prog.size();
+          a.NW = NW, a.L = (int)L, a.S = (int)s.S, a.S_pad = s.S_pad, a.ntiles = s.ntiles, a.maxk = maxk, a.which = 0;
+          a.first = 0, a.D = (int)D;
+          a.w = ta.w;
+          a.Pfrag = s.Pfrag + (size_t)c * B * DP * DP;
+          a.PTg = s.PTg + (size_t)c * B * DP * DP;
+          a.PT = PT;
+          a.codes_tile = s.codes_tile;
+          a.ambig = s.ambig;
+          a.pi = d_pi;
+          a.partials = ta.partials;
+          a.counts = ta.counts;
+          a.U = U, a.Ucnt = Ucnt, a.work = work, a.wcnt = wcnt;
+          a.acc = nullptr, a.den = nullptr, a.aexp = nullptr;
+          OutsideStore o;
+          o.tile0 = tile0, o.ct = ct, o.V = V, o.Vcnt = Vcnt;
+          if (C > 1 || tile0 == 0)
+            hipLaunchKernelGGL(marg_transpose_kernel, dim3((unsigned)B), dim3(256), 0, s.stream, a.Pfrag, a.PTg, PT, NW, (int)L);
+          const dim3 grid((unsigned)nt), block(64);
+          switch (NW) {
+            case 1: hipLaunchKernelGGL(outside_store_kernel<1>, grid, block, 0, s.stream, a, o); break;
+            case 2: hipLaunchKernelGGL(outside_store_kernel<2>, grid, block, 0, s.stream, a, o); break;
+            case 3: hipLaunchKernelGGL(outside_store_kernel<3>, grid, block, 0, s.stream, a, o); break;
+            default: hipLaunchKernelGGL(outside_store_kernel<4>, grid, block, 0, s.stream, a, o); break;
+          }
+        }
+        for (ta.b0 = 0; ta.b0 < n_branch; ta.b0 += 65535) {
+          const dim3 grid((unsigned)nt, (unsigned)std::min(65535, n_branch - ta.b0)), block(64);
+          if (nuc) hipLaunchKernelGGL(branch_trials_nuc_kernel, grid, block, 0, s.stream, ta);
+          else
+            switch (NW) {
+              case 1: hipLaunchKernelGGL(branch_trials_kernel<1>, grid, block, 0, s.stream, ta); break;
+              case 2: hipLaunchKernelGGL(branch_trials_kernel<2>, grid, block, 0, s.stream, ta); break;
+              case 3: hipLaunchKernelGGL(branch_trials_kernel<3>, grid, block, 0, s.stream, ta); break;
+              default: hipLaunchKernelGGL(branch_trials_kernel<4>, grid, block, 0, s.stream, ta); break;
+            }
+        }
+        HIPCHK(hipGetLastError());
+      }
+    }
+    hipLaunchKernelGGL(trials_reduce_kernel, dim3((unsigned)n_trials), dim3(64), 0, s.stream, part_sum, part_cnt, part_flag, ntiles,
+                       part_stride, d_tot);
+    HIPCHK(hipGetLastError());
+    int32_t h_status = 0;
+    HIPCHK(hipMemcpyAsync(totals.data(), d_tot, (size_t)n_trials * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(hipMemcpyAsync(&h_status, status, sizeof(int32_t), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(hipStreamSynchronize(s.stream));
+    if (h_status)
+      return fail(pre + "Failed to compute a valid transition matrix; this is usually caused by ill-conditioned rate matrices "
+                        "(e.g. very large rate values)");
+    for (int64_t t = 0; t < n_trials; t++) parts[(size_t)t].push_back(totals[(size_t)t]);
+    // per-pattern results -> the caller's pattern order: out[trial][caller pattern]
+    if (site_lik_out) {
+      h_l.resize((size_t)n_trials * s.S_pad);
+      HIPCHK(hipMemcpy(h_l.data(), lik, h_l.size() * sizeof(double), hipMemcpyDeviceToHost));
+      for (int64_t t = 0; t < n_trials; t++)
+        for (int64_t k = 0; k < s.S; k++)
+          site_lik_out[(size_t)t * S + caller_pattern(p, s.s0 + k)] = h_l[(size_t)t * s.S_pad + k];
+    }
+    if (site_scaler_out) {
+      h_c.resize((size_t)n_trials * s.S_pad);
+      HIPCHK(hipMemcpy(h_c.data(), cnt, h_c.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+      for (int64_t t = 0; t < n_trials; t++)
+        for (int64_t k = 0; k < s.S; k++)
+          site_scaler_out[(size_t)t * S + caller_pattern(p, s.s0 + k)] = h_c[(size_t)t * s.S_pad + k];
+    }
+  }
+  for (int64_t t = 0; t < n_trials; t++) logl_out[t] = combine(parts[(size_t)t]);
+  return 0;
+}
+
+}  // namespace
+}  // namespace hyhip
+
+extern "C" {
+
+int hyphy_hip_branch_trials(hyphy_hip_partition *p, int64_t n_trials, const int64_t *nodes, const double *q_dense,
+                            int q_is_probability, const double *weights, double *logl_out, double *site_lik_out,
+                            int64_t *site_scaler_out) {
+  if (p && n_trials > 0 && !q_dense) return fail("branch_trials: null matrix pointer");
+  return trials_common("branch_trials", p, n_trials, nodes, q_dense, nullptr, q_is_probability, weights, logl_out, site_lik_out,
+                       site_scaler_out);
+}
+
+int hyphy_hip_branch_trials_built(hyphy_hip_partition *p, int64_t n_trials, const int64_t *nodes, const double *coeffs,
+                                  const double *weights, double *logl_out, double *site_lik_out, int64_t *site_scaler_out) {
+  if (p && n_trials > 0 && !coeffs) return fail("branch_trials_built: null coefficient pointer");
+  return trials_common("branch_trials_built", p, n_trials, nodes, nullptr, coeffs, 0, weights, logl_out, site_lik_out,
+                       site_scaler_out);
+}
+
+}  // extern "C"

@@ -23,7 +23,7 @@ EXPORTS = [
     "hyphy_hip_expm_batch", "hyphy_hip_set_q_templates", "hyphy_hip_build_q", "hyphy_hip_q_buffer",
     "hyphy_hip_evaluate_built", "hyphy_hip_evaluate_built_sites", "hyphy_hip_update_q_templates", "hyphy_hip_evaluate_categories_built", "hyphy_hip_evaluate_categories_built_sites", "hyphy_hip_prune_timings", "hyphy_hip_prune_launches",
     "hyphy_hip_prune_kernel_name", "hyphy_hip_branch_cache_build", "hyphy_hip_branch_cache_evaluate",
-    "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
+    "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
     "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
     "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error", "hyphy_hip_last_expm_kernel",
     "hyphy_hip_version",
@@ -143,6 +143,10 @@ def load():
     lib.hyphy_hip_set_repeats.argtypes = [vp, C.c_int]
     lib.hyphy_hip_marginal_ancestral.restype = C.c_int
     lib.hyphy_hip_marginal_ancestral.argtypes = [vp, C.c_int64, dp, dp, lp, dp]
+    lib.hyphy_hip_branch_trials.restype = C.c_int
+    lib.hyphy_hip_branch_trials.argtypes = [vp, C.c_int64, lp, dp, C.c_int, dp, dp, dp, lp]
+    lib.hyphy_hip_branch_trials_built.restype = C.c_int
+    lib.hyphy_hip_branch_trials_built.argtypes = [vp, C.c_int64, lp, dp, dp, dp, dp, lp]
     lib.hyphy_hip_plan_marginal.restype = C.c_int64
     lib.hyphy_hip_plan_marginal.argtypes = [C.c_int64, C.c_int64, lp, lp, C.c_int64]
     lib.hyphy_hip_plan_trunk_walk.restype = C.c_int64
@@ -697,6 +701,38 @@ class HipPartition:
         _check(self._lib.hyphy_hip_marginal_ancestral(self._h, 0 if which == "internal" else 1, _d(w), _d(sup), _l(ms), _d(mv)))
         out = tuple(x for x in (sup, ms, mv) if x is not None)
         return out[0] if len(out) == 1 else out
+
+    # -- trial matrices on any number of branches from one outside pass ----------------------------
+    def _trial_args(self, nodes, mats, tail, weights, per_site):
+        nd = np.ascontiguousarray(nodes, dtype=np.int64).reshape(-1)
+        m = np.ascontiguousarray(mats, dtype=np.float64)
+        if m.size != len(nd) * self.C * int(np.prod(tail)):
+            raise ValueError(f"expected [{len(nd)}, {self.C}, {', '.join(str(x) for x in tail)}] values, got {m.shape}")
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            assert w.shape == (self.C,)
+        ll = np.zeros(len(nd))
+        sl = np.zeros((len(nd), self.S)) if per_site else None
+        sc = np.zeros((len(nd), self.S), dtype=np.int64) if per_site else None
+        return nd, m, w, ll, sl, sc
+
+    def branch_trials(self, nodes, q_dense, weights=None, q_is_probability: bool = False, per_site: bool = False):
+        """log-L [n_trials] with the matrix of branch ``nodes[t]`` replaced by exp(``q_dense[t]``) (``q_dense``: [n_trials, D, D], or
+        [n_trials, C, D, D] with one matrix per rate class), everything else as at the last evaluation of every class: one outside
+        pass serves every trial of the call.  ``weights``: class weights when C > 1.  ``per_site``: also the per-pattern values and
+        2^64 exponents, [n_trials, S] each.  Nothing on the device changes."""
+        nd, q, w, ll, sl, sc = self._trial_args(nodes, q_dense, (self.D, self.D), weights, per_site)
+        _check(self._lib.hyphy_hip_branch_trials(self._h, len(nd), _l(nd), _d(q), int(q_is_probability), _d(w), _d(ll), _d(sl), _l(sc)))
+        return (ll, sl, sc) if per_site else ll
+
+    def branch_trials_built(self, nodes, coeffs, weights=None, per_site: bool = False):
+        """``branch_trials`` with the trial rate matrices formed on the device from coefficient rows over the templates of
+        ``set_q_templates`` (``coeffs``: [n_trials, K] or [n_trials, C, K]), as ``build_q`` forms them."""
+        K = int(np.asarray(coeffs).shape[-1])
+        nd, co, w, ll, sl, sc = self._trial_args(nodes, coeffs, (K,), weights, per_site)
+        _check(self._lib.hyphy_hip_branch_trials_built(self._h, len(nd), _l(nd), _d(co), _d(w), _d(ll), _d(sl), _l(sc)))
+        return (ll, sl, sc) if per_site else ll
 
     # -- branch cache (one-branch line searches) --------------------------------------------------
     def branch_cache_build(self, node: int, cat: int = 0):

@@ -421,6 +421,36 @@ int hyphy_hip_marginal_ancestral(hyphy_hip_partition *p, int64_t which, const do
  * NULL), -1 on bad arguments. */
 int64_t hyphy_hip_plan_marginal(int64_t L, int64_t I, const int64_t *flat_parents, int64_t *out, int64_t cap);
 
+/* ---- every branch's trial likelihoods from one outside pass -------------------------------------------------
+ * Replaces the one evaluation per independent parameter of _LikelihoodFunction::ComputeGradient's finite differences
+ * (src/core/likefunc.cpp:7025-7109) for the parameters that are local to one branch: one pre-order pass keeps the outside vector
+ * V_c = U_p * prod of the other children's edge products of EVERY branch c, after which the likelihood with the matrix of branch
+ * c replaced by M is sum_i V_c[i] (M in_c)[i] per pattern, independent over (trial, pattern).
+ *   nodes   [n_trials]            node codes (leaf l -> l, internal i -> L + i, never the root), any order, repeats allowed
+ *   q_dense [n_trials][C][D*D]    the branch's matrix in every rate class: rate matrices, or transition matrices when
+ *                                 q_is_probability; hyphy_hip_branch_trials_built takes coeffs [n_trials][C][K] over the
+ *                                 templates of hyphy_hip_set_q_templates instead (Q = sum_k coeffs_k T_k, as hyphy_hip_build_q)
+ *   weights [C] (NULL when C == 1) class weights; the classes of a trial are mixed by weight
+ *   logl_out [n_trials]           what hyphy_hip_evaluate (C == 1) / hyphy_hip_evaluate_categories (C > 1) would return with the
+ *                                 matrix of branch nodes[t] replaced by trial t in every class and everything else as at the last
+ *                                 evaluation of each class; -INFINITY when the trial makes a pattern impossible (for C > 1 too:
+ *                                 there is no floor on the logarithm here)
+ *   site_lik_out / site_scaler_out [n_trials][S] or NULL: per pattern (l, c) in the caller's pattern order, meaning as in
+ *                                 hyphy_hip_evaluate; l = 0 where the trial makes the pattern impossible
+ * Call after an evaluation of every class.  Leaves no state behind: the device's matrices and images, the schedules, the tuner's
+ * state, the class tables, the branch-cache slots and hyphy_hip_last_expm_kernel are what they were (persisted copies are restored
+ * first if the last full pass kept them on chip, as before a marginal reconstruction).  Two identical calls give identical bits.
+ * The outside vectors take B x tiles x 16 DP doubles: the pass runs over chunks of tiles that keep them within HYPHY_HIP_TRIALS_MB
+ * (default 1024, read at every call, at least one tile); all scratch comes from the pool and is returned before the call returns.
+ * Returns < 0 when a pin is active, a class was never evaluated, C > 1 without weights, a node code is out of range or the root's,
+ * or a trial matrix cannot be exponentiated; n_trials == 0 returns 0 and writes nothing. */
+int hyphy_hip_branch_trials(hyphy_hip_partition *p, int64_t n_trials, const int64_t *nodes, const double *q_dense,
+                            int q_is_probability, const double *weights /* [C] or NULL */, double *logl_out,
+                            double *site_lik_out, int64_t *site_scaler_out);
+int hyphy_hip_branch_trials_built(hyphy_hip_partition *p, int64_t n_trials, const int64_t *nodes, const double *coeffs,
+                                  const double *weights /* [C] or NULL */, double *logl_out, double *site_lik_out,
+                                  int64_t *site_scaler_out);
+
 /* ---- branch cache ---------------------------------------------------------------------
  * Replaces _TheTree::ComputeBranchCache (src/core/tree_evaluator.cpp:4286-4845) and
  * _TheTree::ComputeLLWithBranchCache (src/core/tree.cpp:3383-3936), driven by the policy code of
