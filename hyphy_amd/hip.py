@@ -23,7 +23,7 @@ EXPORTS = [
     "hyphy_hip_expm_batch", "hyphy_hip_set_q_templates", "hyphy_hip_build_q", "hyphy_hip_q_buffer",
     "hyphy_hip_evaluate_built", "hyphy_hip_evaluate_built_sites", "hyphy_hip_update_q_templates", "hyphy_hip_evaluate_categories_built", "hyphy_hip_evaluate_categories_built_sites", "hyphy_hip_prune_timings", "hyphy_hip_prune_launches",
     "hyphy_hip_prune_kernel_name", "hyphy_hip_branch_cache_build", "hyphy_hip_branch_cache_evaluate",
-    "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
+    "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_joint_ancestral", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
     "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
     "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error", "hyphy_hip_last_expm_kernel",
     "hyphy_hip_version",
@@ -143,6 +143,8 @@ def load():
     lib.hyphy_hip_set_repeats.argtypes = [vp, C.c_int]
     lib.hyphy_hip_marginal_ancestral.restype = C.c_int
     lib.hyphy_hip_marginal_ancestral.argtypes = [vp, C.c_int64, dp, dp, lp, dp]
+    lib.hyphy_hip_joint_ancestral.restype = C.c_int
+    lib.hyphy_hip_joint_ancestral.argtypes = [vp, C.c_int, lp, lp]
     lib.hyphy_hip_branch_trials.restype = C.c_int
     lib.hyphy_hip_branch_trials.argtypes = [vp, C.c_int64, lp, dp, C.c_int, dp, dp, dp, lp]
     lib.hyphy_hip_branch_trials_built.restype = C.c_int
@@ -701,6 +703,19 @@ class HipPartition:
         _check(self._lib.hyphy_hip_marginal_ancestral(self._h, 0 if which == "internal" else 1, _d(w), _d(sup), _l(ms), _d(mv)))
         out = tuple(x for x in (sup, ms, mv) if x is not None)
         return out[0] if len(out) == 1 else out
+
+    def joint_ancestral(self, do_leaves: bool = False, class_of_pattern=None) -> np.ndarray:
+        """Joint maximum-likelihood ancestral states (the reference's default ``ReconstructAncestors``) under the matrices, root
+        frequencies and leaf data of the last evaluation: int64 [I (+ L with ``do_leaves``), S], rows = internal nodes by internal
+        index (the root last), then the leaves; -1 where a node is completely unresolved.  ``class_of_pattern`` [S]: the rate class
+        whose matrices each pattern uses (default: class 0).  Nothing on the device changes."""
+        cls = None
+        if class_of_pattern is not None:
+            cls = np.ascontiguousarray(class_of_pattern, dtype=np.int64)
+            assert cls.shape == (self.S,)
+        out = np.full((self.I + (self.L if do_leaves else 0), self.S), -2, dtype=np.int64)
+        _check(self._lib.hyphy_hip_joint_ancestral(self._h, int(bool(do_leaves)), _l(cls), _l(out)))
+        return out
 
     # -- trial matrices on any number of branches from one outside pass ----------------------------
     def _trial_args(self, nodes, mats, tail, weights, per_site):

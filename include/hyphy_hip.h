@@ -451,6 +451,29 @@ int hyphy_hip_branch_trials_built(hyphy_hip_partition *p, int64_t n_trials, cons
                                   const double *weights /* [C] or NULL */, double *logl_out, double *site_lik_out,
                                   int64_t *site_scaler_out);
 
+/* ---- joint maximum-likelihood ancestral reconstruction ------------------------------------------------------
+ * Replaces _TheTree::RecoverAncestralSequences (src/core/tree.cpp:4209-4510), the max-product pass behind
+ * `ReconstructAncestors (lf)` without MARGINAL: per pattern an upward pass over the nodes in ascending node code
+ * (msg[p] = max_c P[p][c] v[c] with the FIRST maximising c as backpointer, strict > starting from 0; a child whose vector is
+ * exactly all ones is completely unresolved: backpointer -1, no contribution), the root state as the first argmax of
+ * pi[c] m_root[c] (every node -1 when m_root is exactly all ones), and a traceback state[n] = arg_n[state[parent]] (-1 below -1).
+ * Factors are multiplied in the reference's order as plain products, rescaled by exact powers of 2^64 after every factor, so the
+ * states are those of unbounded-range arithmetic where the reference's single rescaling would underflow.
+ *   do_leaves          also reconstruct the leaves (the DOLEAVES form)
+ *   class_of_pattern   [S] rate class of each pattern (the reference's catAssignments), caller's pattern order; NULL: class 0
+ *                      everywhere (NULL or all zero when C == 1)
+ *   states_out         [I (+ L)][S]: rows 0 .. I-1 the internal nodes by internal index (the root last), with do_leaves rows
+ *                      I .. I+L-1 the leaves; patterns in the caller's order; values in [0, D) or -1
+ * Uses the matrices and leaf data of the last evaluation of each class that is referenced (a class no pattern refers to need not
+ * have been evaluated) and the root frequencies currently on the device (one vector for every class, those of the last
+ * evaluation).  Reads the matrix images and the leaf table only — no conditionals — so it works whatever form the last pass ran
+ * in, and leaves no state behind.  Scratch (about I x 16 x DP x 9 bytes per 16-pattern tile) comes from the pool and is returned
+ * before the call returns; the pass runs over chunks of tiles that keep it within HYPHY_HIP_JOINT_MB (default 1024, read at every
+ * call, at least one tile).  Two identical calls give identical arrays.
+ * Returns < 0 on a NULL partition or output, an active pin, a class id out of range, or a referenced class never evaluated. */
+int hyphy_hip_joint_ancestral(hyphy_hip_partition *p, int do_leaves, const int64_t *class_of_pattern /* [S] or NULL */,
+                              int64_t *states_out /* [I (+ L)][S] */);
+
 /* ---- branch cache ---------------------------------------------------------------------
  * Replaces _TheTree::ComputeBranchCache (src/core/tree_evaluator.cpp:4286-4845) and
  * _TheTree::ComputeLLWithBranchCache (src/core/tree.cpp:3383-3936), driven by the policy code of

@@ -131,6 +131,7 @@ static bool _hyhip_cat_block = false;  // this ComputeBlock call builds / uses a
 static std::map<const void *, std::pair<const void *, long>> _hyhip_tree_owner;  // _TheTree* -> (lf, partition index)
 long _hyhip_calls = 0L, _hyhip_cached_calls = 0L, _hyhip_deferred = 0L;
 static long _hyhip_marginal_calls = 0L;  // marginal reconstructions answered by hyphy_hip_marginal_ancestral (HYPHY_HIP_MARGINAL=1)
+static long _hyhip_joint_calls = 0L;     // joint reconstructions answered by hyphy_hip_joint_ancestral (HYPHY_HIP_JOINT=1)
 // class weights the weighted-sum loop of PopulateConditionalProbabilities passed for (lf, partition) last: the weights of the baseline
 // evaluation of RecoverAncestralSequencesMarginal (recorded by _hyphy_hip_cat_begin whether or not it batches the classes)
 static std::map<std::pair<const void *, long>, std::vector<double>> _hyhip_class_weights;
@@ -190,6 +191,8 @@ static void _hyphy_hip_teardown(const void *lf) {
     w = w->first.first == lf ? _hyhip_class_weights.erase(w) : std::next(w);
   if (getenv("HYPHY_HIP_VERBOSE") && _hyhip_marginal_calls)
     fprintf(stderr, "[hyphy_hip] %ld marginal reconstructions ran on the device\n", _hyhip_marginal_calls);
+  if (getenv("HYPHY_HIP_VERBOSE") && _hyhip_joint_calls)
+    fprintf(stderr, "[hyphy_hip] %ld joint reconstructions ran on the device\n", _hyhip_joint_calls);
   if (getenv("HYPHY_HIP_VERBOSE")) fprintf(stderr, "[hyphy_hip] %ld ComputeBlock evaluations ran on the device so far (+ %ld through the branch cache); %ld matrix exponentials moved to the device; adapter mode: %.3f s of wall clock inside the adapter's ComputeBlock calls (coefficients, library call and its wait, per-pattern downloads)\n", _hyhip_calls, _hyhip_cached_calls, _hyhip_deferred, _hyhip_compute_seconds);
 }
 
@@ -1890,6 +1893,56 @@ int _hyphy_hip_marginal(const void *lf, long index, bool do_leaves, hyFloat *sup
   _hyhip_marginal_calls++;
   return 0;
 }
+// Joint ancestral reconstruction (HYPHY_HIP_JOINT=1, opt-in): ReconstructAncestors announces (likelihood function, partition) right
+// before it calls _TheTree::RecoverAncestralSequences (likefunc2.cpp:447); the tree asks here before its upward loop.  A table
+// [I (+ L)][patterns] of states (-1: unresolved; rows = internal nodes by flat index, then leaves; columns = pattern indices, what
+// siteOrdering maps the cache order to): the upward loop is skipped and the traceback fills parentStates from it.  nullptr: declined,
+// the CPU path runs unchanged.  catAssignments is indexed by pattern (the reference reads it through siteOrdering, tree.cpp:4307).
+// The hand-off goes through the two statics below.  An announcement must not survive the call it was made for: the tree clears it
+// when it asks (only when it has an iNodeCache), and the call site clears it again right behind the call, so a call that never
+// asked (the two-sequence path) cannot leave one behind for a later, unrelated tree.
+static const void *_hyhip_joint_lf = nullptr;
+static long _hyhip_joint_index = -1L;
+void _hyphy_hip_joint_announce(const void *lf, long index) {
+  _hyhip_joint_lf = lf;
+  _hyhip_joint_index = index;
+}
+const long *_hyphy_hip_joint_states(bool do_leaves, const hyFloat *cat_assignments, long S, long I, long L, long D) {
+  static const bool on = getenv("HYPHY_HIP_JOINT") && atoi(getenv("HYPHY_HIP_JOINT")) == 1;
+  const void *lf = _hyhip_joint_lf;
+  const long index = _hyhip_joint_index;
+  _hyhip_joint_lf = nullptr;  // (an announcement serves the one call behind it)
+  _hyhip_joint_index = -1L;
+  if (!on || !lf || !_hyphy_hip_enabled()) return nullptr;
+  auto it = _hyhip_lfs.find(lf);
+  if (it == _hyhip_lfs.end() || index < 0 || index >= (long)it->second.size()) return nullptr;
+  _HyHipPart &hp = it->second[index];
+  if (!hp.part || hp.spmd || hp.pending || S < 1 || I < 1 || L < 1 || D < 2) return nullptr;
+  const long C = std::max<long>(1, (long)hp.cat_seen.size());
+  for (long c = 0; c < C && c < (long)hp.mix_state.size(); c++)
+    if (hp.mix_state[c] > 0) return nullptr;  // (explicit-form mixtures: left to the host)
+  std::vector<int64_t> cls;
+  if (cat_assignments) {
+    cls.resize((size_t)S);
+    for (long s = 0; s < S; s++) {
+      const long c = (long)cat_assignments[s];
+      if (c < 0 || c >= C || (hp.cat_seen.size() && !hp.cat_seen[c])) return nullptr;
+      cls[(size_t)s] = c;
+    }
+  } else if (C > 1) {
+    return nullptr;
+  }
+  const size_t n = (size_t)(I + (do_leaves ? L : 0)) * (size_t)S;
+  std::vector<int64_t> out(n);
+  if (hyphy_hip_joint_ancestral(hp.part, do_leaves ? 1 : 0, cat_assignments ? cls.data() : nullptr, out.data()) != 0) {
+    if (getenv("HYPHY_HIP_VERBOSE")) fprintf(stderr, "[hyphy_hip] joint reconstruction declined: %s\n", hyphy_hip_last_error());
+    return nullptr;
+  }
+  static std::vector<long> table;
+  table.assign(out.begin(), out.end());
+  _hyhip_joint_calls++;
+  return table.data();
+}
 #endif
 '''
 
@@ -2116,3 +2169,52 @@ MARG_NEW = r"""  ComputeSiteLikelihoodsForABlock(index, siteLikelihoods, scalers
 #endif
   if (doLeaves) {
 """
+
+
+# ---- block 9: joint ancestral reconstruction in one device pass (HYPHY_HIP_JOINT=1) ---------------------------------------------------
+# likefunc2.cpp copy, ReconstructAncestors: the call site announces (likelihood function, partition) to the adapter.
+# tree.cpp copy, RecoverAncestralSequences: the upward loop is skipped when the adapter returns a state table and the traceback fills
+# parentStates from it; everything that turns states into strings stays the reference's own code
+JOINT_DECL = r"""
+#ifdef HYPHY_HIP
+void _hyphy_hip_joint_announce(const void *lf, long index);
+#endif
+"""
+JOINT_CALL_OLD = "      } else\n        thisSet = tree->RecoverAncestralSequences("
+JOINT_CALL_NEW = r"""      } else
+#ifdef HYPHY_HIP
+        _hyphy_hip_joint_announce(this, partIndex),
+#endif
+        thisSet = tree->RecoverAncestralSequences("""
+JOINT_DONE_ANCHOR = "            (_Vector *)conditionalTerminalNodeLikelihoodCaches(partIndex),\n            doLeaves);\n"
+JOINT_DONE = r"""#ifdef HYPHY_HIP
+      _hyphy_hip_joint_announce(nullptr, -1L);  // (an announcement never outlives its call)
+#endif
+"""
+JOINT_TREE_DECL = r"""
+#ifdef HYPHY_HIP
+const long *_hyphy_hip_joint_states(bool do_leaves, const hyFloat *cat_assignments, long S, long I, long L, long D);  // likefunc.cpp copy
+#endif
+"""
+JOINT_UP_OLD = "  if (iNodeCache) {\n    for (long nodeID = 0; nodeID < allNodeCount; nodeID++) {\n      long parent_index = flatParents.get(nodeID), node_index = nodeID;"
+JOINT_UP_NEW = r"""#ifdef HYPHY_HIP
+  const long *hip_states =
+      iNodeCache ? _hyphy_hip_joint_states(alsoDoLeaves, catAssignments, patternCount, iNodeCount, leafCount, alphabetDimension) : nullptr;
+#else
+  const long *hip_states = nullptr;
+#endif
+  if (iNodeCache && !hip_states) {
+    for (long nodeID = 0; nodeID < allNodeCount; nodeID++) {
+      long parent_index = flatParents.get(nodeID), node_index = nodeID;"""
+JOINT_REWIND_OLD = "    stateCache -= patternCount * (iNodeCount - 1) * alphabetDimension;\n    if (alsoDoLeaves) {"
+JOINT_REWIND_NEW = r"""    if (!hip_states) stateCache -= patternCount * (iNodeCount - 1) * alphabetDimension;
+    if (alsoDoLeaves && !hip_states) {"""
+JOINT_TRACE_OLD = "      if (howManyOnes != alphabetDimension) {\n        for (long c = 0; c < alphabetDimension; c++) {\n          hyFloat thisV = theProbs[c] * rootConditionals[c];"
+JOINT_TRACE_NEW = r"""      if (hip_states) {
+        const long pattern = siteOrdering.list_data[siteID];
+        for (long nodeID = 0; nodeID < stateCacheDim; nodeID++)
+          parentStates.list_data[nodeID] = hip_states[nodeID * patternCount + pattern];
+      } else
+      if (howManyOnes != alphabetDimension) {
+        for (long c = 0; c < alphabetDimension; c++) {
+          hyFloat thisV = theProbs[c] * rootConditionals[c];"""

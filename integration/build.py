@@ -66,6 +66,11 @@ def main():
     tr = splice(tr, "using namespace hyphy_global_objects;\n", AB.TREE_HOOK_DEF)
     tr = splice(tr, "  if (parallel.lLength) {\n    if (parallel.lLength == 1) {", AB.TREE_HOOK_CALL, before=True)
     tr = replace_once(tr, AB.TREE_SKIP_OLD, AB.TREE_SKIP_NEW)
+    # joint ancestral reconstruction in one device pass (HYPHY_HIP_JOINT=1): RecoverAncestralSequences asks the adapter for a state table
+    tr = splice(tr, "using namespace hyphy_global_objects;\n", AB.JOINT_TREE_DECL)
+    tr = replace_once(tr, AB.JOINT_UP_OLD, AB.JOINT_UP_NEW)
+    tr = replace_once(tr, AB.JOINT_REWIND_OLD, AB.JOINT_REWIND_NEW)
+    tr = replace_once(tr, AB.JOINT_TRACE_OLD, AB.JOINT_TRACE_NEW)
     tsrc = os.path.join(OUT, "tree_hip.cpp")
     open(tsrc, "w").write(tr)
     # likefunc2.cpp copy (r06): PopulateConditionalProbabilities' weighted-sum loop collects its classes for ONE device evaluation
@@ -77,6 +82,12 @@ def main():
     # marginal ancestral reconstruction in one device pass (HYPHY_HIP_MARGINAL=1)
     l2 = splice(l2, '#include "likefunc.h"\n', AB.MARG_DECL) if '#include "likefunc.h"\n' in l2 else splice(l2, "using namespace hy_global;\n", AB.MARG_DECL)
     l2 = replace_once(l2, AB.MARG_ANCHOR, AB.MARG_NEW)
+    # ... and its call site announces (likelihood function, partition) to the adapter
+    l2 = splice(l2, '#include "likefunc.h"\n', AB.JOINT_DECL) if '#include "likefunc.h"\n' in l2 else splice(l2, "using namespace hy_global;\n", AB.JOINT_DECL)
+    l2 = replace_once(l2, AB.JOINT_CALL_OLD, AB.JOINT_CALL_NEW)
+    if l2.count(AB.JOINT_DONE_ANCHOR) != 1:
+        raise SystemExit("anchor not unique: the end of the RecoverAncestralSequences call")
+    l2 = splice(l2, AB.JOINT_DONE_ANCHOR, AB.JOINT_DONE)
     l2src = os.path.join(OUT, "likefunc2_hip.cpp")
     open(l2src, "w").write(l2)
     # 3. compile that one file with the reference's flags (oracle/Makefile.ref) + -DHYPHY_HIP
