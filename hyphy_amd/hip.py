@@ -23,7 +23,7 @@ EXPORTS = [
     "hyphy_hip_expm_batch", "hyphy_hip_set_q_templates", "hyphy_hip_build_q", "hyphy_hip_q_buffer",
     "hyphy_hip_evaluate_built", "hyphy_hip_evaluate_built_sites", "hyphy_hip_update_q_templates", "hyphy_hip_evaluate_categories_built", "hyphy_hip_evaluate_categories_built_sites", "hyphy_hip_prune_timings", "hyphy_hip_prune_launches",
     "hyphy_hip_prune_kernel_name", "hyphy_hip_branch_cache_build", "hyphy_hip_branch_cache_evaluate",
-    "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_joint_ancestral", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
+    "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_joint_ancestral", "hyphy_hip_sample_ancestral", "hyphy_hip_sample_uniforms", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
     "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
     "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error", "hyphy_hip_last_expm_kernel",
     "hyphy_hip_version",
@@ -145,6 +145,10 @@ def load():
     lib.hyphy_hip_marginal_ancestral.argtypes = [vp, C.c_int64, dp, dp, lp, dp]
     lib.hyphy_hip_joint_ancestral.restype = C.c_int
     lib.hyphy_hip_joint_ancestral.argtypes = [vp, C.c_int, lp, lp]
+    lib.hyphy_hip_sample_ancestral.restype = C.c_int
+    lib.hyphy_hip_sample_ancestral.argtypes = [vp, C.c_int64, C.c_int64, lp, lp, C.c_uint64, dp, C.POINTER(C.c_int8)]
+    lib.hyphy_hip_sample_uniforms.restype = C.c_int
+    lib.hyphy_hip_sample_uniforms.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, dp]
     lib.hyphy_hip_branch_trials.restype = C.c_int
     lib.hyphy_hip_branch_trials.argtypes = [vp, C.c_int64, lp, dp, C.c_int, dp, dp, dp, lp]
     lib.hyphy_hip_branch_trials_built.restype = C.c_int
@@ -327,6 +331,14 @@ def expm_batch(Q: np.ndarray) -> np.ndarray:
     P = np.empty_like(Qb)
     _check(load().hyphy_hip_expm_batch(Qb.shape[1], Qb.shape[0], _d(Qb), _d(P)))
     return P[0] if single else P
+
+
+def sample_uniforms(seed: int, n_rep: int, I: int, n_sites: int) -> np.ndarray:
+    """Host-only: the uniforms [n_rep, I, n_sites] that ``HipPartition.sample_ancestral`` draws with under ``seed`` when none are
+    supplied (Philox4x32-10, counter = (site, node, replicate, 0))."""
+    out = np.zeros((int(n_rep), int(I), int(n_sites)))
+    _check(load().hyphy_hip_sample_uniforms(C.c_uint64(int(seed) & (2 ** 64 - 1)), int(n_rep), int(I), int(n_sites), _d(out)))
+    return out
 
 
 def last_expm_kernel() -> str:
@@ -715,6 +727,30 @@ class HipPartition:
             assert cls.shape == (self.S,)
         out = np.full((self.I + (self.L if do_leaves else 0), self.S), -2, dtype=np.int64)
         _check(self._lib.hyphy_hip_joint_ancestral(self._h, int(bool(do_leaves)), _l(cls), _l(out)))
+        return out
+
+    def sample_ancestral(self, n_rep: int, pattern_of_site=None, class_of_pattern=None, seed: int = 0, uniforms=None) -> np.ndarray:
+        """Posterior draws of the internal nodes' states (the reference's ``SampleAncestors``) under the matrices, root frequencies,
+        leaf data and conditionals of the last evaluation: int8 [n_rep, I, n_sites], internal index (the root last), -1 where the
+        pattern is impossible.  ``pattern_of_site`` [n_sites]: the pattern each site shows (default: site j = pattern j);
+        ``class_of_pattern`` [S]: the rate class of each pattern (default: class 0); ``uniforms`` [n_rep, I, n_sites] in [0, 1): the
+        uniform of every draw (default: Philox4x32-10 keyed by ``seed``, see ``sample_uniforms``).  Nothing on the device changes."""
+        pos = None
+        n_sites = self.S
+        if pattern_of_site is not None:
+            pos = np.ascontiguousarray(pattern_of_site, dtype=np.int64).reshape(-1)
+            n_sites = len(pos)
+        cls = None
+        if class_of_pattern is not None:
+            cls = np.ascontiguousarray(class_of_pattern, dtype=np.int64)
+            assert cls.shape == (self.S,)
+        u = None
+        if uniforms is not None:
+            u = np.ascontiguousarray(uniforms, dtype=np.float64)
+            assert u.shape == (int(n_rep), self.I, n_sites)
+        out = np.full((int(n_rep), self.I, n_sites), -2, dtype=np.int8)
+        _check(self._lib.hyphy_hip_sample_ancestral(self._h, int(n_rep), n_sites, _l(pos), _l(cls), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                                    _d(u), out.ctypes.data_as(C.POINTER(C.c_int8))))
         return out
 
     # -- trial matrices on any number of branches from one outside pass ----------------------------

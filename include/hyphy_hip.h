@@ -474,6 +474,43 @@ int hyphy_hip_branch_trials_built(hyphy_hip_partition *p, int64_t n_trials, cons
 int hyphy_hip_joint_ancestral(hyphy_hip_partition *p, int do_leaves, const int64_t *class_of_pattern /* [S] or NULL */,
                               int64_t *states_out /* [I (+ L)][S] */);
 
+/* ---- sampled ancestral reconstruction ------------------------------------------------------------------------
+ * Replaces _TheTree::SampleAncestorsBySequence (src/core/tree.cpp:4086-4205), the `sample == true` mode of ReconstructAncestors
+ * (HBL's SampleAncestors): posterior draws of the states of the internal nodes, root first; leaves are never sampled.
+ * A draw is (replicate r, site j, internal node n).  Site j shows pattern s = pattern_of_site[j], which belongs to rate class
+ * c = class_of_pattern[s].  With in_n the stored conditional of node n at pattern s in class c:
+ *   root (n = I-1): w[i] = pi[i] * in_n[i];  otherwise: w[i] = P_n^(c)[state of the parent][i] * in_n[i]   (one rounded product)
+ *   total = w[0] + ... + w[D-1] in ascending i, every addition rounded (no fused multiply-add, no reassociation);  x = u * total
+ *   state = the smallest i with cum_i >= x and cum_i > 0, cum_i the same running sum
+ * The 2^64 scaler of a stored conditional cancels within a draw and is not applied.
+ * Two deviations from the reference: total == 0 or NaN (an impossible pattern) gives state -1, and every descendant of a -1 node
+ * is -1 (the reference would index row -1); u == 0 picks the first state of positive weight (the reference's
+ * `while (totalSum < randVal)` returns -1 there).
+ *   pattern_of_site    [n_sites] pattern of each site, caller's pattern order; NULL: site j = pattern j, n_sites == S
+ *   class_of_pattern   [S] rate class of each pattern; NULL: class 0 everywhere
+ *   uniforms           [n_rep][I][n_sites], each in [0, 1): the uniform of every draw (an adapter can hand over the reference's own
+ *                      Mersenne-Twister stream in the reference's order: node in pre-order, then pattern, then site).  NULL: the
+ *                      device generates them with Philox4x32-10, key = (seed low 32 bits, seed high 32 bits), counter =
+ *                      (j, n, r, 0), u = ((x0 >> 5) * 2^26 + (x1 >> 6)) * 2^-53 from the first two output words (multipliers
+ *                      0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85): a draw depends on (seed, r, j, n) only,
+ *                      not on chunking, shards, device count or the device's pattern order
+ *   states_out         [n_rep][I][n_sites] signed bytes (D <= 64), internal index, the root last; -1 or [0, D)
+ * Uses the matrices, leaf data and conditionals of the last evaluation of each class that is referenced and the root frequencies of
+ * the last evaluation; conditionals a lazy pass did not keep are restored first (as hyphy_hip_download_partials does).  Leaves no
+ * state behind: later evaluations, partial updates, branch-cache slots and hyphy_hip_last_expm_kernel are unchanged, and two
+ * identical calls give identical arrays.  Scratch (a byte, and with `uniforms` a double, per draw) comes from the pool and is
+ * returned before the call returns; the pass runs over chunks (replicates x 16-pattern tiles) that keep it within
+ * HYPHY_HIP_SAMPLE_MB (default 1024, read at every call, at least one tile x one replicate).
+ * Returns < 0 on a NULL partition or output, an active pin, a pattern or class index out of range, a referenced class never
+ * evaluated, or a supplied uniform outside [0, 1); n_rep == 0 or n_sites == 0 returns 0 and writes nothing. */
+int hyphy_hip_sample_ancestral(hyphy_hip_partition *p, int64_t n_rep, int64_t n_sites,
+                               const int64_t *pattern_of_site /* [n_sites] or NULL */,
+                               const int64_t *class_of_pattern /* [S] or NULL */, uint64_t seed,
+                               const double *uniforms /* [n_rep][I][n_sites] or NULL */,
+                               int8_t *states_out /* [n_rep][I][n_sites] */);
+/* host-only, no device: the uniforms the call above would use with uniforms == NULL, out[n_rep][I][n_sites] */
+int hyphy_hip_sample_uniforms(uint64_t seed, int64_t n_rep, int64_t I, int64_t n_sites, double *out);
+
 /* ---- branch cache ---------------------------------------------------------------------
  * Replaces _TheTree::ComputeBranchCache (src/core/tree_evaluator.cpp:4286-4845) and
  * _TheTree::ComputeLLWithBranchCache (src/core/tree.cpp:3383-3936), driven by the policy code of
