@@ -32,6 +32,21 @@ constexpr double kLogScaler = 64.0 * 0.69314718055994530942;    // _logLFScaler
 // so a node's freshly computed conditionals feed its parent's product with no data movement.
 // ---------------------------------------------------------------------------------------
 __host__ __device__ inline int frag_index(int kk, int lane) { return (((kk >> 1) * 64 + lane) << 1) + (kk & 1); }
+// ... and its inverse over a whole A-operand image ([NW][NKK*64], row block w = FRAG with lane's low bits the row): double idx is M[row][col]
+__host__ __device__ inline void frag_image_rc(int idx, int NW, int &row, int &col) {
+  const int w = idx / (NW * 256), rem = idx - w * (NW * 256);
+  const int l = (rem >> 1) & 63, kk = 2 * (rem >> 7) + (rem & 1);
+  row = 16 * w + (l & 15), col = 4 * kk + (l >> 4);
+}
+
+// launch of a kernel templated on NW (row blocks of 16 states, 1..4) at its instantiation for `nw`
+#define LAUNCH_NW(kernel, nw, grid, block, stream, ...)                                      \
+  switch (nw) {                                                                              \
+    case 1: hipLaunchKernelGGL(kernel<1>, grid, block, 0, stream, __VA_ARGS__); break;       \
+    case 2: hipLaunchKernelGGL(kernel<2>, grid, block, 0, stream, __VA_ARGS__); break;       \
+    case 3: hipLaunchKernelGGL(kernel<3>, grid, block, 0, stream, __VA_ARGS__); break;       \
+    default: hipLaunchKernelGGL(kernel<4>, grid, block, 0, stream, __VA_ARGS__); break;      \
+  }
 
 // Host-compiled schedule entry (int4), built by build_schedule() in api.hip:
 //   x  bits 0-1  kind: OPK_LEAF (group of <= 2 leaf children), OPK_INTERNAL (child vector in an LDS

@@ -96,6 +96,17 @@ __device__ __forceinline__ double row_sum4(double x) {
   return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
 }
 
+// column `code` of a matrix out of its column-gather image ([code][w][g][r] = P[16w + 4r + g][code]) at this lane's rows: the edge
+// product of a leaf without ambiguity codes, as a fragment vector
+template <int NW>
+__device__ __forceinline__ void gather_column(const double *Pg, int code, int g, double (&E)[4 * NW]) {
+#pragma unroll
+  for (int w = 0; w < NW; w++) {
+    const unsigned off = (unsigned)((code * NW + w) * 16 + g * 4) * 8u;
+    const f64x2 v0 = ld16(Pg, off), v1 = ld16(Pg, off + 16u);
+    E[4 * w] = v0[0], E[4 * w + 1] = v0[1], E[4 * w + 2] = v1[0], E[4 * w + 3] = v1[1];
+  }
+}
 
 }  // namespace
 }  // namespace hyhip

@@ -135,14 +135,8 @@ __global__ __launch_bounds__(256) void joint_kernel(JointArgs a) {
           }
         } else {
           const int code = (int)a.codes[(size_t)c * a.S_pad + pat];
-          if (code >= 0) {  // column gather, [code][w][g][r] = P[16w + 4r + g][code]
-            const double *Pg = a.PTg + (size_t)c * DP * DP;
-#pragma unroll
-            for (int w = 0; w < NW; w++) {
-              const unsigned off = (unsigned)((code * NW + w) * 16 + g * 4) * 8u;
-              const f64x2 v0 = ld16(Pg, off), v1 = ld16(Pg, off + 16u);
-              f[4 * w] = v0[0], f[4 * w + 1] = v0[1], f[4 * w + 2] = v1[0], f[4 * w + 3] = v1[1];
-            }
+          if (code >= 0) {
+            gather_column<NW>(a.PTg + (size_t)c * DP * DP, code, g, f);
           } else {
             const double *av = a.ambig + (size_t)(-code - 1) * DP;
             const double *Pf = a.Pfrag + (size_t)c * DP * DP;
@@ -189,9 +183,8 @@ __global__ __launch_bounds__(256) void joint_kernel(JointArgs a) {
     {  // stage the matrix of branch L + n
       const double *Pf = a.Pfrag + (size_t)(L + n) * DP * DP;
       for (int idx = threadIdx.x; idx < DP * DP; idx += 256) {
-        const int w = idx / TILE, rem = idx - w * TILE;
-        const int k2 = rem >> 7, l = (rem >> 1) & 63, kk = 2 * k2 + (rem & 1);
-        const int row = 16 * w + (l & 15), c = 4 * kk + (l >> 4);
+        int row, c;
+        frag_image_rc(idx, NW, row, c);
         const double x = Pf[idx];
         Pl[c * DP + (row & 3) * NKK + (row >> 2)] = row < D && c < D ? x : 0.;
       }
@@ -380,24 +373,6 @@ __global__ __launch_bounds__(256) void joint_nuc_kernel(JointArgs a) {
   }
 }
 
-// pool blocks of one call, returned (behind a synchronisation) when it ends
-struct Blocks {
-  std::vector<void *> held;
-  ~Blocks() { release(); }
-  void release() {
-    for (void *b : held) pool_free_sync(b);
-    held.clear();
-  }
-  template <typename T>
-  hipError_t get(T **out, size_t n) {
-    void *b = nullptr;
-    const hipError_t e = pool_malloc(&b, std::max<size_t>(1, n) * sizeof(T));
-    if (e == hipSuccess) held.push_back(b);
-    *out = (T *)b;
-    return e;
-  }
-};
-
 }  // namespace
 }  // namespace hyhip
 
@@ -406,7 +381,7 @@ extern "C" {
 int hyphy_hip_joint_ancestral(hyphy_hip_partition *p, int do_leaves, const int64_t *class_of_pattern, int64_t *states_out) {
   if (!p) return fail("joint_ancestral: partition == NULL");
   if (!states_out) return fail("joint_ancestral: states_out == NULL");
-  if (p->pin_node >= 0) return fail("joint_ancestral: a node's states are pinned (clear the pin first)");
+  if (check_unpinned(p, "joint_ancestral: ")) return -1;
   const int C = (int)p->C;
   const int64_t D = p->D, L = p->L, I = p->I, B = p->B, S = p->S;
   std::vector<char> used((size_t)C, 0);
@@ -418,9 +393,7 @@ int hyphy_hip_joint_ancestral(hyphy_hip_partition *p, int do_leaves, const int64
         return fail("joint_ancestral: pattern " + std::to_string(i) + ": rate class " + std::to_string(c) + " out of range");
       used[(size_t)c] = 1;
     }
-  for (int c = 0; c < C; c++)
-    if (used[(size_t)c] && (!p->initialized[(size_t)c] || p->cached_pi.size() != (size_t)D))
-      return fail("joint_ancestral: rate class " + std::to_string(c) + " has not been evaluated");
+  if (check_evaluated(p, "joint_ancestral: ", &used)) return -1;
   if (finish_pending_async(p)) return -1;
   const int DP = p->DP, NW = p->NW;
   const bool nuc = p->nuc;
@@ -436,10 +409,8 @@ int hyphy_hip_joint_ancestral(hyphy_hip_partition *p, int do_leaves, const int64
     std::vector<int32_t> fill(kid_off.begin(), kid_off.end() - 1);
     for (int64_t c = 0; c < L + I - 1; c++) kids[(size_t)fill[(size_t)p->parents[(size_t)c]]++] = (int32_t)c;
   }
-  std::vector<double> pi_pad((size_t)(nuc ? 4 : DP), 0.);
-  for (int64_t j = 0; j < D; j++) pi_pad[(size_t)j] = p->cached_pi[(size_t)j];
-  const char *mb_env = getenv("HYPHY_HIP_JOINT_MB");  // (read per call)
-  const double budget = (mb_env && atof(mb_env) > 0. ? atof(mb_env) : 1024.) * 1048576.;
+  const std::vector<double> pi_pad = padded_pi(p);
+  const double budget = scratch_budget("HYPHY_HIP_JOINT_MB");
   const int TP = nuc ? 64 : 16;                                                  // patterns of a tile
   const size_t tile_msg = nuc ? (size_t)4 * 64 : (size_t)16 * DP;                // doubles of one node's msg per tile
   const size_t tile_bp = nuc ? (size_t)64 : (size_t)64 * NW;                     // words of its backpointers
@@ -496,22 +467,13 @@ int hyphy_hip_joint_ancestral(hyphy_hip_partition *p, int do_leaves, const int64
         a.tile0 = tile0, a.nt = std::min(ct, ntiles - tile0);
         const dim3 grid((unsigned)((a.nt + 3) / 4)), block(256);
         if (nuc) hipLaunchKernelGGL(joint_nuc_kernel, grid, block, 0, s.stream, a);
-        else
-          switch (NW) {
-            case 1: hipLaunchKernelGGL(joint_kernel<1>, grid, block, 0, s.stream, a); break;
-            case 2: hipLaunchKernelGGL(joint_kernel<2>, grid, block, 0, s.stream, a); break;
-            case 3: hipLaunchKernelGGL(joint_kernel<3>, grid, block, 0, s.stream, a); break;
-            default: hipLaunchKernelGGL(joint_kernel<4>, grid, block, 0, s.stream, a); break;
-          }
+        else LAUNCH_NW(joint_kernel, NW, grid, block, s.stream, a);
         HIPCHK(hipGetLastError());
       }
       h_out.resize((size_t)rows * npad);
       HIPCHK(hipMemcpyAsync(h_out.data(), d_out, h_out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s.stream));
       HIPCHK(hipStreamSynchronize(s.stream));
-      // -> the caller's pattern order: out[row][caller pattern]
-      for (int64_t r = 0; r < rows; r++)
-        for (int64_t k = 0; k < n; k++)
-          states_out[(size_t)r * S + caller_pattern(p, s.s0 + (list.empty() ? k : list[(size_t)k]))] = h_out[(size_t)r * npad + k];
+      rows_to_caller(p, s, h_out.data(), npad, rows, n, states_out, list.empty() ? nullptr : list.data());
     }
   }
   return 0;

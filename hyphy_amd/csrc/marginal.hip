@@ -12,14 +12,17 @@
 // The sibling products come from a prefix pass (prefix product stored per child, edge products stored beside it) and a suffix
 // pass in reverse child order: every edge product is formed once, every needed transposed product once.
 //
-// Decomposition (MFMA path, every state count but 4 — 2..64): one wave per 16-pattern tile walks the host-compiled pre-order program (plan_marginal
-// below).  Vectors live in the fragment layout (common.h), so elementwise products are lane-local and the MFMA's C/D image of
-// a product is the B operand of the next one.  The outside vectors and their exponents go to a scratch block shaped like one
-// class of the partials ([I][ntiles][TILE] + [I][S_pad]); the prefix / edge products of the children of the node being walked
-// go to a per-tile work area ([ntiles][2 * max children][TILE]).  A tile is owned by one wave: no synchronisation.
-// 4 states: one thread per pattern, the same walk over the [I][4][S_pad] plane layout.
+// Decomposition: the walk is outside.h's — outside_walk<NW> (every state count but 4: one wave per 16-pattern tile over the
+// host-compiled pre-order program, plan_marginal_program below, vectors in the fragment layout of common.h, so elementwise products
+// are lane-local and the MFMA's C/D image of a product is the B operand of the next one) and outside_walk_nuc (4 states: one thread
+// per pattern over the [I][4][S_pad] planes).  The kernels here are that walk with MargSink, which accumulates num_n at every node
+// (which == 0) or num_l at every leaf (which == 1).  The chunk of the walk is the whole shard: the outside vectors and their
+// exponents go to a scratch block shaped like one class of the partials ([I][ntiles][TILE] + [I][S_pad]), the prefix / edge
+// products of the children of the node being walked to a per-tile work area ([ntiles][2 * max children][TILE]).  A tile is owned
+// by one wave: no synchronisation.  That scratch stays with the shard (Shard::marg_*) until the partition is destroyed.
 // Classes run one after another (one launch each), accumulating into the output block [rows][S][D] with a denominator and an
-// exponent per (row, pattern); a last kernel normalises in place and picks the MAP state.
+// exponent per (row, pattern); a last kernel normalises in place and picks the MAP state.  The output block and its companions are
+// per-call pool blocks.
 #include "devutil.h"
 #include "outside.h"
 #include "partition.h"
@@ -29,203 +32,103 @@ using namespace hyhip;
 namespace hyhip {
 namespace {
 
-// add w * num (exponent e) to the accumulated support of `row`; den = sum of num * lv over the states
-template <int NKK>
-__device__ __forceinline__ void accumulate(const MargArgs &a, int row, int site, int g, const double (&num)[NKK], double den, int e) {
-  if (site >= a.S) return;
-  double *out = a.acc + ((size_t)row * a.S + site) * a.D;
-  const size_t q = (size_t)row * a.S_pad + site;
-  if (a.first) {
+// The walk's sink: the support block [rows][S][D] of the call, with a denominator and a 2^64 exponent per (row, pattern), and which
+// rows it has — the internal nodes (which == 0: `node`) or the leaves (which == 1: `leaf`, U_l / sum_y U_l(y) leafvec_l(y))
+struct MargSink {
+  static constexpr bool kLeafProduct = true;
+  double w;        // weight of this class (1 when C == 1)
+  int first;       // the first class: store, do not add
+  int which, D, S;
+  double *acc;     // [rows][S][D]
+  double *den;     // [rows][S_pad]
+  int32_t *aexp;   // [rows][S_pad]
+
+  __device__ __forceinline__ bool leaves() const { return which == 1; }
+
+  // add w * num (exponent e) to the accumulated support of `row`; den = sum of num * lv over the states
+  template <int NKK>
+  __device__ __forceinline__ void add(const WalkArgs &a, int row, int site, int g, const double (&num)[NKK], double dn, int e) const {
+    if (site >= S) return;
+    double *out = acc + ((size_t)row * S + site) * D;
+    const size_t q = (size_t)row * a.S_pad + site;
+    if (first) {
+#pragma unroll
+      for (int kk = 0; kk < NKK; kk++)
+        if (4 * kk + g < D) out[4 * kk + g] = w * num[kk];
+      if (g == 0) {
+        den[q] = w * dn;
+        aexp[q] = e;
+      }
+      return;
+    }
+    const int e_old = aexp[q];
+    const double d_old = den[q];
+    const int e_new = min(e_old, e);  // (true value = stored * 2^(-64 e): the smaller exponent is the larger scale)
+    const double f_old = ldexp(1.0, -64 * (e_old - e_new)), f_new = w * ldexp(1.0, -64 * (e - e_new));
 #pragma unroll
     for (int kk = 0; kk < NKK; kk++)
-      if (4 * kk + g < a.D) out[4 * kk + g] = a.w * num[kk];
+      if (4 * kk + g < D) out[4 * kk + g] = out[4 * kk + g] * f_old + num[kk] * f_new;
     if (g == 0) {
-      a.den[q] = a.w * den;
-      a.aexp[q] = e;
+      den[q] = d_old * f_old + dn * f_new;
+      aexp[q] = e_new;
     }
-    return;
   }
-  const int e_old = a.aexp[q];
-  const double d_old = a.den[q];
-  const int e_new = min(e_old, e);  // (true value = stored * 2^(-64 e): the smaller exponent is the larger scale)
-  const double f_old = ldexp(1.0, -64 * (e_old - e_new)), f_new = a.w * ldexp(1.0, -64 * (e - e_new));
+  template <int NKK>
+  __device__ __forceinline__ void node(const WalkArgs &a, int n, int tile, int lane, const double (&pre)[NKK], int pcnt) const {
+    if (which != 0) return;  // in_n * U_n
+    double t = 0.;
 #pragma unroll
-  for (int kk = 0; kk < NKK; kk++)
-    if (4 * kk + g < a.D) out[4 * kk + g] = out[4 * kk + g] * f_old + num[kk] * f_new;
-  if (g == 0) {
-    a.den[q] = d_old * f_old + den * f_new;
-    a.aexp[q] = e_new;
+    for (int kk = 0; kk < NKK; kk++) t += pre[kk];
+    add<NKK>(a, n, tile * 16 + (lane & 15), lane >> 4, pre, row_sum4(t), pcnt);
   }
-}
+  template <int NKK>
+  __device__ __forceinline__ void branch(const WalkArgs &, int, int, int, const double (&)[NKK], int) const {}
+  template <int NKK>
+  __device__ __forceinline__ void leaf(const WalkArgs &a, int l, int tile, int lane, const double (&U)[NKK], int vcnt) const {
+    const int g = lane >> 4, sl = lane & 15;
+    const int c = (int)a.codes_tile[((size_t)tile * a.L + l) * 16 + sl];
+    double lv[NKK];
+    leaf_vec<NKK>(a, c, g, lv);
+    double t = 0.;
+#pragma unroll
+    for (int kk = 0; kk < NKK; kk++) t += U[kk] * lv[kk];
+    add<NKK>(a, l, tile * 16 + sl, g, U, row_sum4(t), vcnt);
+  }
+
+  // 4 states: one thread per pattern
+  __device__ __forceinline__ void add(const WalkArgs &a, int row, size_t s, const double (&num)[4], double dn, int e) const {
+    if (s >= (size_t)S) return;
+    double *out = acc + ((size_t)row * S + s) * 4;
+    const size_t q = (size_t)row * a.S_pad + s;
+    if (first) {
+      for (int j = 0; j < 4; j++) out[j] = w * num[j];
+      den[q] = w * dn;
+      aexp[q] = e;
+      return;
+    }
+    const int e_old = aexp[q], e_new = min(e_old, e);
+    const double f_old = ldexp(1.0, -64 * (e_old - e_new)), f_new = w * ldexp(1.0, -64 * (e - e_new));
+    for (int j = 0; j < 4; j++) out[j] = out[j] * f_old + num[j] * f_new;
+    den[q] = den[q] * f_old + dn * f_new;
+    aexp[q] = e_new;
+  }
+  __device__ __forceinline__ void node(const WalkArgs &a, int n, size_t s, const double (&pre)[4], int pcnt) const {
+    if (which == 0) add(a, n, s, pre, (pre[0] + pre[1]) + (pre[2] + pre[3]), pcnt);
+  }
+  __device__ __forceinline__ void branch(const WalkArgs &, int, size_t, const double (&)[4], int) const {}
+  __device__ __forceinline__ void leaf(const WalkArgs &a, int l, size_t s, const double (&U)[4], int vcnt) const {
+    double lv[4];
+    nuc_leaf_vec(a, (int)a.codes[(size_t)l * a.S_pad + s], lv);
+    add(a, l, s, U, (U[0] * lv[0] + U[1] * lv[1]) + (U[2] * lv[2] + U[3] * lv[3]), vcnt);
+  }
+};
 
 template <int NW>
-__global__ __launch_bounds__(64) void marginal_mfma_kernel(MargArgs a) {
-  constexpr int NKK = 4 * NW, TILE = NKK * 64;
-  const int lane = threadIdx.x, g = lane >> 4, sl = lane & 15;
-  const int tile = blockIdx.x, site = tile * 16 + sl;
-  double *work = a.work + (size_t)tile * 2 * a.maxk * TILE;
-  int32_t *wcnt = a.wcnt + (size_t)tile * 2 * a.maxk * 16;
-  for (int pc = 0; pc < a.n_prog;) {
-    const int4 h = a.prog[pc];
-    const int node = h.y, k = h.z;
-    double pre[NKK];
-    int pcnt = 0;
-    if (h.w) {  // the root: U = pi
-#pragma unroll
-      for (int kk = 0; kk < NKK; kk++) pre[kk] = a.pi[4 * kk + g];
-    } else {
-      ld_vec<NKK>(a.U + ((size_t)node * a.ntiles + tile) * TILE, lane, pre);
-      pcnt = a.Ucnt[(size_t)node * a.S_pad + site];
-    }
-    // prefix pass: slot 2i = U_p * prod_{j < i} E_j, slot 2i + 1 = E_i
-    for (int i = 0; i < k; i++) {
-      const int4 ce = a.prog[pc + 1 + i];
-      double E[NKK];
-      int ecnt;
-      edge_product<NW>(a, ce, tile, lane, E, ecnt);
-      st_vec<NKK>(work + (size_t)(2 * i) * TILE, lane, pre);
-      st_vec<NKK>(work + (size_t)(2 * i + 1) * TILE, lane, E);
-      wcnt[(2 * i) * 16 + sl] = pcnt;  // (every lane of the pattern stores the same word: each reads back its own store)
-      wcnt[(2 * i + 1) * 16 + sl] = ecnt;
-#pragma unroll
-      for (int kk = 0; kk < NKK; kk++) pre[kk] *= E[kk];
-      pcnt += ecnt;
-      rescale_vec<NKK>(pre, pcnt);
-    }
-    if (a.which == 0) {  // in_n * U_n
-      double t = 0.;
-#pragma unroll
-      for (int kk = 0; kk < NKK; kk++) t += pre[kk];
-      accumulate<NKK>(a, node, site, g, pre, row_sum4(t), pcnt);
-    }
-    // suffix pass, children in reverse order
-    double suf[NKK];
-#pragma unroll
-    for (int kk = 0; kk < NKK; kk++) suf[kk] = 1.;
-    int scnt = 0;
-    for (int i = k - 1; i >= 0; i--) {
-      const int4 ce = a.prog[pc + 1 + i];
-      if (ce.z >= 0 || a.which == 1) {
-        double V[NKK], U[NKK];
-        ld_vec<NKK>(work + (size_t)(2 * i) * TILE, lane, V);
-#pragma unroll
-        for (int kk = 0; kk < NKK; kk++) V[kk] *= suf[kk];
-        int vcnt = wcnt[(2 * i) * 16 + sl] + scnt;
-        rescale_vec<NKK>(V, vcnt);
-        mfma_product<NW>(a.PT + (size_t)ce.y * 16 * NW * 16 * NW, V, lane, U);
-        if (ce.z >= 0) {
-          rescale_vec<NKK>(U, vcnt);
-          st_vec<NKK>(a.U + ((size_t)ce.z * a.ntiles + tile) * TILE, lane, U);
-          a.Ucnt[(size_t)ce.z * a.S_pad + site] = vcnt;
-        } else {  // leaf (DOLEAVES): U_l / sum_y U_l(y) leafvec_l(y)
-          const int c = (int)a.codes_tile[((size_t)tile * a.L + ce.y) * 16 + sl];
-          double lv[NKK];
-          leaf_vec<NKK>(a, c, g, lv);
-          double t = 0.;
-#pragma unroll
-          for (int kk = 0; kk < NKK; kk++) t += U[kk] * lv[kk];
-          accumulate<NKK>(a, ce.y, site, g, U, row_sum4(t), vcnt);
-        }
-      }
-      if (i > 0) {
-        double E[NKK];
-        ld_vec<NKK>(work + (size_t)(2 * i + 1) * TILE, lane, E);
-#pragma unroll
-        for (int kk = 0; kk < NKK; kk++) suf[kk] *= E[kk];
-        scnt += wcnt[(2 * i + 1) * 16 + sl];
-        rescale_vec<NKK>(suf, scnt);
-      }
-    }
-    pc += 1 + k;
-  }
+__global__ __launch_bounds__(64) void marginal_mfma_kernel(WalkArgs a, MargSink k) {
+  outside_walk<NW>(a, k);
 }
 
-// 4 states: one thread per pattern (argument block and helpers: outside.h)
-__device__ __forceinline__ void nuc_accumulate(const MargNucArgs &a, int row, int s, const double (&num)[4], double den, int e) {
-  if (s >= a.S) return;
-  double *out = a.acc + ((size_t)row * a.S + s) * 4;
-  const size_t q = (size_t)row * a.S_pad + s;
-  if (a.first) {
-    for (int j = 0; j < 4; j++) out[j] = a.w * num[j];
-    a.den[q] = a.w * den;
-    a.aexp[q] = e;
-    return;
-  }
-  const int e_old = a.aexp[q], e_new = min(e_old, e);
-  const double f_old = ldexp(1.0, -64 * (e_old - e_new)), f_new = a.w * ldexp(1.0, -64 * (e - e_new));
-  for (int j = 0; j < 4; j++) out[j] = out[j] * f_old + num[j] * f_new;
-  a.den[q] = a.den[q] * f_old + den * f_new;
-  a.aexp[q] = e_new;
-}
-
-__global__ __launch_bounds__(256) void marginal_nuc_kernel(MargNucArgs a) {
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= a.S_pad) return;
-  const size_t SP = a.S_pad;
-  for (int pc = 0; pc < a.n_prog;) {
-    const int4 h = a.prog[pc];
-    const int node = h.y, k = h.z;
-    double pre[4];
-    int pcnt = 0;
-    if (h.w) {
-      for (int j = 0; j < 4; j++) pre[j] = a.pi[j];
-    } else {
-      for (int j = 0; j < 4; j++) pre[j] = a.U[((size_t)node * 4 + j) * SP + s];
-      pcnt = a.Ucnt[(size_t)node * SP + s];
-    }
-    for (int i = 0; i < k; i++) {
-      const int4 ce = a.prog[pc + 1 + i];
-      const double *P = a.P + (size_t)ce.y * 16;
-      double in[4], E[4];
-      int ecnt = 0;
-      if (ce.z >= 0) {
-        for (int j = 0; j < 4; j++) in[j] = a.partials[((size_t)ce.z * 4 + j) * SP + s];
-        ecnt = a.counts[(size_t)ce.z * SP + s];
-      } else {
-        nuc_leaf_vec(a, (int)a.codes[(size_t)ce.y * SP + s], in);
-      }
-      for (int x = 0; x < 4; x++) E[x] = P[4 * x] * in[0] + P[4 * x + 1] * in[1] + P[4 * x + 2] * in[2] + P[4 * x + 3] * in[3];
-      for (int j = 0; j < 4; j++) {
-        a.work[((size_t)(2 * i) * 4 + j) * SP + s] = pre[j];
-        a.work[((size_t)(2 * i + 1) * 4 + j) * SP + s] = E[j];
-        pre[j] *= E[j];
-      }
-      a.wcnt[(size_t)(2 * i) * SP + s] = pcnt;
-      a.wcnt[(size_t)(2 * i + 1) * SP + s] = ecnt;
-      pcnt += ecnt;
-      rescale4(pre, pcnt);
-    }
-    if (a.which == 0) nuc_accumulate(a, node, s, pre, (pre[0] + pre[1]) + (pre[2] + pre[3]), pcnt);
-    double suf[4] = {1., 1., 1., 1.};
-    int scnt = 0;
-    for (int i = k - 1; i >= 0; i--) {
-      const int4 ce = a.prog[pc + 1 + i];
-      if (ce.z >= 0 || a.which == 1) {
-        const double *P = a.P + (size_t)ce.y * 16;
-        double V[4], U[4];
-        for (int j = 0; j < 4; j++) V[j] = a.work[((size_t)(2 * i) * 4 + j) * SP + s] * suf[j];
-        int vcnt = a.wcnt[(size_t)(2 * i) * SP + s] + scnt;
-        rescale4(V, vcnt);
-        for (int y = 0; y < 4; y++) U[y] = P[y] * V[0] + P[4 + y] * V[1] + P[8 + y] * V[2] + P[12 + y] * V[3];
-        if (ce.z >= 0) {
-          rescale4(U, vcnt);
-          for (int j = 0; j < 4; j++) a.U[((size_t)ce.z * 4 + j) * SP + s] = U[j];
-          a.Ucnt[(size_t)ce.z * SP + s] = vcnt;
-        } else {
-          double lv[4];
-          nuc_leaf_vec(a, (int)a.codes[(size_t)ce.y * SP + s], lv);
-          nuc_accumulate(a, ce.y, s, U, (U[0] * lv[0] + U[1] * lv[1]) + (U[2] * lv[2] + U[3] * lv[3]), vcnt);
-        }
-      }
-      if (i > 0) {
-        for (int j = 0; j < 4; j++) suf[j] *= a.work[((size_t)(2 * i + 1) * 4 + j) * SP + s];
-        scnt += a.wcnt[(size_t)(2 * i + 1) * SP + s];
-        rescale4(suf, scnt);
-      }
-    }
-    pc += 1 + k;
-  }
-}
+__global__ __launch_bounds__(256) void marginal_nuc_kernel(WalkArgs a, MargSink k) { outside_walk_nuc(a, k); }
 
 // support = accumulated numerator / denominator, in place; MAP state (first maximum) and its support
 __global__ __launch_bounds__(256) void marginal_finish_kernel(double *__restrict__ acc, const double *__restrict__ den, int rows, int S,
@@ -300,12 +203,10 @@ int hyphy_hip_marginal_ancestral(hyphy_hip_partition *p, int64_t which, const do
                                  int64_t *map_state_out, double *map_support_out) {
   if (!p) return fail("marginal_ancestral: partition == NULL");
   if (which != 0 && which != 1) return fail("marginal_ancestral: which must be 0 (internal nodes) or 1 (leaves)");
-  if (p->pin_node >= 0) return fail("marginal_ancestral: a node's states are pinned (clear the pin first)");
+  if (check_unpinned(p, "marginal_ancestral: ")) return -1;
   const int C = (int)p->C;
   if (C > 1 && !weights) return fail("marginal_ancestral: class weights are required when C > 1");
-  for (int c = 0; c < C; c++)
-    if (!p->initialized[c] || p->cached_pi.size() != (size_t)p->D)
-      return fail("marginal_ancestral: rate class " + std::to_string(c) + " has not been evaluated");
+  if (check_evaluated(p, "marginal_ancestral: ")) return -1;
   if (finish_pending_async(p)) return -1;
   for (int c = 0; c < C; c++)
     if (ensure_resident(p, c)) return -1;
@@ -317,8 +218,7 @@ int hyphy_hip_marginal_ancestral(hyphy_hip_partition *p, int64_t which, const do
   if (p->marg_prog.empty()) p->marg_prog = plan_marginal_program(L, I, p->parents.data(), &p->marg_maxk);
   const std::vector<int4> &prog = p->marg_prog;
   const int maxk = p->marg_maxk;
-  std::vector<double> pi_pad((size_t)(p->nuc ? 4 : DP), 0.);
-  for (int64_t j = 0; j < D; j++) pi_pad[(size_t)j] = p->cached_pi[(size_t)j];
+  const std::vector<double> pi_pad = padded_pi(p);
   for (Shard &s : p->shards) {
     HIPCHK(hipSetDevice(s.device));
     HIPCHK(hipStreamSynchronize(s.stream));
@@ -344,56 +244,25 @@ int hyphy_hip_marginal_ancestral(hyphy_hip_partition *p, int64_t which, const do
       for (size_t b : bytes) s.dev_bytes += b;
     }
     HIPCHK(hipMemcpy(s.marg_pi, pi_pad.data(), pi_pad.size() * sizeof(double), hipMemcpyHostToDevice));
+    Blocks blk;  // the call's own blocks: back to the pool on every way out of this shard
     double *acc = nullptr, *den = nullptr, *msup = nullptr;
     int32_t *aexp = nullptr, *mst = nullptr;
     const size_t nrs = (size_t)rows * s.S;
-    hipError_t e = pool_malloc((void **)&acc, std::max<size_t>(1, nrs * D) * sizeof(double));
-    if (e == hipSuccess) e = pool_malloc((void **)&den, (size_t)rows * s.S_pad * sizeof(double));
-    if (e == hipSuccess) e = pool_malloc((void **)&aexp, (size_t)rows * s.S_pad * sizeof(int32_t));
-    if (e == hipSuccess) e = pool_malloc((void **)&msup, std::max<size_t>(1, nrs) * sizeof(double));
-    if (e == hipSuccess) e = pool_malloc((void **)&mst, std::max<size_t>(1, nrs) * sizeof(int32_t));
+    hipError_t e = blk.get(&acc, nrs * D);
+    if (e == hipSuccess) e = blk.get(&den, (size_t)rows * s.S_pad);
+    if (e == hipSuccess) e = blk.get(&aexp, (size_t)rows * s.S_pad);
+    if (e == hipSuccess) e = blk.get(&msup, nrs);
+    if (e == hipSuccess) e = blk.get(&mst, nrs);
     for (int c = 0; c < C && e == hipSuccess; c++) {
-      const double w = C > 1 ? weights[c] : 1.0;
+      WalkArgs a = walk_args(p, s, c);
+      a.prog = s.marg_prog, a.pi = s.marg_pi, a.PT = s.marg_PT;
+      a.U = s.marg_U, a.Ucnt = s.marg_Ucnt, a.work = s.marg_work, a.wcnt = s.marg_wcnt;
+      const MargSink k = {C > 1 ? weights[c] : 1.0, c == 0, (int)which, (int)D, (int)s.S, acc, den, aexp};
       if (p->nuc) {
-        MargNucArgs a;
-        a.prog = s.marg_prog;
-        a.n_prog = (int)prog.size();
-        a.L = (int)L, a.S = (int)s.S, a.S_pad = s.S_pad, a.maxk = maxk, a.which = (int)which, a.first = c == 0;
-        a.w = w;
-        a.P = s.Prow + (size_t)c * B * 16;
-        a.codes = s.codes;
-        a.ambig = s.ambig;
-        a.pi = s.marg_pi;
-        a.partials = s.partials + (size_t)c * s.partial_stride;
-        a.counts = s.counts + (size_t)c * I * s.S_pad;
-        a.U = s.marg_U, a.Ucnt = s.marg_Ucnt, a.work = s.marg_work, a.wcnt = s.marg_wcnt;
-        a.acc = acc, a.den = den, a.aexp = aexp;
-        hipLaunchKernelGGL(marginal_nuc_kernel, dim3((unsigned)((s.S_pad + 255) / 256)), dim3(256), 0, s.stream, a);
+        hipLaunchKernelGGL(marginal_nuc_kernel, dim3((unsigned)((s.S_pad + 255) / 256)), dim3(256), 0, s.stream, a, k);
       } else {
-        MargArgs a;
-        a.prog = s.marg_prog;
-        a.n_prog = (int)prog.size();
-        a.NW = NW, a.L = (int)L, a.S = (int)s.S, a.S_pad = s.S_pad, a.ntiles = s.ntiles, a.maxk = maxk, a.which = (int)which;
-        a.first = c == 0, a.D = (int)D;
-        a.w = w;
-        a.Pfrag = s.Pfrag + (size_t)c * B * DP * DP;
-        a.PTg = s.PTg + (size_t)c * B * DP * DP;
-        a.PT = s.marg_PT;
-        a.codes_tile = s.codes_tile;
-        a.ambig = s.ambig;
-        a.pi = s.marg_pi;
-        a.partials = s.partials + (size_t)c * s.partial_stride;
-        a.counts = s.counts + (size_t)c * I * s.S_pad;
-        a.U = s.marg_U, a.Ucnt = s.marg_Ucnt, a.work = s.marg_work, a.wcnt = s.marg_wcnt;
-        a.acc = acc, a.den = den, a.aexp = aexp;
         hipLaunchKernelGGL(marg_transpose_kernel, dim3((unsigned)B), dim3(256), 0, s.stream, a.Pfrag, a.PTg, s.marg_PT, NW, (int)L);
-        const dim3 grid((unsigned)s.ntiles), block(64);
-        switch (NW) {
-          case 1: hipLaunchKernelGGL(marginal_mfma_kernel<1>, grid, block, 0, s.stream, a); break;
-          case 2: hipLaunchKernelGGL(marginal_mfma_kernel<2>, grid, block, 0, s.stream, a); break;
-          case 3: hipLaunchKernelGGL(marginal_mfma_kernel<3>, grid, block, 0, s.stream, a); break;
-          default: hipLaunchKernelGGL(marginal_mfma_kernel<4>, grid, block, 0, s.stream, a); break;
-        }
+        LAUNCH_NW(marginal_mfma_kernel, NW, dim3((unsigned)s.ntiles), dim3(64), s.stream, a, k);
       }
       e = hipGetLastError();
     }
@@ -422,15 +291,9 @@ int hyphy_hip_marginal_ancestral(hyphy_hip_partition *p, int64_t which, const do
       std::vector<double> hv(nrs);
       e = hipMemcpy(hs.data(), mst, nrs * sizeof(int32_t), hipMemcpyDeviceToHost);
       if (e == hipSuccess) e = hipMemcpy(hv.data(), msup, nrs * sizeof(double), hipMemcpyDeviceToHost);
-      for (int64_t r = 0; r < rows && e == hipSuccess; r++)
-        for (int64_t k = 0; k < s.S; k++) {
-          const size_t o = (size_t)r * S + caller_pattern(p, s.s0 + k);
-          if (map_state_out) map_state_out[o] = hs[(size_t)r * s.S + k];
-          if (map_support_out) map_support_out[o] = hv[(size_t)r * s.S + k];
-        }
+      if (e == hipSuccess && map_state_out) rows_to_caller(p, s, hs.data(), (size_t)s.S, rows, s.S, map_state_out);
+      if (e == hipSuccess && map_support_out) rows_to_caller(p, s, hv.data(), (size_t)s.S, rows, s.S, map_support_out);
     }
-    for (void *d : {(void *)acc, (void *)den, (void *)aexp, (void *)msup, (void *)mst})
-      if (d) pool_free_sync(d);
     if (e != hipSuccess) return fail(std::string("marginal_ancestral: ") + hipGetErrorString(e));
   }
   return 0;

@@ -1,48 +1,72 @@
-// Device helpers of the pre-order ("outside") walks: the marginal reconstruction (marginal.hip) and the outside pass of the branch
-// trials (trials.hip) walk the same host-compiled program (plan_marginal_program) with the same products, the same 2^64 rescaling
-// and the same transposed matrix images.  gfx950 only.
+// The pre-order ("outside") walk over the resident conditionals, once per layout: outside_walk<NW, Sink> (fragment layout, one wave
+// per 16-pattern tile) and outside_walk_nuc<Sink> (4 states, plane layout, one thread per pattern).  Both walk the host-compiled
+// program (plan_marginal_program): per node load U_p (the root: pi), a prefix pass over the children into the work area (prefix
+// product and edge product per child), a suffix pass in reverse child order, V_c = prefix * suffix, U_c = P_c^T V_c, every vector
+// rescaled by 2^64 where the pruning pass would.  What a pass keeps is its sink's business — a small struct, inlined, with hooks
+//   node      a node's finished prefix product (= in_n * U_n) and its exponent
+//   leaves    whether the V of a leaf child is wanted at all
+//   branch    a child's rescaled V and its exponent
+//   leaf      a leaf's U = P_l^T V_l (not rescaled), formed only when the sink's kLeafProduct is set
+// in two forms each, told apart by their arguments: (tile, lane, fragment vector) and (pattern, 4 values).  The marginal
+// reconstruction (marginal.hip) accumulates support in `node` / `leaf`; the branch trials (trials.hip) store V in `branch`.
+// U, Ucnt, work and wcnt are indexed by (tile or pattern within the chunk, size of the chunk): a chunk that is the whole shard gives
+// the [I][ntiles][TILE] / [I][S_pad] shapes of the partials.  gfx950 only.
 #pragma once
 #include "devutil.h"
+#include "partition.h"
 
 namespace hyhip {
 namespace {
 
 // program entries (int4): a node header (0, internal index, children, 1 for the root), then one entry per child
 // (1, child node code = matrix slot, child internal index or -1 for a leaf, position among the children)
-struct MargArgs {
+struct WalkArgs {  // what the walks read; "tile" below: 16 patterns (4 states: ONE pattern)
   const int4 *prog;
   int n_prog;
-  int NW, L, S, S_pad, ntiles, maxk, which, first, D;
-  double w;                  // weight of this class (1 when C == 1)
+  int L, S_pad, ntiles, maxk;
+  int first, count, chunk;   // first tile of the launch, its tiles, tiles the blocks U .. wcnt are shaped for
   const double *Pfrag;       // [B][NW][NKK*64] A-operand images of this class
   const double *PTg;         // [B][DP][NW][4][4] column-gather images (leaf edges)
-  const double *PT;          // [B][NW][NKK*64] A-operand images of the TRANSPOSED matrices (marginal scratch)
+  const double *PT;          // [B][NW][NKK*64] A-operand images of the TRANSPOSED matrices (scratch of the pass)
+  const double *Prow;        // 4 states: [B][16] row-major
   const int16_t *codes_tile; // [ntiles][L][16]
+  const int16_t *codes;      // 4 states: [L][S_pad]
   const double *ambig;       // [n_ambig][DP]
   const double *pi;          // [DP]
-  const double *partials;    // this class: [I][ntiles][TILE]
+  const double *partials;    // this class: [I][ntiles][TILE]       (4 states: [I][4][S_pad])
   const int32_t *counts;     // this class: [I][S_pad]
-  double *U;                 // [I][ntiles][TILE] outside vectors
-  int32_t *Ucnt;             // [I][S_pad]
-  double *work;              // [ntiles][2 maxk][TILE]
-  int32_t *wcnt;             // [ntiles][2 maxk][16]
-  double *acc;               // [rows][S][D]
-  double *den;               // [rows][S_pad]
-  int32_t *aexp;             // [rows][S_pad]
+  double *U;                 // [I][chunk][TILE] outside vectors     (4 states: [I][4][chunk])
+  int32_t *Ucnt;             // [I][chunk][16]                       (4 states: [I][chunk])
+  double *work;              // [chunk][2 maxk][TILE]                (4 states: [2 maxk][4][chunk])
+  int32_t *wcnt;             // [chunk][2 maxk][16]                  (4 states: [2 maxk][chunk])
 };
+
+// the block for class c of shard s with the whole shard as the chunk; the caller adds prog, pi and the scratch (PT, U, Ucnt, work, wcnt)
+inline WalkArgs walk_args(const hyphy_hip_partition *p, const Shard &s, int c) {
+  const size_t img = (size_t)c * p->B * p->DP * p->DP;
+  WalkArgs a = {};
+  a.n_prog = (int)p->marg_prog.size();
+  a.L = (int)p->L, a.S_pad = s.S_pad, a.ntiles = s.ntiles, a.maxk = p->marg_maxk;
+  a.count = a.chunk = p->nuc ? s.S_pad : s.ntiles;
+  if (p->nuc) a.Prow = s.Prow + (size_t)c * p->B * 16;
+  else a.Pfrag = s.Pfrag + img, a.PTg = s.PTg + img;
+  a.codes_tile = s.codes_tile, a.codes = s.codes, a.ambig = s.ambig;
+  a.partials = s.partials + (size_t)c * s.partial_stride;
+  a.counts = s.counts + (size_t)c * p->I * s.S_pad;
+  return a;
+}
 
 // transposed A-operand images M[r][c] = P[c][r] of every branch of one class: leaves from the column-gather image (the only
 // image the exponential writes for a leaf without ambiguity codes), internal nodes from the A-operand image
 __global__ __launch_bounds__(256) void marg_transpose_kernel(const double *__restrict__ Pfrag, const double *__restrict__ PTg,
                                                              double *__restrict__ PT, int NW, int L) {
-  const int NKK = 4 * NW, DP = 16 * NW, TILE = NKK * 64;
+  const int DP = 16 * NW, TILE = DP * 16;
   const int b = blockIdx.x;
   const double *src = Pfrag + (size_t)b * DP * DP, *gsrc = PTg + (size_t)b * DP * DP;
   double *dst = PT + (size_t)b * DP * DP;
   for (int idx = threadIdx.x; idx < DP * DP; idx += blockDim.x) {
-    const int w = idx / TILE, rem = idx - w * TILE;
-    const int k2 = rem >> 7, l = (rem >> 1) & 63, kk = 2 * k2 + (rem & 1);
-    const int r = 16 * w + (l & 15), c = 4 * kk + (l >> 4);  // M[r][c] = P[c][r]
+    int r, c;  // M[r][c] = P[c][r]
+    frag_image_rc(idx, NW, r, c);
     dst[idx] = b < L ? gsrc[(r * NW + (c >> 4)) * 16 + (c & 3) * 4 + ((c >> 2) & 3)]
                      : src[(c >> 4) * TILE + frag_index(r >> 2, (r & 3) * 16 + (c & 15))];
   }
@@ -101,7 +125,7 @@ __device__ __forceinline__ void mfma_product(const double *A, const double (&b)[
 
 // leaf vector of leaf code c at this lane's states (state indicator or ambiguity row)
 template <int NKK>
-__device__ __forceinline__ void leaf_vec(const MargArgs &a, int c, int g, double (&lv)[NKK]) {
+__device__ __forceinline__ void leaf_vec(const WalkArgs &a, int c, int g, double (&lv)[NKK]) {
   const int DP = 4 * NKK;
 #pragma unroll
   for (int kk = 0; kk < NKK; kk++) lv[kk] = c >= 0 ? (4 * kk + g == c ? 1. : 0.) : a.ambig[(size_t)(-c - 1) * DP + 4 * kk + g];
@@ -109,7 +133,7 @@ __device__ __forceinline__ void leaf_vec(const MargArgs &a, int c, int g, double
 
 // edge product E of child entry ce and its 2^64 exponent
 template <int NW>
-__device__ __forceinline__ void edge_product(const MargArgs &a, const int4 &ce, int tile, int lane, double (&E)[4 * NW], int &ecnt) {
+__device__ __forceinline__ void edge_product(const WalkArgs &a, const int4 &ce, int tile, int lane, double (&E)[4 * NW], int &ecnt) {
   constexpr int NKK = 4 * NW, DP = 16 * NW, TILE = NKK * 64;
   const int g = lane >> 4, sl = lane & 15;
   const double *Pf = a.Pfrag + (size_t)ce.y * DP * DP;
@@ -122,14 +146,8 @@ __device__ __forceinline__ void edge_product(const MargArgs &a, const int4 &ce, 
   }
   ecnt = 0;
   const int c = (int)a.codes_tile[((size_t)tile * a.L + ce.y) * 16 + sl];
-  if (!__any(c < 0)) {  // column gather, [code][w][g][r] = P[16w + 4r + g][code]
-    const double *Pg = a.PTg + (size_t)ce.y * DP * DP;
-#pragma unroll
-    for (int w = 0; w < NW; w++) {
-      const unsigned off = (unsigned)((c * NW + w) * 16 + g * 4) * 8u;
-      const f64x2 v0 = ld16(Pg, off), v1 = ld16(Pg, off + 16u);
-      E[4 * w] = v0[0], E[4 * w + 1] = v0[1], E[4 * w + 2] = v1[0], E[4 * w + 3] = v1[1];
-    }
+  if (!__any(c < 0)) {
+    gather_column<NW>(a.PTg + (size_t)ce.y * DP * DP, c, g, E);
   } else {  // ambiguity codes in this tile: product with the resolution vectors
     double lv[NKK];
     leaf_vec<NKK>(a, c, g, lv);
@@ -137,24 +155,81 @@ __device__ __forceinline__ void edge_product(const MargArgs &a, const int4 &ce, 
   }
 }
 
-struct MargNucArgs {
-  const int4 *prog;
-  int n_prog, L, S, S_pad, maxk, which, first;
-  double w;
-  const double *P;           // this class: [B][16] row-major
-  const int16_t *codes;      // [L][S_pad]
-  const double *ambig;       // [n_ambig][4]
-  const double *pi;          // [4]
-  const double *partials;    // this class: [I][4][S_pad]
-  const int32_t *counts;     // this class: [I][S_pad]
-  double *U;                 // [I][4][S_pad]
-  int32_t *Ucnt;             // [I][S_pad]
-  double *work;              // [2 maxk][4][S_pad]
-  int32_t *wcnt;             // [2 maxk][S_pad]
-  double *acc;               // [rows][S][4]
-  double *den;               // [rows][S_pad]
-  int32_t *aexp;             // [rows][S_pad]
-};
+// the walk of one tile
+template <int NW, typename Sink>
+__device__ __forceinline__ void outside_walk(const WalkArgs &a, Sink &sink) {
+  constexpr int NKK = 4 * NW, TILE = NKK * 64;
+  const int lane = threadIdx.x, sl = lane & 15;
+  const int lt = blockIdx.x, tile = a.first + lt;
+  double *work = a.work + (size_t)lt * 2 * a.maxk * TILE;
+  int32_t *wcnt = a.wcnt + (size_t)lt * 2 * a.maxk * 16;
+  for (int pc = 0; pc < a.n_prog;) {
+    const int4 h = a.prog[pc];
+    const int node = h.y, k = h.z;
+    double pre[NKK];
+    int pcnt = 0;
+    if (h.w) {  // the root: U = pi
+#pragma unroll
+      for (int kk = 0; kk < NKK; kk++) pre[kk] = a.pi[4 * kk + (lane >> 4)];
+    } else {
+      ld_vec<NKK>(a.U + ((size_t)node * a.chunk + lt) * TILE, lane, pre);
+      pcnt = a.Ucnt[((size_t)node * a.chunk + lt) * 16 + sl];
+    }
+    // prefix pass: slot 2i = U_p * prod_{j < i} E_j, slot 2i + 1 = E_i
+    for (int i = 0; i < k; i++) {
+      const int4 ce = a.prog[pc + 1 + i];
+      double E[NKK];
+      int ecnt;
+      edge_product<NW>(a, ce, tile, lane, E, ecnt);
+      st_vec<NKK>(work + (size_t)(2 * i) * TILE, lane, pre);
+      st_vec<NKK>(work + (size_t)(2 * i + 1) * TILE, lane, E);
+      wcnt[(2 * i) * 16 + sl] = pcnt;  // (every lane of the pattern stores the same word: each reads back its own store)
+      wcnt[(2 * i + 1) * 16 + sl] = ecnt;
+#pragma unroll
+      for (int kk = 0; kk < NKK; kk++) pre[kk] *= E[kk];
+      pcnt += ecnt;
+      rescale_vec<NKK>(pre, pcnt);
+    }
+    sink.node(a, node, tile, lane, pre, pcnt);
+    // suffix pass, children in reverse order
+    double suf[NKK];
+#pragma unroll
+    for (int kk = 0; kk < NKK; kk++) suf[kk] = 1.;
+    int scnt = 0;
+    for (int i = k - 1; i >= 0; i--) {
+      const int4 ce = a.prog[pc + 1 + i];
+      if (ce.z >= 0 || sink.leaves()) {
+        double V[NKK];
+        ld_vec<NKK>(work + (size_t)(2 * i) * TILE, lane, V);
+#pragma unroll
+        for (int kk = 0; kk < NKK; kk++) V[kk] *= suf[kk];
+        int vcnt = wcnt[(2 * i) * 16 + sl] + scnt;
+        rescale_vec<NKK>(V, vcnt);
+        sink.branch(a, ce.y, lt, lane, V, vcnt);
+        if (ce.z >= 0 || Sink::kLeafProduct) {
+          double U[NKK];
+          mfma_product<NW>(a.PT + (size_t)ce.y * 16 * NW * 16 * NW, V, lane, U);
+          if (ce.z >= 0) {
+            rescale_vec<NKK>(U, vcnt);
+            st_vec<NKK>(a.U + ((size_t)ce.z * a.chunk + lt) * TILE, lane, U);
+            a.Ucnt[((size_t)ce.z * a.chunk + lt) * 16 + sl] = vcnt;
+          } else {
+            sink.leaf(a, ce.y, tile, lane, U, vcnt);
+          }
+        }
+      }
+      if (i > 0) {
+        double E[NKK];
+        ld_vec<NKK>(work + (size_t)(2 * i + 1) * TILE, lane, E);
+#pragma unroll
+        for (int kk = 0; kk < NKK; kk++) suf[kk] *= E[kk];
+        scnt += wcnt[(2 * i + 1) * 16 + sl];
+        rescale_vec<NKK>(suf, scnt);
+      }
+    }
+    pc += 1 + k;
+  }
+}
 
 __device__ __forceinline__ void rescale4(double (&v)[4], int &cnt) {
   const double tot = (v[0] + v[1]) + (v[2] + v[3]);
@@ -165,8 +240,81 @@ __device__ __forceinline__ void rescale4(double (&v)[4], int &cnt) {
   }
 }
 
-__device__ __forceinline__ void nuc_leaf_vec(const MargNucArgs &a, int c, double (&lv)[4]) {
+__device__ __forceinline__ void nuc_leaf_vec(const WalkArgs &a, int c, double (&lv)[4]) {
   for (int j = 0; j < 4; j++) lv[j] = c >= 0 ? (j == c ? 1. : 0.) : a.ambig[(size_t)(-c - 1) * 4 + j];
+}
+
+// 4 states: the walk of one pattern (launch: 256 threads per workgroup, any grid that covers a.count)
+template <typename Sink>
+__device__ __forceinline__ void outside_walk_nuc(const WalkArgs &a, Sink &sink) {
+  const int ls = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ls >= a.count) return;
+  const size_t s = (size_t)a.first + ls, SP = a.S_pad, CS = (size_t)a.chunk;
+  for (int pc = 0; pc < a.n_prog;) {
+    const int4 h = a.prog[pc];
+    const int node = h.y, k = h.z;
+    double pre[4];
+    int pcnt = 0;
+    if (h.w) {
+      for (int j = 0; j < 4; j++) pre[j] = a.pi[j];
+    } else {
+      for (int j = 0; j < 4; j++) pre[j] = a.U[((size_t)node * 4 + j) * CS + ls];
+      pcnt = a.Ucnt[(size_t)node * CS + ls];
+    }
+    for (int i = 0; i < k; i++) {
+      const int4 ce = a.prog[pc + 1 + i];
+      const double *P = a.Prow + (size_t)ce.y * 16;
+      double in[4], E[4];
+      int ecnt = 0;
+      if (ce.z >= 0) {
+        for (int j = 0; j < 4; j++) in[j] = a.partials[((size_t)ce.z * 4 + j) * SP + s];
+        ecnt = a.counts[(size_t)ce.z * SP + s];
+      } else {
+        nuc_leaf_vec(a, (int)a.codes[(size_t)ce.y * SP + s], in);
+      }
+      for (int x = 0; x < 4; x++) E[x] = P[4 * x] * in[0] + P[4 * x + 1] * in[1] + P[4 * x + 2] * in[2] + P[4 * x + 3] * in[3];
+      for (int j = 0; j < 4; j++) {
+        a.work[((size_t)(2 * i) * 4 + j) * CS + ls] = pre[j];
+        a.work[((size_t)(2 * i + 1) * 4 + j) * CS + ls] = E[j];
+        pre[j] *= E[j];
+      }
+      a.wcnt[(size_t)(2 * i) * CS + ls] = pcnt;
+      a.wcnt[(size_t)(2 * i + 1) * CS + ls] = ecnt;
+      pcnt += ecnt;
+      rescale4(pre, pcnt);
+    }
+    sink.node(a, node, s, pre, pcnt);
+    double suf[4] = {1., 1., 1., 1.};
+    int scnt = 0;
+    for (int i = k - 1; i >= 0; i--) {
+      const int4 ce = a.prog[pc + 1 + i];
+      if (ce.z >= 0 || sink.leaves()) {
+        const double *P = a.Prow + (size_t)ce.y * 16;
+        double V[4];
+        for (int j = 0; j < 4; j++) V[j] = a.work[((size_t)(2 * i) * 4 + j) * CS + ls] * suf[j];
+        int vcnt = a.wcnt[(size_t)(2 * i) * CS + ls] + scnt;
+        rescale4(V, vcnt);
+        sink.branch(a, ce.y, (size_t)ls, V, vcnt);
+        if (ce.z >= 0 || Sink::kLeafProduct) {
+          double U[4];
+          for (int y = 0; y < 4; y++) U[y] = P[y] * V[0] + P[4 + y] * V[1] + P[8 + y] * V[2] + P[12 + y] * V[3];
+          if (ce.z >= 0) {
+            rescale4(U, vcnt);
+            for (int j = 0; j < 4; j++) a.U[((size_t)ce.z * 4 + j) * CS + ls] = U[j];
+            a.Ucnt[(size_t)ce.z * CS + ls] = vcnt;
+          } else {
+            sink.leaf(a, ce.y, s, U, vcnt);
+          }
+        }
+      }
+      if (i > 0) {
+        for (int j = 0; j < 4; j++) suf[j] *= a.work[((size_t)(2 * i + 1) * 4 + j) * CS + ls];
+        scnt += a.wcnt[(size_t)(2 * i + 1) * CS + ls];
+        rescale4(suf, scnt);
+      }
+    }
+    pc += 1 + k;
+  }
 }
 
 }  // namespace

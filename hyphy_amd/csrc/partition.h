@@ -390,6 +390,58 @@ inline size_t ops_capacity(const hyphy_hip_partition *p) { return (size_t)(p->L 
 inline int64_t caller_pattern(const hyphy_hip_partition *p, int64_t j) { return p->perm.empty() ? j : p->perm[j]; }
 inline int twin_slot0(const hyphy_hip_partition *p) { return (int)(p->B + (p->I + 2)); }
 
+// ---- shared by the passes over the resident conditionals (marginal.hip, trials.hip, joint.hip, sample.hip) ----------------
+// device blocks of one call: from the pool, back to it (behind a synchronisation) when the call returns, on every path
+struct Blocks {
+  std::vector<void *> held;
+  ~Blocks() { release(); }
+  void release() {
+    for (void *b : held) pool_free_sync(b);
+    held.clear();
+  }
+  template <typename T>
+  hipError_t get(T **out, size_t n) {
+    void *b = nullptr;
+    const hipError_t e = pool_malloc(&b, std::max<size_t>(1, n) * sizeof(T));
+    if (e == hipSuccess) held.push_back(b);
+    *out = (T *)b;
+    return e;
+  }
+};
+
+// what they refuse (`pre`: the entry point's name and ": "; `used`: the classes the call reads, nullptr: all)
+inline int check_unpinned(const hyphy_hip_partition *p, const std::string &pre) {
+  return p->pin_node >= 0 ? fail(pre + "a node's states are pinned (clear the pin first)") : 0;
+}
+inline int check_evaluated(const hyphy_hip_partition *p, const std::string &pre, const std::vector<char> *used = nullptr) {
+  for (int64_t c = 0; c < p->C; c++)
+    if ((!used || (*used)[(size_t)c]) && (!p->initialized[(size_t)c] || p->cached_pi.size() != (size_t)p->D))
+      return fail(pre + "rate class " + std::to_string(c) + " has not been evaluated");
+  return 0;
+}
+
+// the root frequencies of the last evaluation, zero-padded to the device's state count
+inline std::vector<double> padded_pi(const hyphy_hip_partition *p) {
+  std::vector<double> pi((size_t)(p->nuc ? 4 : p->DP), 0.);
+  std::copy(p->cached_pi.begin(), p->cached_pi.begin() + p->D, pi.begin());
+  return pi;
+}
+
+// a scratch budget in bytes from an environment variable in MB (read per call; default 1024, also for anything not positive)
+inline double scratch_budget(const char *env) {
+  const char *mb = getenv(env);
+  return (mb && atof(mb) > 0. ? atof(mb) : 1024.) * 1048576.;
+}
+
+// rows of a shard's result on the host (pattern k of the shard, or list[k], at src[row * stride + k], k < n) into the caller's pattern
+// order: out[row][caller pattern]
+template <typename T, typename O>
+inline void rows_to_caller(const hyphy_hip_partition *p, const Shard &s, const T *src, size_t stride, int64_t rows, int64_t n, O *out,
+                           const int32_t *list = nullptr) {
+  for (int64_t r = 0; r < rows; r++)
+    for (int64_t k = 0; k < n; k++) out[(size_t)r * p->S + caller_pattern(p, s.s0 + (list ? list[k] : k))] = src[(size_t)r * stride + k];
+}
+
 // "use the shard's own Q buffer" (filled / staged by hyphy_hip_build_q on every shard): compared by address
 extern const double kOwnQBuffer;
 

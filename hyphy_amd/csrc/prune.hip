@@ -2438,13 +2438,7 @@ void launch_transpose_frag(const double *src_image, double *dst_image, const dou
   hipLaunchKernelGGL(transpose_frag_kernel, dim3(1), dim3(256), 0, stream, src_image, dst_image, row_scale, NW);
 }
 void launch_bc_eval(const BcArgs &a, hipStream_t stream) {
-  const dim3 grid(a.ntiles), block(64);
-  switch (a.NW) {
-    case 1: hipLaunchKernelGGL(bc_eval_kernel<1>, grid, block, 0, stream, a); break;
-    case 2: hipLaunchKernelGGL(bc_eval_kernel<2>, grid, block, 0, stream, a); break;
-    case 3: hipLaunchKernelGGL(bc_eval_kernel<3>, grid, block, 0, stream, a); break;
-    default: hipLaunchKernelGGL(bc_eval_kernel<4>, grid, block, 0, stream, a); break;
-  }
+  LAUNCH_NW(bc_eval_kernel, a.NW, dim3(a.ntiles), dim3(64), stream, a);
 }
 int prune_nuc_grid(const NucArgs &a) {
   const int np = nuc2_np(a);

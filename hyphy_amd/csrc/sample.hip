@@ -98,17 +98,18 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
       for (int c = threadIdx.x; c < DP; c += 256) Pl[c] = c < D ? a.pi[c] : 0.;
     } else {
       const double *Pf = a.Pfrag + (size_t)(L + n) * DP * DP;
-      for (int idx = threadIdx.x; idx < DP * DP; idx += 256) {  // (pfrag_at of joint.hip, inverted)
-        const int wb = idx / TILE, rem = idx - wb * TILE;
-        const int l = (rem >> 1) & 63, kk = 2 * (rem >> 7) + (rem & 1);
-        Pl[(16 * wb + (l & 15)) * LD + 4 * kk + (l >> 4)] = Pf[idx];
+      for (int idx = threadIdx.x; idx < DP * DP; idx += 256) {
+        int row, c;
+        frag_image_rc(idx, NW, row, c);
+        Pl[row * LD + c] = Pf[idx];
       }
     }
     {
       const double *cf = a.partials + ((size_t)n * a.ntiles + tile) * TILE;
-      for (int idx = threadIdx.x; idx < TILE; idx += 256) {  // (frag_index, inverted)
-        const int l = (idx >> 1) & 63, kk = 2 * (idx >> 7) + (idx & 1);
-        cv[(l & 15) * LD + 4 * kk + (l >> 4)] = cf[idx];
+      for (int idx = threadIdx.x; idx < TILE; idx += 256) {  // (one row block: row = pattern of the tile)
+        int pat, c;
+        frag_image_rc(idx, NW, pat, c);
+        cv[pat * LD + c] = cf[idx];
       }
     }
     __syncthreads();
@@ -151,22 +152,6 @@ __global__ __launch_bounds__(256) void sample_nuc_kernel(SampleArgs a) {
   }
 }
 
-// pool blocks of one call, returned (behind a synchronisation) when it ends
-struct Blocks {
-  std::vector<void *> held;
-  ~Blocks() {
-    for (void *b : held) pool_free_sync(b);
-  }
-  template <typename T>
-  hipError_t get(T **out, size_t n) {
-    void *b = nullptr;
-    const hipError_t e = pool_malloc(&b, std::max<size_t>(1, n) * sizeof(T));
-    if (e == hipSuccess) held.push_back(b);
-    *out = (T *)b;
-    return e;
-  }
-};
-
 struct Entry {
   int32_t cls, pat, site;  // rate class, pattern of the shard, site
 };
@@ -193,7 +178,7 @@ int hyphy_hip_sample_ancestral(hyphy_hip_partition *p, int64_t n_rep, int64_t n_
                                const int64_t *class_of_pattern, uint64_t seed, const double *uniforms, int8_t *states_out) {
   if (!p) return fail("sample_ancestral: partition == NULL");
   if (!states_out) return fail("sample_ancestral: states_out == NULL");
-  if (p->pin_node >= 0) return fail("sample_ancestral: a node's states are pinned (clear the pin first)");
+  if (check_unpinned(p, "sample_ancestral: ")) return -1;
   if (n_rep < 0 || n_sites < 0) return fail("sample_ancestral: negative count");
   if (n_rep > INT32_MAX || n_sites > INT32_MAX) return fail("sample_ancestral: count above 2^31 - 1");
   if (n_rep == 0 || n_sites == 0) return 0;
@@ -210,9 +195,7 @@ int hyphy_hip_sample_ancestral(hyphy_hip_partition *p, int64_t n_rep, int64_t n_
       return fail("sample_ancestral: pattern " + std::to_string(s) + ": rate class " + std::to_string(c) + " out of range");
     used[(size_t)c] = 1;
   }
-  for (int c = 0; c < C; c++)
-    if (used[(size_t)c] && (!p->initialized[(size_t)c] || p->cached_pi.size() != (size_t)D))
-      return fail("sample_ancestral: rate class " + std::to_string(c) + " has not been evaluated");
+  if (check_evaluated(p, "sample_ancestral: ", &used)) return -1;
   if (uniforms) {
     const size_t total = (size_t)n_rep * I * n_sites;
     for (size_t k = 0; k < total; k++)
@@ -226,10 +209,8 @@ int hyphy_hip_sample_ancestral(hyphy_hip_partition *p, int64_t n_rep, int64_t n_
   const bool nuc = p->nuc;
   std::vector<int32_t> parent((size_t)(L + I), -1);
   for (int64_t c = 0; c < L + I - 1; c++) parent[(size_t)c] = (int32_t)p->parents[(size_t)c];
-  std::vector<double> pi_pad((size_t)(nuc ? 4 : DP), 0.);
-  for (int64_t j = 0; j < D; j++) pi_pad[(size_t)j] = p->cached_pi[(size_t)j];
-  const char *mb_env = getenv("HYPHY_HIP_SAMPLE_MB");  // (read per call)
-  const double budget = (mb_env && atof(mb_env) > 0. ? atof(mb_env) : 1024.) * 1048576.;
+  const std::vector<double> pi_pad = padded_pi(p);
+  const double budget = scratch_budget("HYPHY_HIP_SAMPLE_MB");
   const double draw_bytes = (double)I * (uniforms ? 9. : 1.);  // scratch of one entry and replicate: a byte (and a uniform) per node
   // device pattern (over all shards) of every caller pattern
   std::vector<int64_t> dev_of((size_t)S);
@@ -336,13 +317,7 @@ int hyphy_hip_sample_ancestral(hyphy_hip_partition *p, int64_t n_rep, int64_t n_
                 work.push_back(make_int4(tiles[t].x, (int)((size_t)tiles[t].y - e0), tiles[t].z, (int)d));
             if (work.size() > max_work) return fail("sample_ancestral: internal: work list larger than planned");
             HIPCHK(hipMemcpyAsync(d_work, work.data(), work.size() * sizeof(int4), hipMemcpyHostToDevice, s.stream));
-            const dim3 grid((unsigned)work.size()), block(256);
-            switch (NW) {
-              case 1: hipLaunchKernelGGL(sample_kernel<1>, grid, block, 0, s.stream, a); break;
-              case 2: hipLaunchKernelGGL(sample_kernel<2>, grid, block, 0, s.stream, a); break;
-              case 3: hipLaunchKernelGGL(sample_kernel<3>, grid, block, 0, s.stream, a); break;
-              default: hipLaunchKernelGGL(sample_kernel<4>, grid, block, 0, s.stream, a); break;
-            }
+            LAUNCH_NW(sample_kernel, NW, dim3((unsigned)work.size()), dim3(256), s.stream, a);
           }
           HIPCHK(hipGetLastError());
           // -> [replicate][node][site], the caller's site order

@@ -1,14 +1,14 @@
 // Every branch's trial likelihoods from one outside pass — the device counterpart of the finite-difference gradient of
 // _LikelihoodFunction::ComputeGradient (likefunc.cpp:7025-7109), which re-evaluates the partition once per independent parameter.
 // A parameter local to one branch changes that branch's transition matrix only, and with the branch's outside vector in hand
-//   V_c = U_p * prod_{s in children(p), s != c} E_s        (U_root = pi, U_c = P_c^T V_c: the walk of marginal.hip)
+//   V_c = U_p * prod_{s in children(p), s != c} E_s        (U_root = pi, U_c = P_c^T V_c: the walk of outside.h)
 // the likelihood under ANY replacement M of the matrix of branch c is one contraction per pattern,
 //   L_s(P_c -> M) = sum_i V_c[i] (M in_c)[i],    2^64 exponent = exponent(V_c) + exponent(in_c),
 // in_c the stored conditional of an internal child, the state indicator / ambiguity vector of a leaf.
 //
-// Phase 1 (outside_store_kernel<NW>, outside_store_nuc_kernel): the pre-order walk of marginal_mfma_kernel over the same program
-// (plan_marginal_program), one wave per 16-pattern tile, with the same prefix / suffix sibling products, rescaling and transposed
-// images (outside.h).  It keeps V_c and its exponent of EVERY child, leaves included, and accumulates no support.
+// Phase 1 (outside_store_kernel<NW>, outside_store_nuc_kernel): outside.h's walk — the one the marginal reconstruction runs, over
+// the same program (plan_marginal_program), one wave per 16-pattern tile — with the OutsideStore sink: it keeps V_c and its exponent
+// of EVERY child, leaves included, forms no U for a leaf and accumulates no support.
 // Phase 2 (branch_trials_kernel<NW>, branch_trials_nuc_kernel): one wave per (branch with at least one trial, tile), the tile the
 // fastest grid index — the workgroups that run together read the same trial images.  V_c and in_c are loaded once; every trial of
 // the branch is one [D x D] x [D x 16] product on the FP64 MFMA and a weighted row sum.  Classes run one launch after another and
@@ -31,148 +31,38 @@ using namespace hyhip;
 namespace hyhip {
 namespace {
 
-struct OutsideStore {  // where phase 1 keeps what it computes: blocks of one chunk of tiles, indexed by the tile within the chunk
-  int tile0, ct;       // first tile of the chunk, tiles of the scratch blocks
-  double *V;           // [B][ct][TILE]
-  int32_t *Vcnt;       // [B][ct][16]
+// phase 1's sink: V_c and its exponent of every child, leaves included, into blocks of one chunk of tiles (a.chunk of them), indexed
+// by the tile within the chunk.  A leaf's U is not formed.
+struct OutsideStore {
+  static constexpr bool kLeafProduct = false;
+  double *V;      // [B][ct][TILE]   (4 states: [B][4][ct * 64])
+  int32_t *Vcnt;  // [B][ct][16]     (4 states: [B][ct * 64])
+
+  __device__ __forceinline__ bool leaves() const { return true; }
+  template <int NKK>
+  __device__ __forceinline__ void node(const WalkArgs &, int, int, int, const double (&)[NKK], int) const {}
+  template <int NKK>
+  __device__ __forceinline__ void branch(const WalkArgs &a, int c, int lt, int lane, const double (&v)[NKK], int vcnt) const {
+    st_vec<NKK>(V + ((size_t)c * a.chunk + lt) * (NKK * 64), lane, v);
+    Vcnt[((size_t)c * a.chunk + lt) * 16 + (lane & 15)] = vcnt;
+  }
+  template <int NKK>
+  __device__ __forceinline__ void leaf(const WalkArgs &, int, int, int, const double (&)[NKK], int) const {}
+  // 4 states
+  __device__ __forceinline__ void node(const WalkArgs &, int, size_t, const double (&)[4], int) const {}
+  __device__ __forceinline__ void branch(const WalkArgs &a, int c, size_t ls, const double (&v)[4], int vcnt) const {
+    for (int j = 0; j < 4; j++) V[((size_t)c * 4 + j) * a.chunk + ls] = v[j];
+    Vcnt[(size_t)c * a.chunk + ls] = vcnt;
+  }
+  __device__ __forceinline__ void leaf(const WalkArgs &, int, size_t, const double (&)[4], int) const {}
 };
 
-// marginal_mfma_kernel's walk (a.U, a.Ucnt, a.work, a.wcnt: chunk-sized blocks), keeping the outside vector of every branch
 template <int NW>
-__global__ __launch_bounds__(64) void outside_store_kernel(MargArgs a, OutsideStore o) {
-  constexpr int NKK = 4 * NW, TILE = NKK * 64;
-  const int lane = threadIdx.x, g = lane >> 4, sl = lane & 15;
-  const int lt = blockIdx.x, tile = o.tile0 + lt;
-  double *work = a.work + (size_t)lt * 2 * a.maxk * TILE;
-  int32_t *wcnt = a.wcnt + (size_t)lt * 2 * a.maxk * 16;
-  for (int pc = 0; pc < a.n_prog;) {
-    const int4 h = a.prog[pc];
-    const int node = h.y, k = h.z;
-    double pre[NKK];
-    int pcnt = 0;
-    if (h.w) {  // the root: U = pi
-#pragma unroll
-      for (int kk = 0; kk < NKK; kk++) pre[kk] = a.pi[4 * kk + g];
-    } else {
-      ld_vec<NKK>(a.U + ((size_t)node * o.ct + lt) * TILE, lane, pre);
-      pcnt = a.Ucnt[((size_t)node * o.ct + lt) * 16 + sl];
-    }
-    // prefix pass: slot 2i = U_p * prod_{j < i} E_j, slot 2i + 1 = E_i
-    for (int i = 0; i < k; i++) {
-      const int4 ce = a.prog[pc + 1 + i];
-      double E[NKK];
-      int ecnt;
-      edge_product<NW>(a, ce, tile, lane, E, ecnt);
-      st_vec<NKK>(work + (size_t)(2 * i) * TILE, lane, pre);
-      st_vec<NKK>(work + (size_t)(2 * i + 1) * TILE, lane, E);
-      wcnt[(2 * i) * 16 + sl] = pcnt;  // (every lane of the pattern stores the same word: each reads back its own store)
-      wcnt[(2 * i + 1) * 16 + sl] = ecnt;
-#pragma unroll
-      for (int kk = 0; kk < NKK; kk++) pre[kk] *= E[kk];
-      pcnt += ecnt;
-      rescale_vec<NKK>(pre, pcnt);
-    }
-    // suffix pass, children in reverse order
-    double suf[NKK];
-#pragma unroll
-    for (int kk = 0; kk < NKK; kk++) suf[kk] = 1.;
-    int scnt = 0;
-    for (int i = k - 1; i >= 0; i--) {
-      const int4 ce = a.prog[pc + 1 + i];
-      double V[NKK];
-      ld_vec<NKK>(work + (size_t)(2 * i) * TILE, lane, V);
-#pragma unroll
-      for (int kk = 0; kk < NKK; kk++) V[kk] *= suf[kk];
-      int vcnt = wcnt[(2 * i) * 16 + sl] + scnt;
-      rescale_vec<NKK>(V, vcnt);
-      st_vec<NKK>(o.V + ((size_t)ce.y * o.ct + lt) * TILE, lane, V);
-      o.Vcnt[((size_t)ce.y * o.ct + lt) * 16 + sl] = vcnt;
-      if (ce.z >= 0) {
-        double U[NKK];
-        mfma_product<NW>(a.PT + (size_t)ce.y * 16 * NW * 16 * NW, V, lane, U);
-        rescale_vec<NKK>(U, vcnt);
-        st_vec<NKK>(a.U + ((size_t)ce.z * o.ct + lt) * TILE, lane, U);
-        a.Ucnt[((size_t)ce.z * o.ct + lt) * 16 + sl] = vcnt;
-      }
-      if (i > 0) {
-        double E[NKK];
-        ld_vec<NKK>(work + (size_t)(2 * i + 1) * TILE, lane, E);
-#pragma unroll
-        for (int kk = 0; kk < NKK; kk++) suf[kk] *= E[kk];
-        scnt += wcnt[(2 * i + 1) * 16 + sl];
-        rescale_vec<NKK>(suf, scnt);
-      }
-    }
-    pc += 1 + k;
-  }
+__global__ __launch_bounds__(64) void outside_store_kernel(WalkArgs a, OutsideStore o) {
+  outside_walk<NW>(a, o);
 }
 
-// 4 states: marginal_nuc_kernel's walk over patterns [s0, s0 + n) (a.U, a.Ucnt, a.work, a.wcnt, V, Vcnt: planes of `cs` patterns)
-__global__ __launch_bounds__(256) void outside_store_nuc_kernel(MargNucArgs a, int s0, int n, int cs, double *__restrict__ Vout,
-                                                                int32_t *__restrict__ Vcnt) {
-  const int ls = blockIdx.x * blockDim.x + threadIdx.x;
-  if (ls >= n) return;
-  const size_t s = (size_t)s0 + ls, SP = a.S_pad, CS = (size_t)cs;
-  for (int pc = 0; pc < a.n_prog;) {
-    const int4 h = a.prog[pc];
-    const int node = h.y, k = h.z;
-    double pre[4];
-    int pcnt = 0;
-    if (h.w) {
-      for (int j = 0; j < 4; j++) pre[j] = a.pi[j];
-    } else {
-      for (int j = 0; j < 4; j++) pre[j] = a.U[((size_t)node * 4 + j) * CS + ls];
-      pcnt = a.Ucnt[(size_t)node * CS + ls];
-    }
-    for (int i = 0; i < k; i++) {
-      const int4 ce = a.prog[pc + 1 + i];
-      const double *P = a.P + (size_t)ce.y * 16;
-      double in[4], E[4];
-      int ecnt = 0;
-      if (ce.z >= 0) {
-        for (int j = 0; j < 4; j++) in[j] = a.partials[((size_t)ce.z * 4 + j) * SP + s];
-        ecnt = a.counts[(size_t)ce.z * SP + s];
-      } else {
-        nuc_leaf_vec(a, (int)a.codes[(size_t)ce.y * SP + s], in);
-      }
-      for (int x = 0; x < 4; x++) E[x] = P[4 * x] * in[0] + P[4 * x + 1] * in[1] + P[4 * x + 2] * in[2] + P[4 * x + 3] * in[3];
-      for (int j = 0; j < 4; j++) {
-        a.work[((size_t)(2 * i) * 4 + j) * CS + ls] = pre[j];
-        a.work[((size_t)(2 * i + 1) * 4 + j) * CS + ls] = E[j];
-        pre[j] *= E[j];
-      }
-      a.wcnt[(size_t)(2 * i) * CS + ls] = pcnt;
-      a.wcnt[(size_t)(2 * i + 1) * CS + ls] = ecnt;
-      pcnt += ecnt;
-      rescale4(pre, pcnt);
-    }
-    double suf[4] = {1., 1., 1., 1.};
-    int scnt = 0;
-    for (int i = k - 1; i >= 0; i--) {
-      const int4 ce = a.prog[pc + 1 + i];
-      const double *P = a.P + (size_t)ce.y * 16;
-      double V[4];
-      for (int j = 0; j < 4; j++) V[j] = a.work[((size_t)(2 * i) * 4 + j) * CS + ls] * suf[j];
-      int vcnt = a.wcnt[(size_t)(2 * i) * CS + ls] + scnt;
-      rescale4(V, vcnt);
-      for (int j = 0; j < 4; j++) Vout[((size_t)ce.y * 4 + j) * CS + ls] = V[j];
-      Vcnt[(size_t)ce.y * CS + ls] = vcnt;
-      if (ce.z >= 0) {
-        double U[4];
-        for (int y = 0; y < 4; y++) U[y] = P[y] * V[0] + P[4 + y] * V[1] + P[8 + y] * V[2] + P[12 + y] * V[3];
-        rescale4(U, vcnt);
-        for (int j = 0; j < 4; j++) a.U[((size_t)ce.z * 4 + j) * CS + ls] = U[j];
-        a.Ucnt[(size_t)ce.z * CS + ls] = vcnt;
-      }
-      if (i > 0) {
-        for (int j = 0; j < 4; j++) suf[j] *= a.work[((size_t)(2 * i + 1) * 4 + j) * CS + ls];
-        scnt += a.wcnt[(size_t)(2 * i + 1) * CS + ls];
-        rescale4(suf, scnt);
-      }
-    }
-    pc += 1 + k;
-  }
-}
+__global__ __launch_bounds__(256) void outside_store_nuc_kernel(WalkArgs a, OutsideStore o) { outside_walk_nuc(a, o); }
 
 struct TrialArgs {
   int NW, L, S_pad, ntiles, tile0, ct;  // (4 states: tiles of 64 patterns, ntiles unused)
@@ -196,7 +86,7 @@ struct TrialArgs {
 };
 
 // this class's value (l, exponent e) of pattern q into the mix of the classes before it, aligned on the smaller exponent (the larger
-// scale), as accumulate() of marginal.hip aligns its numerators
+// scale), as MargSink::add of marginal.hip aligns its numerators
 __device__ __forceinline__ void mix_in(const TrialArgs &a, size_t q, double &l, int &e) {
   l *= a.w;
   if (a.first) return;
@@ -345,41 +235,21 @@ __global__ __launch_bounds__(64) void trials_reduce_kernel(double *part_sum, lon
   }
 }
 
-// device blocks of one call: from the pool, back to it when the call returns (on every path)
-struct Blocks {
-  std::vector<void *> held;
-  ~Blocks() { release(); }
-  void release() {
-    for (void *b : held) pool_free_sync(b);
-    held.clear();
-  }
-  template <typename T>
-  hipError_t get(T **out, size_t n) {
-    void *b = nullptr;
-    const hipError_t e = pool_malloc(&b, std::max<size_t>(1, n) * sizeof(T));
-    if (e == hipSuccess) held.push_back(b);
-    *out = (T *)b;
-    return e;
-  }
-};
-
 int trials_common(const char *what, hyphy_hip_partition *p, int64_t n_trials, const int64_t *nodes, const double *q_dense,
                   const double *coeffs, int q_is_probability, const double *weights, double *logl_out, double *site_lik_out,
                   int64_t *site_scaler_out) {
   const std::string pre = std::string(what) + ": ";
   if (!p) return fail(pre + "partition == NULL");
   if (n_trials < 0) return fail(pre + "n_trials < 0");
-  if (p->pin_node >= 0) return fail(pre + "a node's states are pinned (clear the pin first)");
+  if (check_unpinned(p, pre)) return -1;
   const int C = (int)p->C;
   if (C > 1 && !weights) return fail(pre + "class weights are required when C > 1");
-  for (int c = 0; c < C; c++)
-    if (!p->initialized[c] || p->cached_pi.size() != (size_t)p->D)
-      return fail(pre + "rate class " + std::to_string(c) + " has not been evaluated");
+  if (check_evaluated(p, pre)) return -1;
   if (n_trials == 0) return 0;
   if (!nodes || !logl_out || (!q_dense && !coeffs)) return fail(pre + "null argument");
   if (coeffs && !p->K) return fail(pre + "templates not set (hyphy_hip_set_q_templates)");
   if (n_trials * (int64_t)C > 0x3fffffff) return fail(pre + "too many trials");
-  const int64_t D = p->D, L = p->L, I = p->I, B = p->B, S = p->S;
+  const int64_t D = p->D, L = p->L, I = p->I, B = p->B;
   for (int64_t t = 0; t < n_trials; t++)
     if (nodes[t] < 0 || nodes[t] >= B)
       return fail(pre + "trial " + std::to_string(t) + ": node code out of range (the root has no branch)");
@@ -393,8 +263,7 @@ int trials_common(const char *what, hyphy_hip_partition *p, int64_t n_trials, co
   if (p->marg_prog.empty()) p->marg_prog = plan_marginal_program(L, I, p->parents.data(), &p->marg_maxk);
   const std::vector<int4> &prog = p->marg_prog;
   const int maxk = p->marg_maxk;
-  std::vector<double> pi_pad((size_t)(nuc ? 4 : DP), 0.);
-  for (int64_t j = 0; j < D; j++) pi_pad[(size_t)j] = p->cached_pi[(size_t)j];
+  const std::vector<double> pi_pad = padded_pi(p);
   // trials grouped by branch, branches in ascending node code, the trials of a branch in the caller's order
   std::vector<int> order((size_t)n_trials), branch, tr_off;
   for (int64_t t = 0; t < n_trials; t++) order[(size_t)t] = (int)t;
@@ -406,8 +275,7 @@ int trials_common(const char *what, hyphy_hip_partition *p, int64_t n_trials, co
     }
   tr_off.push_back((int)n_trials);
   const int n_branch = (int)branch.size();
-  const char *mb_env = getenv("HYPHY_HIP_TRIALS_MB");  // (read per call)
-  const double budget = (mb_env && atof(mb_env) > 0. ? atof(mb_env) : 1024.) * 1048576.;
+  const double budget = scratch_budget("HYPHY_HIP_TRIALS_MB");
   const size_t MS = nuc ? 16 : (size_t)DP * DP;     // doubles of a trial matrix on the device
   const size_t TILE = nuc ? 256 : (size_t)16 * DP;  // doubles of one tile of one node
   const int TP = nuc ? 64 : 16;                     // its patterns
@@ -493,61 +361,23 @@ int trials_common(const char *what, hyphy_hip_partition *p, int64_t n_trials, co
         ta.ambig = s.ambig, ta.freq = s.freq;
         ta.lik = lik, ta.cnt = cnt;
         ta.part_sum = part_sum, ta.part_cnt = part_cnt, ta.part_flag = part_flag, ta.part_stride = part_stride;
+        WalkArgs a = walk_args(p, s, c);
+        a.prog = d_prog, a.pi = d_pi, a.PT = PT;
+        a.U = U, a.Ucnt = Ucnt, a.work = work, a.wcnt = wcnt;
+        const int unit = nuc ? TP : 1;  // (4 states: the walk counts patterns)
+        a.first = tile0 * unit, a.count = nt * unit, a.chunk = ct * unit;
+        const OutsideStore o = {V, Vcnt};
         if (nuc) {
-          MargNucArgs a;
-          a.prog = d_prog;
-          a.n_prog = (int)prog.size();
-          a.L = (int)L, a.S = (int)s.S, a.S_pad = s.S_pad, a.maxk = maxk, a.which = 0, a.first = 0;
-          a.w = ta.w;
-          a.P = s.Prow + (size_t)c * B * 16;
-          a.codes = s.codes;
-          a.ambig = s.ambig;
-          a.pi = d_pi;
-          a.partials = ta.partials;
-          a.counts = ta.counts;
-          a.U = U, a.Ucnt = Ucnt, a.work = work, a.wcnt = wcnt;
-          a.acc = nullptr, a.den = nullptr, a.aexp = nullptr;
-          hipLaunchKernelGGL(outside_store_nuc_kernel, dim3((unsigned)((nt * 64 + 255) / 256)), dim3(256), 0, s.stream, a, tile0 * 64,
-                             nt * 64, ct * 64, V, Vcnt);
+          hipLaunchKernelGGL(outside_store_nuc_kernel, dim3((unsigned)((a.count + 255) / 256)), dim3(256), 0, s.stream, a, o);
         } else {
-          MargArgs a;
-          a.prog = d_prog;
-          a.n_prog = (int)prog.size();
-          a.NW = NW, a.L = (int)L, a.S = (int)s.S, a.S_pad = s.S_pad, a.ntiles = s.ntiles, a.maxk = maxk, a.which = 0;
-          a.first = 0, a.D = (int)D;
-          a.w = ta.w;
-          a.Pfrag = s.Pfrag + (size_t)c * B * DP * DP;
-          a.PTg = s.PTg + (size_t)c * B * DP * DP;
-          a.PT = PT;
-          a.codes_tile = s.codes_tile;
-          a.ambig = s.ambig;
-          a.pi = d_pi;
-          a.partials = ta.partials;
-          a.counts = ta.counts;
-          a.U = U, a.Ucnt = Ucnt, a.work = work, a.wcnt = wcnt;
-          a.acc = nullptr, a.den = nullptr, a.aexp = nullptr;
-          OutsideStore o;
-          o.tile0 = tile0, o.ct = ct, o.V = V, o.Vcnt = Vcnt;
           if (C > 1 || tile0 == 0)
             hipLaunchKernelGGL(marg_transpose_kernel, dim3((unsigned)B), dim3(256), 0, s.stream, a.Pfrag, a.PTg, PT, NW, (int)L);
-          const dim3 grid((unsigned)nt), block(64);
-          switch (NW) {
-            case 1: hipLaunchKernelGGL(outside_store_kernel<1>, grid, block, 0, s.stream, a, o); break;
-            case 2: hipLaunchKernelGGL(outside_store_kernel<2>, grid, block, 0, s.stream, a, o); break;
-            case 3: hipLaunchKernelGGL(outside_store_kernel<3>, grid, block, 0, s.stream, a, o); break;
-            default: hipLaunchKernelGGL(outside_store_kernel<4>, grid, block, 0, s.stream, a, o); break;
-          }
+          LAUNCH_NW(outside_store_kernel, NW, dim3((unsigned)nt), dim3(64), s.stream, a, o);
         }
         for (ta.b0 = 0; ta.b0 < n_branch; ta.b0 += 65535) {
           const dim3 grid((unsigned)nt, (unsigned)std::min(65535, n_branch - ta.b0)), block(64);
           if (nuc) hipLaunchKernelGGL(branch_trials_nuc_kernel, grid, block, 0, s.stream, ta);
-          else
-            switch (NW) {
-              case 1: hipLaunchKernelGGL(branch_trials_kernel<1>, grid, block, 0, s.stream, ta); break;
-              case 2: hipLaunchKernelGGL(branch_trials_kernel<2>, grid, block, 0, s.stream, ta); break;
-              case 3: hipLaunchKernelGGL(branch_trials_kernel<3>, grid, block, 0, s.stream, ta); break;
-              default: hipLaunchKernelGGL(branch_trials_kernel<4>, grid, block, 0, s.stream, ta); break;
-            }
+          else LAUNCH_NW(branch_trials_kernel, NW, grid, block, s.stream, ta);
         }
         HIPCHK(hipGetLastError());
       }
@@ -567,16 +397,12 @@ int trials_common(const char *what, hyphy_hip_partition *p, int64_t n_trials, co
     if (site_lik_out) {
       h_l.resize((size_t)n_trials * s.S_pad);
       HIPCHK(hipMemcpy(h_l.data(), lik, h_l.size() * sizeof(double), hipMemcpyDeviceToHost));
-      for (int64_t t = 0; t < n_trials; t++)
-        for (int64_t k = 0; k < s.S; k++)
-          site_lik_out[(size_t)t * S + caller_pattern(p, s.s0 + k)] = h_l[(size_t)t * s.S_pad + k];
+      rows_to_caller(p, s, h_l.data(), (size_t)s.S_pad, n_trials, s.S, site_lik_out);
     }
     if (site_scaler_out) {
       h_c.resize((size_t)n_trials * s.S_pad);
       HIPCHK(hipMemcpy(h_c.data(), cnt, h_c.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-      for (int64_t t = 0; t < n_trials; t++)
-        for (int64_t k = 0; k < s.S; k++)
-          site_scaler_out[(size_t)t * S + caller_pattern(p, s.s0 + k)] = h_c[(size_t)t * s.S_pad + k];
+      rows_to_caller(p, s, h_c.data(), (size_t)s.S_pad, n_trials, s.S, site_scaler_out);
     }
   }
   for (int64_t t = 0; t < n_trials; t++) logl_out[t] = combine(parts[(size_t)t]);
