@@ -93,6 +93,8 @@ def load():
     lib.hyphy_hip_expm_batch.argtypes = [C.c_int64, C.c_int64, dp, dp]
     lib.hyphy_hip_set_q_templates.restype = C.c_int
     lib.hyphy_hip_set_q_templates.argtypes = [vp, C.c_int64, dp]
+    lib.hyphy_hip_update_q_templates.restype = C.c_int
+    lib.hyphy_hip_update_q_templates.argtypes = [vp, C.c_int64, dp]
     lib.hyphy_hip_build_q.restype = C.c_int
     lib.hyphy_hip_build_q.argtypes = [vp, C.c_int64, dp]
     lib.hyphy_hip_evaluate_built.restype = C.c_int
@@ -829,6 +831,14 @@ class HipPartition:
     def set_q_templates(self, templates: np.ndarray):
         t = np.ascontiguousarray(templates, dtype=np.float64)
         _check(self._lib.hyphy_hip_set_q_templates(self._h, t.shape[0], _d(t)))
+
+    def update_q_templates(self, templates: np.ndarray):
+        """New VALUES for the templates of ``set_q_templates`` ([K, D, D], C-contiguous float64): copied before the call returns,
+        uploaded in-stream ahead of the next exponential launch; branches not rebuilt afterwards keep their matrices."""
+        t = np.ascontiguousarray(templates, dtype=np.float64)
+        if t.ndim != 3 or t.shape[1:] != (self.D, self.D):
+            raise ValueError(f"expected [K, {self.D}, {self.D}] templates, got {t.shape}")
+        _check(self._lib.hyphy_hip_update_q_templates(self._h, t.shape[0], _d(t)))
 
     def build_q(self, coeffs: np.ndarray):
         c = np.ascontiguousarray(coeffs, dtype=np.float64)
