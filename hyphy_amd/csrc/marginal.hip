@@ -45,24 +45,30 @@ struct MargSink {
 
   __device__ __forceinline__ bool leaves() const { return which == 1; }
 
-  // add w * num (exponent e) to the accumulated support of `row`; den = sum of num * lv over the states
+  // add w * num (exponent e) to the accumulated support of `row`; den = sum of num * lv over the states.  A contribution whose
+  // weighted denominator is exactly 0 (the pattern is impossible under this class, or the class has weight 0) is passed over, and a
+  // stored denominator of 0 is overwritten: such a contribution's exponent says nothing (a zero vector is never rescaled), and under
+  // the min rule it would scale the other classes by 2^(-64 x difference), to nothing from a difference of 17.  Every lane of a
+  // pattern decides alike: dn is a row_sum4, and den[q] is read by all four lanes before lane g == 0 stores it.
   template <int NKK>
   __device__ __forceinline__ void add(const WalkArgs &a, int row, int site, int g, const double (&num)[NKK], double dn, int e) const {
     if (site >= S) return;
     double *out = acc + ((size_t)row * S + site) * D;
     const size_t q = (size_t)row * a.S_pad + site;
-    if (first) {
+    const double wd = w * dn, d_old = first ? 0. : den[q];
+    if (!(wd > 0.) && !first) return;
+    if (!(d_old > 0.)) {
+      const double f = wd > 0. ? w : 0.;
 #pragma unroll
       for (int kk = 0; kk < NKK; kk++)
-        if (4 * kk + g < D) out[4 * kk + g] = w * num[kk];
+        if (4 * kk + g < D) out[4 * kk + g] = f * num[kk];
       if (g == 0) {
-        den[q] = w * dn;
+        den[q] = wd;
         aexp[q] = e;
       }
       return;
     }
     const int e_old = aexp[q];
-    const double d_old = den[q];
     const int e_new = min(e_old, e);  // (true value = stored * 2^(-64 e): the smaller exponent is the larger scale)
     const double f_old = ldexp(1.0, -64 * (e_old - e_new)), f_new = w * ldexp(1.0, -64 * (e - e_new));
 #pragma unroll
@@ -100,16 +106,19 @@ struct MargSink {
     if (s >= (size_t)S) return;
     double *out = acc + ((size_t)row * S + s) * 4;
     const size_t q = (size_t)row * a.S_pad + s;
-    if (first) {
-      for (int j = 0; j < 4; j++) out[j] = w * num[j];
-      den[q] = w * dn;
+    const double wd = w * dn, d_old = first ? 0. : den[q];
+    if (!(wd > 0.) && !first) return;
+    if (!(d_old > 0.)) {
+      const double f = wd > 0. ? w : 0.;
+      for (int j = 0; j < 4; j++) out[j] = f * num[j];
+      den[q] = wd;
       aexp[q] = e;
       return;
     }
     const int e_old = aexp[q], e_new = min(e_old, e);
     const double f_old = ldexp(1.0, -64 * (e_old - e_new)), f_new = w * ldexp(1.0, -64 * (e - e_new));
     for (int j = 0; j < 4; j++) out[j] = out[j] * f_old + num[j] * f_new;
-    den[q] = den[q] * f_old + dn * f_new;
+    den[q] = d_old * f_old + dn * f_new;
     aexp[q] = e_new;
   }
   __device__ __forceinline__ void node(const WalkArgs &a, int n, size_t s, const double (&pre)[4], int pcnt) const {
@@ -130,15 +139,24 @@ __global__ __launch_bounds__(64) void marginal_mfma_kernel(WalkArgs a, MargSink 
 
 __global__ __launch_bounds__(256) void marginal_nuc_kernel(WalkArgs a, MargSink k) { outside_walk_nuc(a, k); }
 
-// support = accumulated numerator / denominator, in place; MAP state (first maximum) and its support
+// support = accumulated numerator / denominator, in place; MAP state (first maximum) and its support.  A denominator of 0 (the
+// pattern is impossible under every class): NaN in all D entries, state -1, support NaN
 __global__ __launch_bounds__(256) void marginal_finish_kernel(double *__restrict__ acc, const double *__restrict__ den, int rows, int S,
                                                               int S_pad, int D, int32_t *__restrict__ map_state,
                                                               double *__restrict__ map_support) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (size_t)rows * S) return;
   const size_t row = t / S, s = t - row * S;
-  const double inv = 1.0 / den[row * S_pad + s];
+  const double d = den[row * S_pad + s];
   double *v = acc + t * D;
+  if (!(d > 0.)) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    for (int j = 0; j < D; j++) v[j] = nan;
+    map_state[t] = -1;
+    map_support[t] = nan;
+    return;
+  }
+  const double inv = 1.0 / d;
   double best = -1.;
   int arg = 0;
   for (int j = 0; j < D; j++) {

@@ -701,7 +701,9 @@ class HipPartition:
         """Marginal ancestral reconstruction in one pass over the resident conditionals (call after an evaluation of every
         class).  ``which``: "internal" (rows = internal nodes) or "leaves" (rows = leaves, unnormalised L_s(leaf = x) / L_s).
         ``weights``: class weights when C > 1.  Returns the support [rows, S, D] (``support``), and with ``map`` also the MAP
-        state [rows, S] and its support [rows, S]: a single array, or a tuple of those asked for."""
+        state [rows, S] and its support [rows, S]: a single array, or a tuple of those asked for.  A class under which a pattern
+        is impossible (or of weight 0) takes no part in that pattern's rows; a pattern impossible under every class has NaN
+        support, MAP state -1 and MAP support NaN."""
         if which not in ("internal", "leaves"):
             raise ValueError("which must be 'internal' or 'leaves'")
         rows = self.I if which == "internal" else self.L

@@ -409,6 +409,10 @@ int hyphy_hip_set_pinned_states(hyphy_hip_partition *p, int64_t node, const int6
  *   map_state_out   [rows][S] or NULL: state of largest support (the first one on ties); map_support_out [rows][S] or NULL.
  * Call after an evaluation of every class; the pass uses the matrices, root frequencies and patterns of the last evaluation
  * of each class (persisted copies are restored first if the last full pass kept them on chip).  Patterns in the caller's order.
+ * A class under which a pattern's likelihood is exactly 0, or whose weight is 0, takes no part in that pattern's rows: the support is
+ * the mix of the other classes by their shares of the pattern's likelihood, whatever 2^64 exponent the zero class carries.  (In a
+ * leaf row this leaves out such a class's L_s(leaf = x) at the states x that the leaf's own data exclude.)  A pattern that is
+ * impossible under every class gets NaN in all D entries of each of its rows, map_state -1 and map_support NaN; the call succeeds.
  * Returns < 0 when a pin is active, a class was never evaluated, or C > 1 without weights.  Leaves no state behind: later
  * evaluations, partial updates and a branch cache built before the call give what they give without it. */
 int hyphy_hip_marginal_ancestral(hyphy_hip_partition *p, int64_t which, const double *weights /* [C] or NULL */,

@@ -15,6 +15,10 @@ test_scalefree_cpu.py::test_oracle_agrees_on_every_generated_case (relative, pat
 GPU_RTOL = 100 x that plus the absolute 1e-9 of tests/test_gpu_parity.py (tests/test_gpu_rescale.py).  With per-pattern values of
 1e2 .. 1e4 in size the relative term is 3e-11 .. 3e-9: for most patterns the absolute 1e-9 is the larger part of the allowance.
 
+``prune(..., posteriors=True)`` adds the marginal posteriors of a pre-order pass over the same normalised vectors: ``post`` for the
+internal nodes and ``leaf_post``, the reference's DOLEAVES ratio L_s(leaf = x) / L_s (not normalised over x), for the leaves;
+test_scalefree_cpu.py pins both to pinned-state evaluations (exp of the difference of two ``site_logl``) and to brute force.
+
 Node numbering as everywhere in the project: leaf l has node code l, internal node i has code L + i, children before parents, the
 root last; ``flat_parents[code]`` is the internal index of the parent; ``P[code]`` is the matrix of the branch above ``code``.
 """
@@ -49,16 +53,16 @@ def _edge(P, code, L, leaf_codes, ambig, cond, pin, sel):
     return out
 
 
-def _prune_one(D, fp, L, leaf_codes, ambig, P, pi, pin, sel, want_cond, want_post):
+def _prune_one(D, fp, L, leaf_codes, ambig, P, pi, pin, sel, want_cond, want_post, ft=np.float64):
     I = len(fp) - L
     S = len(sel)
     ch = children_of(fp, L)
     cond = [None] * I          # normalised conditionals (largest element 1; zeros where the likelihood is zero)
-    lg = np.zeros((I, S))      # log of everything divided out at and below the node
+    lg = np.zeros((I, S), dtype=ft)   # log of everything divided out at and below the node (``ft``: the type it is summed in)
     edges = {}
     for n in range(I):
         v = np.ones((S, D))
-        acc = np.zeros(S)
+        acc = np.zeros(S, dtype=ft)
         if pin is not None and pin[0] == L + n:
             v = np.zeros((S, D))
             v[np.arange(S), pin[1][sel]] = 1.0
@@ -73,12 +77,12 @@ def _prune_one(D, fp, L, leaf_codes, ambig, P, pi, pin, sel, want_cond, want_pos
             ok = m > 0
             v = np.where(ok[:, None], v / np.where(ok, m, 1.0)[:, None], 0.0)
             with np.errstate(divide="ignore"):
-                acc = acc + np.log(m)
+                acc = acc + np.log(m.astype(ft))
         cond[n] = v
         lg[n] = acc
     root = cond[I - 1] @ pi
     with np.errstate(divide="ignore"):
-        site = np.log(root) + lg[I - 1]
+        site = np.log(root.astype(ft)) + lg[I - 1]
     site = np.where(root > 0, site, -np.inf)
     out = {"site_logl": site}
     if want_cond:
@@ -89,14 +93,13 @@ def _prune_one(D, fp, L, leaf_codes, ambig, P, pi, pin, sel, want_cond, want_pos
         up = [None] * I
         up[I - 1] = np.broadcast_to(pi, (S, D)).copy()
         post = np.zeros((I, S, D))
+        leaf_post = np.zeros((L, S, D))
         for n in range(I - 1, -1, -1):
             w = cond[n] * up[n]
             t = w.sum(axis=1)
             post[n] = np.where((t > 0)[:, None], w / np.where(t > 0, t, 1.0)[:, None], np.nan)
             kids = ch[n]
             for c in kids:
-                if c < L:
-                    continue
                 o = up[n].copy()
                 if pin is not None and pin[0] == L + n:
                     z = np.zeros((S, D))
@@ -108,20 +111,30 @@ def _prune_one(D, fp, L, leaf_codes, ambig, P, pi, pin, sel, want_cond, want_pos
                         m = o.max(axis=1)
                         o = np.where((m > 0)[:, None], o / np.where(m > 0, m, 1.0)[:, None], 0.0)
                 u = o @ P[c]
+                if c < L:                             # a leaf: U_l(x) / sum_y U_l(y) leafvec_l(y), unnormalised over x
+                    k = leaf_codes[c, sel]
+                    lv = np.where((k >= 0)[:, None], np.eye(D)[np.maximum(k, 0)], ambig[np.maximum(-k - 1, 0)])
+                    t = (u * lv).sum(axis=1)
+                    leaf_post[c] = np.where((t > 0)[:, None], u / np.where(t > 0, t, 1.0)[:, None], np.nan)
+                    continue
                 m = u.max(axis=1)
                 up[c - L] = np.where((m > 0)[:, None], u / np.where(m > 0, m, 1.0)[:, None], 0.0)
         out["post"] = post
+        out["leaf_post"] = leaf_post
     return out
 
 
 def prune(D, flat_parents, L, leaf_codes, ambig, pattern_freq, P, root_freqs, weights=None, pinned=None, patterns=None,
-          conditionals=False, posteriors=False):
+          conditionals=False, posteriors=False, log_dtype=np.float64):
     """Scale-free pruning.  ``P``: [B, D, D] transition matrices by node code, or [C, B, D, D] with class ``weights`` [C];
     ``pinned`` = (node code, states [S]); ``patterns``: the subset of pattern indices to evaluate (default: all).
     Returns a dict: ``site_logl`` [S'] (-inf where the likelihood is exactly zero), ``logl`` (sum over patterns with their
     frequencies), and on request ``cond`` [C?, I, S', D] (conditionals divided by their largest element), ``log_mag`` [C?, I, S']
-    (log of that divisor, accumulated over the subtree) and ``post`` [I, S', D] (marginal posteriors of the internal nodes; NaN
-    where the likelihood is zero)."""
+    (log of that divisor, accumulated over the subtree), ``post`` [I, S', D] (marginal posteriors of the internal nodes) and
+    ``leaf_post`` [L, S', D] (the reference's DOLEAVES quantity L_s(leaf = x) / L_s, not normalised over x: U_l(x) / sum_y U_l(y)
+    leafvec_l(y) with U_l the outside vector pushed through P[l]); both NaN where the likelihood is zero.  Classes are mixed by
+    their share of the pattern's likelihood; a class of share 0 is passed over.  ``log_dtype``: the type the logarithms are summed in
+    (np.longdouble where two ``site_logl`` of size 1e3 are to be subtracted to 1e-12 of their difference's exponential)."""
     D, L = int(D), int(L)
     fp = np.asarray(flat_parents, dtype=np.int64)
     codes = np.asarray(leaf_codes, dtype=np.int64)
@@ -132,10 +145,10 @@ def prune(D, flat_parents, L, leaf_codes, ambig, pattern_freq, P, root_freqs, we
     P = np.asarray(P, dtype=np.float64)
     pin = None if pinned is None else (int(pinned[0]), np.asarray(pinned[1], dtype=np.int64))
     if P.ndim == 3:
-        out = _prune_one(D, fp, L, codes, amb, P, pi, pin, sel, conditionals, posteriors)
+        out = _prune_one(D, fp, L, codes, amb, P, pi, pin, sel, conditionals, posteriors, log_dtype)
     else:
         w = np.asarray(weights, dtype=np.float64)
-        per = [_prune_one(D, fp, L, codes, amb, P[c], pi, pin, sel, conditionals, posteriors) for c in range(P.shape[0])]
+        per = [_prune_one(D, fp, L, codes, amb, P[c], pi, pin, sel, conditionals, posteriors, log_dtype) for c in range(P.shape[0])]
         sl = np.stack([p["site_logl"] for p in per])
         with np.errstate(divide="ignore"):
             z = sl + np.log(w)[:, None]
@@ -148,9 +161,12 @@ def prune(D, flat_parents, L, leaf_codes, ambig, pattern_freq, P, root_freqs, we
             out["cond"] = np.stack([p["cond"] for p in per])
             out["log_mag"] = np.stack([p["log_mag"] for p in per])
         if posteriors:   # classes mixed by their share of the pattern's likelihood
-            share = np.exp(z - safe)
-            share = share / share.sum(axis=0)
-            out["post"] = sum(share[c][None, :, None] * per[c]["post"] for c in range(len(per)))
+            share = np.exp(z - safe)           # (a class under which the pattern is impossible has share 0 and a NaN posterior
+            tot = share.sum(axis=0)            #  of its own: it is passed over; impossible under every class: NaN)
+            share = share / np.where(tot > 0, tot, 1.0)
+            for key in ("post", "leaf_post"):
+                mix = sum(np.where(share[c][None, :, None] > 0, share[c][None, :, None] * per[c][key], 0.0) for c in range(len(per)))
+                out[key] = np.where((tot > 0)[None, :, None], mix, np.nan)
     out["logl"] = float(np.sum(out["site_logl"] * freq[sel]))
     return out
 

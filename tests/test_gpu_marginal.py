@@ -1,11 +1,17 @@
 """Marginal ancestral reconstruction on the device (hyphy_hip_marginal_ancestral): one pre-order pass over the resident conditionals
 against the REAL reference's support matrix, against the CPU oracle's pinned-state loop (the computation the reference does:
 RecoverAncestralSequencesMarginal, likefunc2.cpp:932-1120) at every state count, with rate classes, and against the device's own
-pinned route at full size; plus the states the call must leave untouched."""
+pinned route at full size; plus the states the call must leave untouched.
+
+Below those: the call held to the scale-free reference (tests/scalefree.py: ``post``, ``leaf_post``) componentwise, internal rows and
+leaf rows, support and MAP, on the cases of tests/marginal_cases.py — every state count, the rescaling cases, 41 children at one
+node, rate classes whose exponents lie far apart in every order, patterns impossible under one class and under all — in every form
+of the call (shards, the caller's pattern order, every pruning kernel behind it), and twice over the same scratch.  These run with
+HYPHY_HIP_TUNE=0 and probability matrices handed over as they are, so the device's exponentials are no part of the comparison."""
 import numpy as np
 import pytest
 
-from tests import common
+from tests import common, marginal_cases as mc, scalefree as sf
 
 pytestmark = pytest.mark.gpu
 
@@ -294,3 +300,165 @@ def test_full_size_against_device_pinned_route():
         for i in _sample(I):
             ref = _device_pinned(part, f, L + i, (0, 61, 61), base, bsc)
             assert np.allclose(sup[i], ref, rtol=1e-9, atol=1e-12), i
+
+
+# ---- held to the scale-free reference (tests/marginal_cases.py) --------------------------------------------------------------------
+
+WHICH = (("internal", "post"), ("leaves", "leaf_post"))
+
+
+def _evaluate(cs, part, P=None):
+    P = cs["P"] if P is None else P
+    n = np.arange(len(cs["flat_parents"]) - 1, dtype=np.int64)
+    if P.ndim == 4:
+        for c in range(P.shape[0]):
+            part.evaluate(n, n, P[c], cs["root_freqs"], cat=c, q_is_probability=True)
+    else:
+        part.evaluate(n, n, P, cs["root_freqs"], q_is_probability=True)
+
+
+def _held(name, monkeypatch, env=None, cs=None, ref=None, compressed=False):
+    """Both forms of the call on the case under ``env``: support through hold_support, impossible patterns NaN / -1 / NaN, MAP
+    through hold_map.  One call per ``which``.  ``compressed``: the partition has to run class-compressed before the calls (three
+    evaluations: the third is a compressed pass over resident tables) and again at the evaluation after them."""
+    monkeypatch.setenv("HYPHY_HIP_TUNE", "0")
+    for k, v in (env or {}).items():
+        monkeypatch.setenv(k, v)
+    cs = mc.cases()[name] if cs is None else cs
+    ref = mc.reference(name) if ref is None else ref
+    C = cs["P"].shape[0] if cs["P"].ndim == 4 else 1
+    with _mk(cs, C) as part:
+        _evaluate(cs, part)
+        if compressed:
+            part.set_repeats(True)
+            for _ in range(2):
+                _evaluate(cs, part)
+            st = part.repeat_stats()
+            assert st["in_use"] == 1 and st["tables"] > 0, st
+        for which, key in WHICH:
+            what = f"{name} {env or ''} {which} [{part.prune_kernel_name()}]"
+            sup, ms, mv = part.marginal_ancestral(which, weights=cs.get("weights"), map=True)
+            gone = np.isneginf(ref["site_logl"])
+            assert np.isnan(ref[key][:, gone]).all() and np.isnan(sup[:, gone]).all(), what
+            mc.hold_support(what, sup, ref[key], sums_to_one=which == "internal")
+            mc.hold_map(what, ms, mv, sup, ref[key])
+        if compressed:
+            _evaluate(cs, part)
+            assert part.repeat_stats()["in_use"] == 1, part.repeat_stats()
+
+
+@pytest.mark.parametrize("name", mc.group("states"))
+def test_held_at_every_state_count(name, monkeypatch):
+    _held(name, monkeypatch)
+
+
+@pytest.mark.parametrize("name", mc.group("scalefree"))
+def test_held_where_rescaling_bites(name, monkeypatch):
+    _held(name, monkeypatch)
+
+
+@pytest.mark.parametrize("name", mc.group("wide"))
+def test_held_with_forty_children_at_one_node(name, monkeypatch):
+    _held(name, monkeypatch)
+
+
+@pytest.mark.parametrize("name", mc.group("classes"))
+def test_held_with_classes_far_apart_in_every_order(name, monkeypatch):
+    _held(name, monkeypatch)
+
+
+@pytest.mark.parametrize("name", mc.group("one_class_impossible"))
+def test_pattern_impossible_under_one_class(name, monkeypatch):
+    """The other class's exponent is 17 or more above the impossible one's (test_marginal_cases_cpu.py): every row finite and held."""
+    assert np.isfinite(mc.reference(name)["site_logl"]).all()
+    _held(name, monkeypatch)
+
+
+@pytest.mark.parametrize("name", mc.group("all_impossible"))
+def test_pattern_impossible_under_every_class(name, monkeypatch):
+    """NaN in all D entries, MAP state -1 and MAP support NaN on the impossible patterns (include/hyphy_hip.h); held on the rest."""
+    assert np.isneginf(mc.reference(name)["site_logl"]).any()
+    _held(name, monkeypatch)
+
+
+FORM_ENVS = [dict(HYPHY_HIP_FORCE_SHARDS="3"), dict(HYPHY_HIP_SORT_PATTERNS="0"), dict(HYPHY_HIP_FORCE_SHARDS="3", HYPHY_HIP_SORT_PATTERNS="0"),
+             dict(HYPHY_HIP_KERNEL="0"), dict(HYPHY_HIP_KERNEL="1"), dict(HYPHY_HIP_KERNEL="2", HYPHY_HIP_CHAIN_M="2"),
+             dict(HYPHY_HIP_KERNEL="1", HYPHY_HIP_REROOT="1", HYPHY_HIP_CHAIN_M="2")]
+
+
+@pytest.mark.parametrize("env", FORM_ENVS, ids=lambda e: ",".join(f"{k[10:]}={v}" for k, v in e.items()))
+@pytest.mark.parametrize("name", mc.FORMS)
+def test_forms_of_the_call(name, env, monkeypatch):
+    """Held to the reference, not to each other's bits: the persisted conditionals may carry their exponents differently per kernel."""
+    _held(name, monkeypatch, env)
+
+
+@pytest.mark.parametrize("nucgen", ["0", "2"])
+def test_forms_four_states_generated_and_interpreted(nucgen, monkeypatch):
+    _held("mixed_D4_k4_1em20_S37", monkeypatch, dict(HYPHY_HIP_NUCGEN=nucgen))
+
+
+_compressible = {}
+
+
+@pytest.mark.parametrize("D", [61, 4])
+def test_forms_class_compressed(D, monkeypatch):
+    """The call behind a class-compressed evaluation (it restores the per-pattern copies first) on a partition whose subtrees repeat;
+    its matrices are the CPU oracle's exponentials of the case's rates.  The form is asserted in use: at 61 states it exists only on
+    the wave-per-tile kernel, which a partition this small takes on request alone; at 4 states only when forced (HYPHY_HIP_REPEATS=2)."""
+    from oracle import oracle
+    if D not in _compressible:
+        cs = dict(common.compressible_case(D, 7), name=f"compressible_D{D}")
+        cs["P"] = oracle.expm(cs["Q"], False)
+        _compressible[D] = cs, sf.case_reference(cs, posteriors=True)
+    cs, ref = _compressible[D]
+    env = dict(HYPHY_HIP_REPEATS="1", HYPHY_HIP_KERNEL="1") if D > 4 else dict(HYPHY_HIP_REPEATS="2")
+    _held(cs["name"], monkeypatch, env, cs, ref, compressed=True)
+
+
+def _bits(x):
+    return np.ascontiguousarray(x).view(np.int64)
+
+
+@pytest.mark.parametrize("name", mc.FORMS)
+def test_scratch_reuse(name, monkeypatch):
+    """The shard's scratch persists between calls: internal, leaves, internal gives the first call's bits again; after an evaluation
+    with other matrices the call gives a fresh partition's bits under those matrices and none of the first call's."""
+    monkeypatch.setenv("HYPHY_HIP_TUNE", "0")
+    cs = mc.cases()[name]
+    D, B = int(cs["D"]), len(cs["flat_parents"]) - 1
+    P2 = sf.ordinary(np.random.default_rng(21), B, D)
+    with _mk(cs) as part:
+        _evaluate(cs, part)
+        first = part.marginal_ancestral("internal", map=True)
+        leaves = part.marginal_ancestral("leaves", map=True)
+        third = part.marginal_ancestral("internal", map=True)
+        assert all(np.array_equal(_bits(a), _bits(b)) for a, b in zip(first, third)), name
+        assert all(np.array_equal(_bits(a), _bits(b)) for a, b in zip(leaves, part.marginal_ancestral("leaves", map=True))), name
+        _evaluate(cs, part, P2)
+        after = part.marginal_ancestral("internal", map=True)
+        after_l = part.marginal_ancestral("leaves")
+    with _mk(cs) as part:
+        _evaluate(cs, part, P2)
+        fresh = part.marginal_ancestral("internal", map=True)
+        fresh_l = part.marginal_ancestral("leaves")
+    assert all(np.array_equal(_bits(a), _bits(b)) for a, b in zip(after, fresh)), name
+    assert np.array_equal(_bits(after_l), _bits(fresh_l)), name
+    assert np.isfinite(after[0]).all() and not np.any(after[0] == first[0]), name
+    ref = sf.case_reference(dict(cs, P=P2), posteriors=True)
+    mc.hold_support(f"{name} after other matrices", after[0], ref["post"], sums_to_one=True)
+    mc.hold_support(f"{name} after other matrices, leaves", after_l, ref["leaf_post"])
+
+
+@pytest.mark.parametrize("name", ["conflict_k4_d3_D61_1em15", "conflict_k4_d3_D4_1em20", "conflict_k2_d8_D61_1em30", "conflict_k5_d3_D61_1em6",
+                                  "ladder_D61_300", "ladder_D4_300", "mixed_D61_k4_1em15_S53"])
+def test_marginal_posteriors(name, monkeypatch):
+    monkeypatch.setenv("HYPHY_HIP_TUNE", "0")
+    cs = sf.cases_by_name()[name]
+    ref = sf.case_reference(cs, posteriors=True)
+    with _mk(cs) as part:
+        n = np.arange(len(cs["flat_parents"]) - 1, dtype=np.int64)
+        part.evaluate(n, n, cs["P"], cs["root_freqs"], q_is_probability=True, per_site=False)
+        sup = part.marginal_ancestral("internal")
+    ok = np.isfinite(ref["site_logl"])
+    assert np.allclose(sup[:, ok], ref["post"][:, ok], rtol=1e-9, atol=1e-12)

@@ -5,7 +5,7 @@ three steps at once, node sums within ulps of 2^-64, 300- and 600-taxon ladders,
 
 Per pattern ``log(lik) - 64 ln2 sc`` and the total against the reference at scalefree.GPU_RTOL (100 x the oracle's own measured
 deviation from that reference, as the helper's docstring records) plus the absolute 1e-9 test_gpu_parity.py uses near zero;
--inf exactly where the reference has it; exponents integral.  Posteriors at rtol 1e-9 / atol 1e-12 (test_oracle_golden.py's)."""
+-inf exactly where the reference has it; exponents integral.  (Marginal posteriors on these cases: tests/test_gpu_marginal.py.)"""
 import numpy as np
 import pytest
 
@@ -278,16 +278,3 @@ def test_downloaded_conditionals_and_counts(name, kernel, monkeypatch):
         mag = np.log(top) - LOG_SCALER * counts
     ok = ~zero
     assert np.all(np.abs(mag[ok] - ref["log_mag"][ok]) <= RTOL * np.abs(ref["log_mag"][ok]) + ATOL)
-
-
-@pytest.mark.parametrize("name", ["conflict_k4_d3_D61_1em15", "conflict_k4_d3_D4_1em20", "conflict_k2_d8_D61_1em30", "conflict_k5_d3_D61_1em6",
-                                  "ladder_D61_300", "ladder_D4_300", "mixed_D61_k4_1em15_S53"])
-def test_marginal_posteriors(name, monkeypatch):
-    monkeypatch.setenv("HYPHY_HIP_TUNE", "0")
-    cs = CASES[name]
-    ref = sf.case_reference(cs, posteriors=True)
-    with _mk(cs) as part:
-        _full(cs, part, per_site=False)
-        sup = part.marginal_ancestral("internal")
-    ok = np.isfinite(ref["site_logl"])
-    assert np.allclose(sup[:, ok], ref["post"][:, ok], rtol=1e-9, atol=1e-12)

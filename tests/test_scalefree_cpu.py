@@ -102,6 +102,72 @@ def test_posteriors_and_conditionals_agree_with_brute_force():
         c0 = (P[0] @ leafv(0, s)) * (P[1] @ leafv(1, s))
         assert np.allclose(ref["cond"][0, s], c0 / c0.max(), rtol=1e-13)
         assert abs(ref["log_mag"][0, s] - np.log(c0.max())) < 1e-13
+        # leaves: the same enumeration with leaf l set to x in place of its data, over the pattern's own likelihood
+        for l in range(L):
+            want = np.zeros(D)
+            for x in range(D):
+                lv = [np.eye(D)[x] if m == l else leafv(m, s) for m in range(L)]
+                for a in range(D):
+                    for b in range(D):
+                        want[x] += np.sum(pi * P[L + 0][:, a] * P[L + 1][:, b]) * (P[0][a] @ lv[0]) * (P[1][a] @ lv[1]) * (P[2][b] @ lv[2]) * (P[3][b] @ lv[3])
+            assert np.allclose(ref["leaf_post"][l, s], want / tot, rtol=1e-12, atol=0)
+
+
+def _spread(n):
+    return sorted({0, n // 2, n - 1})
+
+
+@pytest.mark.parametrize("name", ["ladder_D4_300", "conflict_k4_d3_D61_1em15", "star_D20_n12_1em6", "classes_D20_k2", "mixed_D4_k4_1em20_S37"])
+def test_posteriors_are_the_pinned_evaluations(name):
+    """``post`` and ``leaf_post`` against the recurrence itself, not the pre-order code: the support of state x at node n is
+    exp(site_logl with n pinned to x - site_logl), for a leaf (its data replaced by x) and an internal node alike; with rate
+    classes both evaluations are the mixed ones.  Every state of three leaves and three internal nodes (the star has three internal
+    nodes in all: the node above its leaves, the cherry and the root), possible patterns only.
+    Where the identity does NOT hold, and no case here has it: a pattern impossible under one class and possible under another, in the
+    row of a leaf, at a state x that the leaf's own data exclude.  The pinned evaluation sums w_c L_c(leaf = x) over every class, the
+    impossible one included (its L_c(leaf = x) is not zero there); ``leaf_post`` mixes per-class ratios by likelihood share and passes
+    a class of share 0 over, numerators and all, as hyphy_hip_marginal_ancestral does (include/hyphy_hip.h).  Internal rows, and leaf
+    rows at the states the data allow, agree either way."""
+    cs = CASES[NAMES.index(name)]
+    L, D = int(cs["L"]), int(cs["D"])
+    I = len(cs["flat_parents"]) - L
+    with np.errstate(invalid="ignore"):
+        ref = sf.case_reference(cs, posteriors=True)
+    ok = np.flatnonzero(np.isfinite(ref["site_logl"]))
+    assert len(ok) >= 8 and (name.startswith("mixed") or len(ok) == len(ref["site_logl"]))
+    assert np.isnan(ref["post"][:, np.isneginf(ref["site_logl"])]).all() and np.isfinite(ref["post"][:, ok]).all()
+    assert np.isnan(ref["leaf_post"][:, np.isneginf(ref["site_logl"])]).all() and np.isfinite(ref["leaf_post"][:, ok]).all()
+    ld = np.longdouble       # (the logarithms are of size 1e3 and their difference is wanted to 1e-12: summed and subtracted in long double)
+    base = sf.case_reference(cs, patterns=ok, log_dtype=ld)["site_logl"]
+    assert np.allclose(base.astype(np.float64), ref["site_logl"][ok], rtol=1e-14, atol=0)
+    for code, got in [(l, ref["leaf_post"][l]) for l in _spread(L)] + [(L + i, ref["post"][i]) for i in _spread(I)]:
+        want = np.zeros((len(ok), D))
+        for x in range(D):
+            pin = (code, np.full(len(ref["site_logl"]), x))
+            want[:, x] = np.exp(sf.case_reference(cs, pinned=pin, patterns=ok, log_dtype=ld)["site_logl"] - base)
+        assert np.allclose(got[ok], want, rtol=1e-12, atol=0), (name, code, float(np.nanmax(np.abs(got[ok] - want) / want)))
+
+
+def test_a_class_of_share_zero_does_not_poison_the_mix():
+    """Two classes, a pattern impossible under the second: the mixed posteriors are the first class's, not NaN; impossible under
+    both: NaN."""
+    rng = np.random.default_rng(6)
+    fp, L = sf.balanced_tree(2, 2)
+    D = 4
+    codes = np.array([[0, 3, 3], [1, 0, 3], [2, 1, 0], [0, 2, 1]], dtype=np.int64)
+    P = np.stack([sf.ordinary(rng, len(fp) - 1, D), sf._block_zero(sf.ordinary(rng, len(fp) - 1, D), D)])
+    cs = sf._case("share0", D, fp, L, codes, P, rng, weights=np.array([0.3, 0.7]))
+    with np.errstate(invalid="ignore"):
+        mix = sf.case_reference(cs, posteriors=True)
+        cs["P"] = np.stack([P[1], P[1]])
+        none = sf.case_reference(cs, posteriors=True)
+    cs["P"] = P[0]
+    one = sf.case_reference(cs, posteriors=True)
+    assert np.isfinite(mix["class_site_logl"][0]).all() and np.isneginf(mix["class_site_logl"][1][1:]).all()
+    for key in ("post", "leaf_post"):
+        assert np.isfinite(mix[key]).all() and np.array_equal(mix[key][:, 1:], one[key][:, 1:])
+        assert not np.allclose(mix[key][:, 0], one[key][:, 0])
+        assert np.isnan(none[key][:, 1:]).all() and np.isfinite(none[key][:, 0]).all()
 
 
 @pytest.mark.parametrize("name", ["codon_deep", "nuc_deep", "codon_ambig", "nuc_ambig"])
