@@ -15,8 +15,6 @@ int fail(const std::string &msg) {
   return -1;
 }
 
-const double kOwnQBuffer = 0.;
-
 namespace {
 
 void free_shard(Shard &s) {
@@ -88,7 +86,6 @@ void refresh_twins(hyphy_hip_partition *p, Shard &s) {
   s.twins_dirty = false;
 }
 
-// Everything in a PruneArgs that does not depend on the schedule being launched.
 // Edge products of the non-last arrivers of a chain schedule: one tile per (class, internal node of the view, tile).  Sized for the
 // tree the schedules are cut from — the trunk when the partition runs class-compressed (16 of 62 internal nodes at the headline
 // workload, 20 of 127 at 128 x 100 k: 1.0 GB instead of 6.5) — and grown when a larger view needs it.
@@ -118,19 +115,13 @@ int ensure_deposits(hyphy_hip_partition *p, Shard &s) {
   return 0;
 }
 
+// Everything in a PruneArgs that does not depend on the schedule being launched.
 PruneArgs base_prune_args(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch) {
   const int64_t B = p->B;
   const int DP = p->DP;
-  PruneArgs pa;
-  pa.ops = nullptr;
-  pa.n_ops = 0;
-  pa.prog = nullptr;
-  pa.n_prog = 1;
-  pa.do_root = 1;
-  pa.NW = p->NW;
-  pa.T = s.T;
-  pa.S_pad = s.S_pad;
-  pa.ntiles = s.ntiles;
+  PruneArgs pa{};  // (what is not set below is null / zero: the schedule, the chain part, the timeline, the fused final combine)
+  pa.n_prog = pa.do_root = pa.n_prog_total = 1;
+  pa.NW = p->NW, pa.T = s.T, pa.S_pad = s.S_pad, pa.ntiles = s.ntiles;
   const hyphy_hip_partition::View &v = p->vw();  // (node indices and leaf numbers are the view's; class strides the partition's)
   pa.root_inode = v.I - 1;
   pa.root_slot = p->root_slot;
@@ -161,441 +152,421 @@ PruneArgs base_prune_args(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_b
   pa.site_lik = s.site_lik + (size_t)cat * s.S_pad;
   pa.site_cnt = s.site_cnt + (size_t)cat * s.S_pad;
   pa.freq = s.freq;
-  pa.wg_sum = s.wg_sum;
   if (p->rr_active && p->chain && !p->nuc) pa.pi = s.pi_ones;  // (re-rooted schedule: pi is folded into the old root's twin image)
-  pa.wg_cnt = s.wg_cnt;
-  pa.wg_flag = s.wg_flag;
+  pa.wg_sum = s.wg_sum, pa.wg_cnt = s.wg_cnt, pa.wg_flag = s.wg_flag;
   pa.n_cat = n_cat_batch;
   pa.cs_P = (size_t)B * DP * DP;
   pa.cs_partials = s.partial_stride;
   pa.cs_counts = (size_t)p->I * s.S_pad;
   pa.cs_site = (size_t)s.S_pad;
   pa.cs_wg = (size_t)s.ntiles / s.T;
-  pa.timeline = nullptr;
-  pa.ablate = 0;
   pa.frag_ctr = s.frag_ctr;
   pa.hand_cnt = s.hand_cnt;
-  pa.n_prog_total = 1;
   pa.wave_variant = getenv("HYPHY_HIP_WAVE_VARIANT") ? atoi(getenv("HYPHY_HIP_WAVE_VARIANT")) : p->wave_variant;
-  pa.chain = 0;
-  pa.jn = nullptr;
-  pa.deposits = nullptr;
-  pa.red_out = nullptr;  // (fused final combine: enqueue_eval turns it on for the launch that finalises the roots)
-  pa.red_rec = nullptr;
-  pa.red_status = nullptr;
-  pa.red_seq = 0.;
-  pa.red_done = nullptr;
-  pa.red_n = 0;
   return pa;
 }
 
 namespace {
 
-int enqueue_eval(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch, bool sched_changed, bool pi_changed,
-                 bool slots_changed, const int64_t *q_nodes, int64_t n_q,
-                 const double *q, bool q_on_device, int q_is_prob, const double *root_freqs, double *d_logl_out,
-                 bool reduce, bool floor_log, const MixSpec *mix = nullptr) {
-  Trace tr("enqueue");
+// ---- one evaluation on one shard: enqueue_eval runs the stages below, in this order, over one context on its stack ----
+struct Timeline;
+struct EvalCtx {
+  hyphy_hip_partition *p;
+  Shard &s;
+  int cat, n_cat_batch;                          // class (class 0 of a batch), classes in the launch
+  bool sched_changed, pi_changed, slots_changed;  // what eval_common found changed against the host caches
+  const EvalRequest &rq;
+  Trace tr{"enqueue"};
+  int n_ops = 0;                  // longest program of the schedule: > 0 means a pruning launch follows
+  bool use_gen = false;           // 4 states: the run-time generated kernel serves this pass
+  ExpmArgs folded_expm;           // 4 states, small shard (have_folded): the exponentials the pruning launch computes itself
+  bool have_folded = false, stamp = false;  // stamp: this evaluation carries a kernel-duration stamp ...
+  size_t ring_slot = 0;           // ... in this pair of the timing ring
+  int n_wg = 0;                   // workgroups of the launch that leaves per-workgroup partial sums
+  bool fused_reduce = false;      // ... which also ran the final combine
+  double *site_lik() const { return s.site_lik + (size_t)cat * s.S_pad; }
+  int32_t *site_cnt() const { return s.site_cnt + (size_t)cat * s.S_pad; }
+  int32_t *d_slots() const { return s.slots + (size_t)cat * p->B; }
+  const double *dense_q() const { return rq.q_source == QSource::OwnStaged ? s.qbuf : rq.q; }
+  bool q_on_device() const { return rq.q_source != QSource::HostDense; }
+  int enqueue_eval();
+  int stage_schedule(), stage_pi(), stage_slot_table(), stage_expm_mixture(), stage_expm_plain(), stage_stamps_open(), stage_prune_nuc(),
+      stage_prune_mfma(), stage_stamps_close(), stage_export(), stage_reduce();
+  void stage_gen_decision();
+  ExpmArgs expm_args_common(bool built) const;
+  int guard_coeff_slot();
+  bool fused_combine_allowed() const;
+  template <typename Args>
+  void wire_fused_combine(Args &a, int *red_done);
+  int dump_timeline(const Timeline &tl);
+};
+
+int EvalCtx::stage_schedule() {  // schedule upload, deposits of chain schedules
   HIPCHK(hipSetDevice(s.device));
-  if (q == &kOwnQBuffer) q = s.qbuf;
-  const int64_t D = p->D, B = p->B;
-  const int DP = p->DP;
   tr.lap("setdevice");
-  if (sched_changed && !p->ops_host.empty()) {
-    HIPCHK(hipStreamSynchronize(s.stream));
-    memcpy(s.h_ops, p->ops_host.data(), p->ops_host.size() * sizeof(int4));
-    HIPCHK(hipMemcpyAsync(s.ops, s.h_ops, p->ops_host.size() * sizeof(int4), hipMemcpyHostToDevice, s.stream));
-    for (size_t k = 0; k < p->programs.size(); k++)
-      s.h_prog[k] = make_int4(p->programs[k].off, p->programs[k].n, p->programs[k].parent, p->programs[k].need);
-    HIPCHK(hipMemcpyAsync(s.prog, s.h_prog, p->programs.size() * sizeof(int4), hipMemcpyHostToDevice, s.stream));
-    if (p->chain) {
-      memcpy(s.h_jn, p->jn_host.data(), p->jn_host.size() * sizeof(int4));
-      HIPCHK(hipMemcpyAsync(s.jn, s.h_jn, p->jn_host.size() * sizeof(int4), hipMemcpyHostToDevice, s.stream));
-    }
-  }
-  if (p->chain && ensure_deposits(p, s)) return -1;
-  // root frequencies, zero padded (uploaded only when they change)
+  if (sched_changed && !p->ops_host.empty()) {  // (a chain schedule's deposits are seen to inside)
+    if (upload_schedule(p, s, false)) return -1;
+  } else if (p->chain && ensure_deposits(p, s)) return -1;
+  return 0;
+}
+
+int EvalCtx::stage_pi() {  // root frequencies, zero padded (uploaded only when they change)
   if (pi_changed) {
-    std::vector<double> pi(p->nuc ? 4 : DP, 0.0);
-    for (int64_t k = 0; k < D; k++) pi[k] = root_freqs[k];
+    std::vector<double> pi(p->nuc ? 4 : p->DP, 0.0);
+    for (int64_t k = 0; k < p->D; k++) pi[k] = rq.root_freqs[k];
     if (upload_small(s, pi.data(), pi.size(), s.pi)) return -1;
     if (!p->rr_path.empty()) s.twins_dirty = true;  // (pi sits in the twin of the old root's edge; an expm launch that covers every twin clears this again)
   }
   tr.lap("ops+pi");
   if (p->all_timings) HIPCHK(hipEventRecord(s.ev[0], s.stream));
   tr.lap("event0");
-  int n_ops_planned = 0;  // longest program: > 0 means a pruning launch follows
-  for (const auto &pr : p->programs) n_ops_planned = std::max(n_ops_planned, pr.n);
-  ExpmArgs folded_expm;
-  bool have_folded = false;
-  // 4 states: a schedule that keeps coming back runs as straight-line code compiled at run time (nucgen.hip) — requested after
-  // nucgen_after() evaluations under it, used from the evaluation that finds it compiled; the interpreter until then and for
-  // everything the generator does not cover (pinned states, the trunk of a class-compressed partition, one-leaf entries)
-  bool use_gen = false;
-  if (p->nuc && p->mode == 0 && p->nucgen_key != 0 && n_ops_planned > 0 && p->pin_node < 0 && p->nuc_leaf_pairs && p->programs.size() == 1 &&
-      s.S_pad % 256 == 0) {
-    const int gm = nucgen_mode();
-    if (gm != 0) {
-      use_gen = nucgen_ready(p->nucgen_key);
-      if (!use_gen && (gm == 2 || ++p->nucgen_uses >= nucgen_after()) && !p->nucgen_asked) {
-        p->nucgen_asked = true;
-        nucgen_request(p->nucgen_key, p->ops_host.data() + p->programs[0].off, p->programs[0].n, (int)p->L, !p->cached_persist, p->nucgen_small, (int)p->B, gm == 2);
-        use_gen = nucgen_ready(p->nucgen_key);
-      }
+  return 0;
+}
+
+// 4 states: a schedule that keeps coming back runs as straight-line code compiled at run time (nucgen.hip) — requested after
+// nucgen_after() evaluations under it, used from the evaluation that finds it compiled; the interpreter until then and for
+// everything the generator does not cover (pinned states, the trunk of a class-compressed partition, one-leaf entries)
+void EvalCtx::stage_gen_decision() {
+  for (const auto &pr : p->programs) n_ops = std::max(n_ops, pr.n);
+  if (!(p->nuc && p->mode == 0 && p->nucgen_key != 0 && n_ops > 0 && p->pin_node < 0 && p->nuc_leaf_pairs && p->programs.size() == 1 &&
+        s.S_pad % 256 == 0))
+    return;
+  const int gm = nucgen_mode();
+  if (gm == 0) return;
+  use_gen = nucgen_ready(p->nucgen_key);
+  if (!use_gen && (gm == 2 || ++p->nucgen_uses >= nucgen_after()) && !p->nucgen_asked) {
+    p->nucgen_asked = true;
+    nucgen_request(p->nucgen_key, p->ops_host.data() + p->programs[0].off, p->programs[0].n, (int)p->L, !p->cached_persist, p->nucgen_small, (int)p->B, gm == 2);
+    use_gen = nucgen_ready(p->nucgen_key);
+  }
+}
+
+// n_cat_batch > 1: the matrices of ALL rate classes in one expm launch, class-major; destination
+// slot of matrix (c, k) is c*B + q_nodes[k] relative to class 0's image arrays
+int EvalCtx::stage_slot_table() {
+  if (!slots_changed) return 0;
+  const int64_t B = p->B, n_q = rq.n_q;
+  int32_t *h_slots = s.h_slots + (size_t)cat * B;
+  HIPCHK(hipStreamSynchronize(s.stream));
+  for (int k = 0; k < n_cat_batch; k++)
+    for (int64_t j = 0; j < n_q; j++) {
+      if (rq.q_nodes[j] < 0 || rq.q_nodes[j] >= B) return fail("q_nodes entry out of range");
+      h_slots[k * n_q + j] = (int32_t)(k * B + rq.q_nodes[j]);
+    }
+  HIPCHK(hipMemcpyAsync(d_slots(), h_slots, n_q * n_cat_batch * sizeof(int32_t), hipMemcpyHostToDevice, s.stream));
+  return 0;
+}
+
+// What every exponential launch of an evaluation states: size, status word and — `built`: rows staged by hyphy_hip_build_q — the template part.
+ExpmArgs EvalCtx::expm_args_common(bool built) const {
+  ExpmArgs ea;
+  ea.D = (int)p->D;
+  ea.status = s.status;
+  if (built) {
+    ea.templates = s.templates;
+    ea.templates_pad = s.templates_pad;
+    ea.coeffs = s.coeffs_cur ? s.coeffs_cur : s.coeffs;
+    ea.coeffs_host = (s.coeffs_cur && s.d_hcoeffs) ? s.h_coeffs + (s.coeffs_cur - s.d_hcoeffs) : nullptr;
+    ea.K = (int)p->K;
+  }
+  return ea;
+}
+
+// The fused expm kernel reads a coefficient ring slot over PCIe when it EXECUTES: behind the launch that consumes the slot an
+// asynchronous caller (d_logl_out) records the slot's event, and hyphy_hip_build_q waits for it before rewriting the slot.
+int EvalCtx::guard_coeff_slot() {
+  if (!rq.d_logl_out || s.coeff_slot < 0) return 0;
+  HIPCHK(hipEventRecord(s.coeff_ev[s.coeff_slot], s.stream));
+  s.coeff_busy[s.coeff_slot] = true;
+  return 0;
+}
+
+// explicit-form branch-site mixtures: exponentiate every component, then mix into the branch's matrix images.  Component rate
+// matrices: dense from the host, or (the shard's own buffer behind hyphy_hip_build_q) formed inside the exponential kernel from the
+// staged coefficient rows, one row per (branch, component)
+int EvalCtx::stage_expm_mixture() {
+  const int64_t D = p->D, B = p->B, n_q = rq.n_q;
+  const int DP = p->DP;
+  const bool mix_built = q_on_device() && dense_q() == s.qbuf && p->coeffs_pending;
+  if ((q_on_device() && !mix_built) || rq.q_is_probability || n_cat_batch != 1)
+    return fail("mixture evaluation: host rate matrices or hyphy_hip_build_q rows, one class at a time");
+  const size_t n_tot = (size_t)rq.mix->n_tot, DD = (size_t)D * D;
+  if (mix_built && s.coeff_rows != (int64_t)n_tot)
+    return fail("mixture evaluation: hyphy_hip_build_q staged a different number of rows than the components of this evaluation");
+  // (rows are staged without saying what they are: the first evaluation that consumes a staging claims it — one row per (branch,
+  //  component) here — and an evaluation of the other kind that happens to need the same number of rows is refused)
+  if (mix_built && s.coeff_kind == 1) return fail("mixture evaluation: the staged rows were consumed as one row per (class, branch): call hyphy_hip_build_q first");
+  if (mix_built) s.coeff_kind = 2;
+  if (s.mix_cap < n_tot || s.mix_nq_cap < (size_t)n_q) {
+    HIPCHK(hipStreamSynchronize(s.stream));
+    for (void *d : {(void *)s.mix_q, (void *)s.mix_p, (void *)s.mix_w, (void *)s.mix_off})
+      if (d) pool_free_sync(d);
+    s.mix_q = s.mix_p = s.mix_w = nullptr;
+    s.mix_off = nullptr;
+    s.mix_cap = std::max(n_tot, (size_t)(2 * B));
+    s.mix_nq_cap = (size_t)B;
+    HIPCHK(pool_malloc((void **)&s.mix_q, s.mix_cap * DD * sizeof(double)));
+    HIPCHK(pool_malloc((void **)&s.mix_p, s.mix_cap * DD * sizeof(double)));
+    HIPCHK(pool_malloc((void **)&s.mix_w, s.mix_cap * sizeof(double)));
+    HIPCHK(pool_malloc((void **)&s.mix_off, (s.mix_nq_cap + 1) * sizeof(int)));
+  }
+  std::vector<int> off((size_t)n_q + 1, 0);
+  for (int64_t k = 0; k < n_q; k++) off[k + 1] = off[k] + (int)rq.mix->count[k];
+  if (!mix_built) HIPCHK(hipMemcpyAsync(s.mix_q, dense_q(), n_tot * DD * sizeof(double), hipMemcpyHostToDevice, s.stream));
+  HIPCHK(hipMemcpyAsync(s.mix_w, rq.mix->weights, n_tot * sizeof(double), hipMemcpyHostToDevice, s.stream));
+  HIPCHK(hipMemcpyAsync(s.mix_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
+  HIPCHK(hipStreamSynchronize(s.stream));  // (pageable sources; `off` goes out of scope)
+  ExpmArgs ea = expm_args_common(mix_built);
+  ea.Q = s.mix_q, ea.n = (int)n_tot, ea.Prow = s.mix_p;
+  const bool coeffs_consumed = launch_expm(ea, s.stream);
+  if (mix_built && !coeffs_consumed && guard_coeff_slot()) return -1;
+  s.twins_dirty = true;  // (the mixing kernel writes matrix images without their twins)
+  launch_mix_images(s.mix_p, s.mix_off, s.mix_w, d_slots(), (int)n_q, (int)D,
+                    p->nuc ? nullptr : s.Pfrag + (size_t)cat * B * DP * DP, p->nuc ? nullptr : s.PTg + (size_t)cat * B * DP * DP,
+                    p->nuc ? s.Prow + (size_t)cat * B * 16 : nullptr, s.stream,
+                    p->nuc ? s.Prow + ((size_t)p->C * B + (size_t)cat * B) * 16 : nullptr);
+  return 0;
+}
+
+int EvalCtx::stage_expm_plain() {
+  const int64_t D = p->D, B = p->B, n_q = rq.n_q, n_mat = n_q * n_cat_batch;
+  const int DP = p->DP, q_is_prob = rq.q_is_probability;
+  const double *dq = dense_q();
+  const bool own = q_on_device() && dq == s.qbuf && !q_is_prob;
+  const bool q_from_templates = own && p->coeffs_pending;
+  if (own) {
+    // the partition's own Q buffer is only meaningful behind hyphy_hip_build_q: either the staged coefficients
+    // (fused construction) or the materialised matrices, with exactly the rows this evaluation consumes
+    if (!q_from_templates && !s.qbuf_built) return fail("evaluate from the Q buffer: no rate matrices staged (call hyphy_hip_build_q first)");
+    if (s.coeff_rows != n_mat) return fail("evaluate from the Q buffer: hyphy_hip_build_q staged a different number of matrices than this evaluation consumes");
+    if (s.coeff_kind == 2) return fail("evaluate from the Q buffer: the staged rows were consumed as mixture components: call hyphy_hip_build_q first");
+    s.coeff_kind = 1;
+  }
+  if (!q_on_device()) {
+    HIPCHK(hipMemcpyAsync(s.qbuf, dq, (size_t)n_mat * D * D * sizeof(double), hipMemcpyHostToDevice, s.stream));
+    dq = s.qbuf;
+  }
+  ExpmArgs ea = expm_args_common(q_from_templates);  // (fused build: coefficients were staged by hyphy_hip_build_q)
+  ea.Q = dq, ea.slots = d_slots(), ea.n = (int)n_mat, ea.is_prob = q_is_prob;
+  ea.prof = getenv("HYPHY_HIP_EXPM_PROF") ? 1 : 0;
+  if (p->nuc) {
+    ea.Prow = s.Prow + (size_t)cat * B * 16;
+    ea.PTrow = s.Prow + ((size_t)p->C * B + (size_t)cat * B) * 16;  // (transposed copies behind the row-major ones)
+  } else {
+    ea.Pfrag = s.Pfrag + (size_t)cat * B * DP * DP;
+    ea.PTg = s.PTg + (size_t)cat * B * DP * DP;
+    static const bool mask_on = !(getenv("HYPHY_HIP_EXPM_MASK") && atoi(getenv("HYPHY_HIP_EXPM_MASK")) == 0);
+    if (mask_on && s.expm_need) {
+      ea.need = s.expm_need;
+      ea.need_B = (int)B;
     }
   }
-  if (n_q > 0) {
-    // n_cat_batch > 1: the matrices of ALL rate classes in one expm launch, class-major; destination
-    // slot of matrix (c, k) is c*B + q_nodes[k] relative to class 0's image arrays
-    const int64_t n_mat = n_q * n_cat_batch;
-    int32_t *h_slots = s.h_slots + (size_t)cat * B, *d_slots = s.slots + (size_t)cat * B;
-    if (slots_changed) {
-      HIPCHK(hipStreamSynchronize(s.stream));
-      for (int c = 0; c < n_cat_batch; c++)
-        for (int64_t k = 0; k < n_q; k++) {
-          if (q_nodes[k] < 0 || q_nodes[k] >= B) return fail("q_nodes entry out of range");
-          h_slots[c * n_q + k] = (int32_t)(c * B + q_nodes[k]);
-        }
-      HIPCHK(hipMemcpyAsync(d_slots, h_slots, n_mat * sizeof(int32_t), hipMemcpyHostToDevice, s.stream));
-    }
-    if (mix) {
-      // explicit-form branch-site mixtures: exponentiate every component, then mix into the branch's matrix images
-      // component rate matrices: dense from the host, or (q == the partition's own buffer behind hyphy_hip_build_q) formed inside
-      // the exponential kernel from the staged coefficient rows, one row per (branch, component)
-      const bool mix_built = q_on_device && q == s.qbuf && p->coeffs_pending;
-      if ((q_on_device && !mix_built) || q_is_prob || n_cat_batch != 1)
-        return fail("mixture evaluation: host rate matrices or hyphy_hip_build_q rows, one class at a time");
-      const size_t n_tot = (size_t)mix->n_tot, DD = (size_t)D * D;
-      if (mix_built && s.coeff_rows != (int64_t)n_tot)
-        return fail("mixture evaluation: hyphy_hip_build_q staged a different number of rows than the components of this evaluation");
-      // (rows are staged without saying what they are: the first evaluation that consumes a staging claims it — one row per (branch,
-      //  component) here — and an evaluation of the other kind that happens to need the same number of rows is refused)
-      if (mix_built && s.coeff_kind == 1) return fail("mixture evaluation: the staged rows were consumed as one row per (class, branch): call hyphy_hip_build_q first");
-      if (mix_built) s.coeff_kind = 2;
-      if (s.mix_cap < n_tot || s.mix_nq_cap < (size_t)n_q) {
-        HIPCHK(hipStreamSynchronize(s.stream));
-        for (void *d : {(void *)s.mix_q, (void *)s.mix_p, (void *)s.mix_w, (void *)s.mix_off})
-          if (d) pool_free_sync(d);
-        s.mix_q = s.mix_p = s.mix_w = nullptr;
-        s.mix_off = nullptr;
-        s.mix_cap = std::max(n_tot, (size_t)(2 * B));
-        s.mix_nq_cap = (size_t)B;
-        HIPCHK(pool_malloc((void **)&s.mix_q, s.mix_cap * DD * sizeof(double)));
-        HIPCHK(pool_malloc((void **)&s.mix_p, s.mix_cap * DD * sizeof(double)));
-        HIPCHK(pool_malloc((void **)&s.mix_w, s.mix_cap * sizeof(double)));
-        HIPCHK(pool_malloc((void **)&s.mix_off, (s.mix_nq_cap + 1) * sizeof(int)));
-      }
-      std::vector<int> off((size_t)n_q + 1, 0);
-      for (int64_t k = 0; k < n_q; k++) off[k + 1] = off[k] + (int)mix->count[k];
-      if (!mix_built) HIPCHK(hipMemcpyAsync(s.mix_q, q, n_tot * DD * sizeof(double), hipMemcpyHostToDevice, s.stream));
-      HIPCHK(hipMemcpyAsync(s.mix_w, mix->weights, n_tot * sizeof(double), hipMemcpyHostToDevice, s.stream));
-      HIPCHK(hipMemcpyAsync(s.mix_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
-      HIPCHK(hipStreamSynchronize(s.stream));  // (pageable sources; `off` goes out of scope)
-      ExpmArgs ea;
-      ea.Q = s.mix_q;
-      ea.slots = nullptr;
-      ea.n = (int)n_tot;
-      ea.D = (int)D;
-      ea.is_prob = 0;
-      ea.status = s.status;
-      ea.templates = nullptr;
-      ea.coeffs = nullptr;
-      ea.K = 0;
-      if (mix_built) {
-        ea.templates = s.templates;
-        ea.templates_pad = s.templates_pad;
-        ea.coeffs = s.coeffs_cur ? s.coeffs_cur : s.coeffs;
-        ea.coeffs_host = (s.coeffs_cur && s.d_hcoeffs) ? s.h_coeffs + (s.coeffs_cur - s.d_hcoeffs) : nullptr;
-        ea.K = (int)p->K;
-      }
-      ea.prof = 0;
-      ea.Prow = s.mix_p;
-      ea.Pfrag = nullptr;
-      ea.PTg = nullptr;
-      const bool mix_coeffs_consumed = launch_expm(ea, s.stream);
-      if (mix_built && d_logl_out && s.coeff_slot >= 0 && !mix_coeffs_consumed) {  // (asynchronous caller: guard the ring slot)
-        HIPCHK(hipEventRecord(s.coeff_ev[s.coeff_slot], s.stream));
-        s.coeff_busy[s.coeff_slot] = true;
-      }
-      s.twins_dirty = true;  // (the mixing kernel writes matrix images without their twins)
-      launch_mix_images(s.mix_p, s.mix_off, s.mix_w, d_slots, (int)n_q, (int)D,
-                        p->nuc ? nullptr : s.Pfrag + (size_t)cat * B * DP * DP, p->nuc ? nullptr : s.PTg + (size_t)cat * B * DP * DP,
-                        p->nuc ? s.Prow + (size_t)cat * B * 16 : nullptr, s.stream,
-                        p->nuc ? s.Prow + ((size_t)p->C * B + (size_t)cat * B) * 16 : nullptr);
-    } else {
-    const double *dq = q;
-    const bool q_from_templates = q_on_device && q == s.qbuf && p->coeffs_pending && !q_is_prob;
-    if (q_on_device && q == s.qbuf && !q_is_prob) {
-      // the partition's own Q buffer is only meaningful behind hyphy_hip_build_q: either the staged coefficients
-      // (fused construction) or the materialised matrices, with exactly the rows this evaluation consumes
-      if (!q_from_templates && !s.qbuf_built) return fail("evaluate from the Q buffer: no rate matrices staged (call hyphy_hip_build_q first)");
-      if (s.coeff_rows != n_mat) return fail("evaluate from the Q buffer: hyphy_hip_build_q staged a different number of matrices than this evaluation consumes");
-      if (s.coeff_kind == 2) return fail("evaluate from the Q buffer: the staged rows were consumed as mixture components: call hyphy_hip_build_q first");
-      s.coeff_kind = 1;
-    }
-    if (!q_on_device) {
-      HIPCHK(hipMemcpyAsync(s.qbuf, q, (size_t)n_mat * D * D * sizeof(double), hipMemcpyHostToDevice, s.stream));
-      dq = s.qbuf;
-    }
-    ExpmArgs ea;
-    ea.Q = dq;
-    ea.slots = d_slots;
-    ea.n = (int)n_mat;
-    ea.D = (int)D;
-    ea.is_prob = q_is_prob;
-    ea.status = s.status;
-    ea.templates = nullptr;
-    ea.coeffs = nullptr;
-    ea.K = 0;
-    ea.prof = getenv("HYPHY_HIP_EXPM_PROF") ? 1 : 0;
-    if (q_from_templates) {  // fused build: coefficients were staged by hyphy_hip_build_q
-      ea.templates = s.templates;
-      ea.templates_pad = s.templates_pad;
-      ea.coeffs = s.coeffs_cur ? s.coeffs_cur : s.coeffs;
-      ea.coeffs_host = (s.coeffs_cur && s.d_hcoeffs) ? s.h_coeffs + (s.coeffs_cur - s.d_hcoeffs) : nullptr;
-      ea.K = (int)p->K;
-    }
-    if (p->nuc) {
-      ea.Prow = s.Prow + (size_t)cat * B * 16;
-      ea.PTrow = s.Prow + ((size_t)p->C * B + (size_t)cat * B) * 16;  // (transposed copies behind the row-major ones)
-      ea.Pfrag = nullptr;
-      ea.PTg = nullptr;
-    } else {
-      ea.Prow = nullptr;
-      ea.Pfrag = s.Pfrag + (size_t)cat * B * DP * DP;
-      ea.PTg = s.PTg + (size_t)cat * B * DP * DP;
-      static const bool mask_on = !(getenv("HYPHY_HIP_EXPM_MASK") && atoi(getenv("HYPHY_HIP_EXPM_MASK")) == 0);
-      if (mask_on && s.expm_need) {
-        ea.need = s.expm_need;
-        ea.need_B = (int)B;
-      }
-    }
-    if (!p->rr_path.empty() && !p->nuc && n_cat_batch <= 1) {  // keep the transposed twins in step with the matrices they mirror
-      const size_t k = p->rr_path.size() - 1;
-      ea.n_twin = (int)k;
-      for (size_t j = 0; j < k; j++) ea.twin_src[j] = p->vw().slot[p->vw().L + p->rr_path[j + 1]];
-      ea.twin_dst0 = twin_slot0(p);
-      ea.twin_pi = s.pi;
-      size_t covered = 0;
-      for (int64_t q = 0; q < n_q; q++)
-        for (size_t j = 0; j < k; j++)
-          if (q_nodes[q] == ea.twin_src[j]) covered++;
-      if (covered == k) s.twins_dirty = false;           // every twin rewritten by this launch (with the current pi)
-    }
-    tr.lap("slots+q");
-    bool coeffs_consumed = false;
-    if (p->nuc && p->mode == 0 && (!use_gen || p->nucgen_small) && prune_nuc_folds_expm((int)p->L, s.S_pad, n_ops_planned) && !(q_from_templates && !ea.coeffs)) {
-      folded_expm = ea;  // (4 states, small shard: the pruning launch computes the exponentials itself)
-      have_folded = true;
-      set_last_expm_kernel("");
-    } else {
-      coeffs_consumed = launch_expm(ea, s.stream);
-    }
-    if (q_from_templates && d_logl_out && s.coeff_slot >= 0 && !coeffs_consumed && !have_folded) {  // asynchronous caller: guard the ring slot until the kernel has run
-      HIPCHK(hipEventRecord(s.coeff_ev[s.coeff_slot], s.stream));
-      s.coeff_busy[s.coeff_slot] = true;
-    }
-    tr.lap("launch_expm");
-    }
+  if (!p->rr_path.empty() && !p->nuc && n_cat_batch <= 1) {  // keep the transposed twins in step with the matrices they mirror
+    const size_t k = p->rr_path.size() - 1;
+    ea.n_twin = (int)k;
+    for (size_t j = 0; j < k; j++) ea.twin_src[j] = p->vw().slot[p->vw().L + p->rr_path[j + 1]];
+    ea.twin_dst0 = twin_slot0(p);
+    ea.twin_pi = s.pi;
+    size_t covered = 0;
+    for (int64_t q = 0; q < n_q; q++)
+      for (size_t j = 0; j < k; j++)
+        if (rq.q_nodes[q] == ea.twin_src[j]) covered++;
+    if (covered == k) s.twins_dirty = false;           // every twin rewritten by this launch (with the current pi)
   }
-  // kernel-duration stamps (an event pair around the pruning launches: two barrier packets, ~5 us of stream time at the
-  // headline size): one evaluation in 16 by default — an optimiser's sweep should not pay for a profile nobody reads —,
-  // HYPHY_HIP_TIMING_EVERY=n keeps one in n (bench.py: 4, the rocprofv3 runs: 1)
+  tr.lap("slots+q");
+  if (p->nuc && p->mode == 0 && (!use_gen || p->nucgen_small) && prune_nuc_folds_expm((int)p->L, s.S_pad, n_ops) && !(q_from_templates && !ea.coeffs)) {
+    folded_expm = ea;  // (4 states, small shard: the pruning launch computes the exponentials itself — and guards the ring slot behind it)
+    have_folded = true;
+    set_last_expm_kernel("");
+  } else {
+    const bool coeffs_consumed = launch_expm(ea, s.stream);
+    if (q_from_templates && !coeffs_consumed && guard_coeff_slot()) return -1;
+  }
+  tr.lap("launch_expm");
+  return 0;
+}
+
+// kernel-duration stamps (an event pair around the pruning launches: two barrier packets, ~5 us of stream time at the
+// headline size): one evaluation in 16 by default — an optimiser's sweep should not pay for a profile nobody reads —,
+// HYPHY_HIP_TIMING_EVERY=n keeps one in n (bench.py: 4, the rocprofv3 runs: 1)
+int EvalCtx::stage_stamps_open() {
   static const int timing_every = getenv("HYPHY_HIP_TIMING_EVERY") ? std::max(1, atoi(getenv("HYPHY_HIP_TIMING_EVERY"))) : 16;
-  const bool stamp = timing_every == 1 || p->all_timings || (s.eval_count++ % (uint64_t)timing_every) == 0;
+  stamp = timing_every == 1 || p->all_timings || (s.eval_count++ % (uint64_t)timing_every) == 0;
   s.last_stamped = stamp;
-  const size_t ring_slot = (size_t)(s.ring_count % kTimingRing) * 2;
+  ring_slot = (size_t)(s.ring_count % kTimingRing) * 2;
   if (stamp && !s.ring[ring_slot]) {  // (the ring's events are made on first use: a short-lived partition never pays for 2 048 of them)
     HIPCHK(hipEventCreate(&s.ring[ring_slot]));
     HIPCHK(hipEventCreate(&s.ring[ring_slot + 1]));
   }
   if (p->all_timings) HIPCHK(hipEventRecord(s.ev[1], s.stream));  // (before the ring's stamp: the exponentials' interval ends here)
   if (stamp) HIPCHK(hipEventRecord(s.ring[ring_slot], s.stream));
-  if (p->mode == 1 && rep_launch(p, s, cat)) return -1;  // lower phase: the class tables this pass recomputes
-  int n_ops = 0;  // longest program
-  for (const auto &pr : p->programs) n_ops = std::max(n_ops, pr.n);
-  double *site_lik = s.site_lik + (size_t)cat * s.S_pad;
-  int32_t *site_cnt = s.site_cnt + (size_t)cat * s.S_pad;
-  int n_wg = 0;
-  bool fused_reduce = false;
-  if (p->nuc) {
-    NucArgs na;
-    na.ops = s.ops + (p->programs.empty() ? 0 : p->programs[0].off);
-    na.n_ops = n_ops;
-    na.S_pad = s.S_pad;
-    na.L = (int)p->L;
-    na.root_inode = (int)p->I - 1;
-    na.P = s.Prow + (size_t)cat * B * 16;
-    na.PT = s.Prow + ((size_t)p->C * B + (size_t)cat * B) * 16;
-    na.codes = s.codes;
-    na.pin = s.pin;
-    na.pin_leaf = (p->pin_node >= 0 && p->pin_node < p->L) ? (int)p->pin_node : -1;
-    na.pin_inode = p->pin_node >= p->L ? (int)(p->pin_node - p->L) : -1;
-    na.ambig = s.ambig;
-    na.partials = s.partials + (size_t)cat * s.partial_stride;
-    na.counts = s.counts + (size_t)cat * p->I * s.S_pad;
-    na.pi = s.pi;
-    na.site_lik = site_lik;
-    na.site_cnt = site_cnt;
-    na.freq = s.freq;
-    na.wg_sum = s.wg_sum;
-    na.wg_cnt = s.wg_cnt;
-    na.wg_flag = s.wg_flag;
-    if (p->mode == 1) {  // the trunk of a class-compressed partition (repeats.hip): generalised leaves, one leaf per entry
-      const hyphy_hip_partition::View &v = p->vw();
-      na.L = v.L;
-      na.root_inode = v.I - 1;
-      na.codes = s.rep_codes_tile;   // (4 states: row-major [view leaf][pattern])
-      na.PT = nullptr;               // (prune_nuc_kernel)
-      na.leaf_tab = s.rep_leaf;
-      na.gtab = s.rep_tab + (size_t)cat * s.rep_rows * 4;
-      na.gcnt = s.rep_cnt + (size_t)cat * s.rep_rows;
-    }
-    n_wg = prune_nuc_grid(na);
-    {  // fused final combine (see the codon branch below): the small-shard instantiation of the 4-state kernel carries it
-      const char *fuse_env = getenv("HYPHY_HIP_FUSED_REDUCE");
-      if (!(fuse_env && atoi(fuse_env) == 0) && p->mode == 0 && reduce && n_ops > 0 && !floor_log && n_cat_batch <= 1 && !p->export_sites &&
-          (use_gen ? p->nucgen_small : prune_nuc_fuses_reduce(na, have_folded))) {
-        double *rec = s.d_hout ? s.d_hout : s.out;
-        fused_reduce = true;
-        na.red_out = d_logl_out ? d_logl_out : rec;
-        na.red_rec = d_logl_out ? s.out + 1 : rec + 1;
-        na.red_status = d_logl_out ? nullptr : s.status;
-        na.red_seq = next_seq(s, !d_logl_out);
-        na.red_done = s.wg_flag + (size_t)p->C * s.wg_cap + 3;  // (the spare words behind the flags; zeroed at creation)
-      }
-    }
-    if (!(use_gen && nucgen_launch(p->nucgen_key, na, s.stream, p->nucgen_small, (int)p->B, have_folded ? &folded_expm : nullptr))) {
-      if (use_gen) return fail("internal: the generated 4-state kernel could not be launched");
-      launch_prune_nuc(na, s.stream, have_folded ? &folded_expm : nullptr);
-    }
-    s.last_nucgen = use_gen;
-    if (have_folded && folded_expm.templates && d_logl_out && s.coeff_slot >= 0) {  // (the ring slot is read by THIS launch)
-      HIPCHK(hipEventRecord(s.coeff_ev[s.coeff_slot], s.stream));
-      s.coeff_busy[s.coeff_slot] = true;
-    }
-  } else {
-    if (p->rr_active && p->chain && s.twins_dirty) refresh_twins(p, s);
-    PruneArgs pa = base_prune_args(p, s, cat, n_cat_batch);
-    pa.ops = s.ops;
-    pa.n_ops = n_ops;
-    pa.prog = s.prog;
-    pa.site_lik = site_lik;
-    pa.site_cnt = site_cnt;
-    pa.timeline = nullptr;
-    pa.ablate = 0;
-    if (const char *ab = getenv("HYPHY_HIP_ABLATE")) pa.ablate = atoi(ab);
-    const char *tl_path = getenv("HYPHY_HIP_TIMELINE");
-    const bool tl_wave = p->variant == 1;  // wave-per-tile kernel: one record of 8 words per wave of the grid
-    const size_t tl_waves = (size_t)s.ntiles * std::max(1, n_cat_batch) * std::max<size_t>(1, p->programs.size());
-    const size_t tl_n = tl_wave ? tl_waves * 24 : (size_t)kTraceWG * p->NW * std::max(1, n_ops) * 4;
-    if (tl_path && n_ops > 0 && s.T == 1) {
-      HIPCHK(pool_malloc((void **)&pa.timeline, tl_n * sizeof(long long)));
-      HIPCHK(hipMemsetAsync(pa.timeline, 0, tl_n * sizeof(long long), s.stream));
-    }
-    n_wg = prune_mfma_grid(pa);
-    pa.frag_ctr = s.frag_ctr;
-    pa.hand_cnt = s.hand_cnt;
-    pa.n_prog_total = p->chain ? (int)p->I : (int)p->programs.size();
-    pa.chain = p->chain ? 1 : 0;
-    pa.jn = s.jn;
-    pa.deposits = s.deposits;
-    pa.cs_deposits = s.deposits_class_stride;
-    // Fused final combine: the launch that finalises the roots also sums the per-tile partial sums and publishes the record —
-    // the last root-finalising wave does what wg_reduce_kernel would do in a launch of its own (prune.hip: publish_partial).
-    // Saves 1.5-3 us per evaluation of a small shard (below two tiles per CU; 64 x 1 250: 69.1 -> 67.7 us, 32 x 5 000: 79.8 ->
-    // 77.0); at the headline size the gain shrinks to ~1 us while the pruning kernel's own duration grows by the 3-4 us of the
-    // serial tail, so larger shards keep the separate kernel.  HYPHY_HIP_FUSED_REDUCE=0/1 forces either.
-    const char *fuse_env = getenv("HYPHY_HIP_FUSED_REDUCE");
-    const bool walk = trunk_walk_applies(p, s) && !pa.timeline && n_ops > 0;  // (repeats.hip: the trunk as one row-split walk per tile)
-    const bool fuse_on = fuse_env ? atoi(fuse_env) != 0 : s.ntiles <= 2 * s.cus;  // (the walk at the headline: 90.0 / 89.8 us fused, 88.3 / 89.5 not)
-    if (fuse_on && reduce && n_ops > 0 && !floor_log && n_cat_batch <= 1 && !pa.timeline && !p->export_sites &&
-        (walk ? (trunk_walk_fuses_reduce(p) && !getenv("HYPHY_HIP_WALK_TIMELINE")) : prune_fuses_reduce(pa))) {
-      double *rec = s.d_hout ? s.d_hout : s.out;
-      fused_reduce = true;
-      pa.red_out = d_logl_out ? d_logl_out : rec;
-      pa.red_rec = d_logl_out ? s.out + 1 : rec + 1;
-      pa.red_status = d_logl_out ? nullptr : s.status;
-      pa.red_seq = next_seq(s, !d_logl_out);
-      pa.red_done = s.frag_ctr + (size_t)p->C * (p->I + 2) * s.ntiles - 1;  // (a word of the arrival counters no schedule indexes; zero between launches)
-      pa.red_n = n_wg;
-    }
-    double *const red_out = pa.red_out;
-    if (walk) {
-      // the trunk of a class-compressed partition, lazy full pass: one row-split walk per tile instead of the schedule
-      pa.red_out = red_out;
-      if (launch_trunk_walk(p, s, cat, n_cat_batch, true, &pa)) return -1;
-      s.last_walk = true;
-    } else {
-    s.last_walk = false;
-    for (size_t lv = 0; lv < p->levels.size(); lv++) {  // one launch per level of subtree fragments
-      pa.prog = s.prog + p->levels[lv].first;
-      pa.n_prog = p->levels[lv].count;
-      pa.do_root = (lv + 1 == p->levels.size()) ? 1 : 0;
-      pa.red_out = pa.do_root ? red_out : nullptr;
-      if (launch_prune_mfma(pa, s.stream)) return fail("internal: no pruning kernel for this launch form (variant " + std::to_string(p->variant) + ", " + std::to_string(p->NW) + " row blocks)");
-    }
-    }
-    if (pa.timeline) {  // tracing only: synchronous dump of the per-entry s_memtime stamps
-      std::vector<long long> h(tl_n);
-      HIPCHK(hipStreamSynchronize(s.stream));
-      HIPCHK(hipMemcpy(h.data(), pa.timeline, tl_n * sizeof(long long), hipMemcpyDeviceToHost));
-      pool_free_sync(pa.timeline);
-      if (tl_wave) {
-        if (FILE *f = fopen(tl_path, "w")) {
-          fprintf(f, "# wave t_start t_prologue t_program t_end levels how hw_id xcc_id   (100 MHz ticks; grid = %s)  then shader cycles: "
-                     "16 phase buckets (prune.hip HYPHY_TR)\n",
-                  p->chain ? "tiles x classes x sources" : "programs x classes x tiles");
-          for (size_t k = 0; k < tl_waves; k++) {
-            const long long *r = &h[k * 24];
-            fprintf(f, "%zu", k);
-            for (int i = 0; i < 24; i++) fprintf(f, " %lld", r[i]);
-            fprintf(f, "\n");
-          }
-          fclose(f);
-        }
-      } else if (FILE *f = fopen(tl_path, "w")) {
-        fprintf(f, "# wg wave entry flags t_start t_compute_done t_after_barrier t_finalised\n");
-        for (int b = 0; b < kTraceWG; b++)
-          for (int w = 0; w < p->NW; w++)
-            for (int o = 0; o < n_ops; o++) {
-              const long long *r = &h[(((size_t)b * p->NW + w) * n_ops + o) * 4];
-              fprintf(f, "%d %d %d %d %lld %lld %lld %lld\n", b, w, o, o < (int)p->ops_host.size() ? (p->ops_host[o].x & 0xff) : 0, r[0], r[1], r[2], r[3]);
-            }
-        fclose(f);
-      }
-    }
-  }
+  return 0;
+}
+int EvalCtx::stage_stamps_close() {
   tr.lap("launch_prune");
   if (stamp) {
     HIPCHK(hipEventRecord(s.ring[ring_slot + 1], s.stream));
     s.ring_count++;
   }
   if (p->all_timings) HIPCHK(hipEventRecord(s.ev[2], s.stream));
-  s.exported = 0;
-  if (p->export_sites && reduce && !floor_log && n_cat_batch <= 1 && s.d_export) {
-    // per-pattern results for the caller, in ITS order, into host-mapped memory — in front of the kernel that publishes the result
-    // record, so that the record's sequence word says they have landed too
-    launch_site_export(site_lik, site_cnt, s.d_inv, (int)s.S, (p->export_sites & 1) ? s.d_export : nullptr,
-                       (p->export_sites & 2) ? reinterpret_cast<long long *>(s.d_export + s.S) : nullptr, s.stream);
-    s.exported = p->export_sites;
+  return 0;
+}
+
+// Fused final combine: the launch that finalises the roots also sums the per-tile partial sums and publishes the record —
+// the last root-finalising wave does what wg_reduce_kernel would do in a launch of its own (prune.hip: publish_partial); red_done: its zeroed arrival word.
+template <typename Args>
+void EvalCtx::wire_fused_combine(Args &a, int *red_done) {
+  double *const d_logl_out = rq.d_logl_out, *rec = s.d_hout ? s.d_hout : s.out;
+  fused_reduce = true;
+  a.red_out = d_logl_out ? d_logl_out : rec, a.red_rec = d_logl_out ? s.out + 1 : rec + 1;
+  a.red_status = d_logl_out ? nullptr : s.status;
+  a.red_seq = next_seq(s, !d_logl_out), a.red_done = red_done;
+}
+// what both pruning stages ask before they fuse (HYPHY_HIP_FUSED_REDUCE is theirs to read: its default differs)
+bool EvalCtx::fused_combine_allowed() const {
+  return rq.reduce && n_ops > 0 && !rq.floor_log && n_cat_batch <= 1 && !p->export_sites;
+}
+
+int EvalCtx::stage_prune_nuc() {
+  const int64_t B = p->B;
+  NucArgs na;
+  na.ops = s.ops + (p->programs.empty() ? 0 : p->programs[0].off), na.n_ops = n_ops;
+  na.S_pad = s.S_pad, na.L = (int)p->L, na.root_inode = (int)p->I - 1;
+  na.P = s.Prow + (size_t)cat * B * 16, na.PT = s.Prow + ((size_t)p->C * B + (size_t)cat * B) * 16;
+  na.codes = s.codes, na.ambig = s.ambig, na.pi = s.pi, na.freq = s.freq, na.pin = s.pin;
+  na.pin_leaf = (p->pin_node >= 0 && p->pin_node < p->L) ? (int)p->pin_node : -1;
+  na.pin_inode = p->pin_node >= p->L ? (int)(p->pin_node - p->L) : -1;
+  na.partials = s.partials + (size_t)cat * s.partial_stride, na.counts = s.counts + (size_t)cat * p->I * s.S_pad;
+  na.site_lik = site_lik(), na.site_cnt = site_cnt();
+  na.wg_sum = s.wg_sum, na.wg_cnt = s.wg_cnt, na.wg_flag = s.wg_flag;
+  if (p->mode == 1) {  // the trunk of a class-compressed partition (repeats.hip): generalised leaves, one leaf per entry
+    const hyphy_hip_partition::View &v = p->vw();
+    na.L = v.L, na.root_inode = v.I - 1;
+    na.codes = s.rep_codes_tile;   // (4 states: row-major [view leaf][pattern])
+    na.PT = nullptr;               // (prune_nuc_kernel)
+    na.leaf_tab = s.rep_leaf;
+    na.gtab = s.rep_tab + (size_t)cat * s.rep_rows * 4, na.gcnt = s.rep_cnt + (size_t)cat * s.rep_rows;
   }
-  if (reduce && !fused_reduce) {
+  n_wg = prune_nuc_grid(na);
+  const char *fuse_env = getenv("HYPHY_HIP_FUSED_REDUCE");
+  if (!(fuse_env && atoi(fuse_env) == 0) && p->mode == 0 && fused_combine_allowed() &&
+      (use_gen ? p->nucgen_small : prune_nuc_fuses_reduce(na, have_folded)))
+    wire_fused_combine(na, s.wg_flag + (size_t)p->C * s.wg_cap + 3);  // (the spare words behind the flags; zeroed at creation)
+  const ExpmArgs *folded = have_folded ? &folded_expm : nullptr;
+  if (!(use_gen && nucgen_launch(p->nucgen_key, na, s.stream, p->nucgen_small, (int)p->B, folded))) {
+    if (use_gen) return fail("internal: the generated 4-state kernel could not be launched");
+    launch_prune_nuc(na, s.stream, folded);
+  }
+  s.last_nucgen = use_gen;
+  if (folded && folded->templates && guard_coeff_slot()) return -1;  // (the ring slot is read by THIS launch)
+  return 0;
+}
+
+// HYPHY_HIP_TIMELINE (tracing only): synchronous dump of the s_memtime stamps of the pruning launches, in the form of the kernel that ran
+struct Timeline {
+  const char *path;
+  bool per_wave;
+  size_t waves, n;  // records of the per-wave form; words in all
+  long long *buf;
+};
+int EvalCtx::dump_timeline(const Timeline &tl) {
+  std::vector<long long> h(tl.n);
+  HIPCHK(hipStreamSynchronize(s.stream));
+  HIPCHK(hipMemcpy(h.data(), tl.buf, tl.n * sizeof(long long), hipMemcpyDeviceToHost));
+  pool_free_sync(tl.buf);
+  FILE *f = fopen(tl.path, "w");
+  if (!f) return 0;
+  if (tl.per_wave) {
+    fprintf(f, "# wave t_start t_prologue t_program t_end levels how hw_id xcc_id   (100 MHz ticks; grid = %s)  then shader cycles: "
+               "16 phase buckets (prune.hip HYPHY_TR)\n",
+            p->chain ? "tiles x classes x sources" : "programs x classes x tiles");
+    for (size_t k = 0; k < tl.waves; k++) {
+      const long long *r = &h[k * 24];
+      fprintf(f, "%zu", k);
+      for (int i = 0; i < 24; i++) fprintf(f, " %lld", r[i]);
+      fprintf(f, "\n");
+    }
+  } else {
+    fprintf(f, "# wg wave entry flags t_start t_compute_done t_after_barrier t_finalised\n");
+    for (int b = 0; b < kTraceWG; b++)
+      for (int w = 0; w < p->NW; w++)
+        for (int o = 0; o < n_ops; o++) {
+          const long long *r = &h[(((size_t)b * p->NW + w) * n_ops + o) * 4];
+          fprintf(f, "%d %d %d %d %lld %lld %lld %lld\n", b, w, o, o < (int)p->ops_host.size() ? (p->ops_host[o].x & 0xff) : 0, r[0], r[1], r[2], r[3]);
+        }
+  }
+  fclose(f);
+  return 0;
+}
+
+int EvalCtx::stage_prune_mfma() {
+  PruneArgs pa = prune_args_current(p, s, cat, n_cat_batch);
+  const size_t tl_waves = (size_t)s.ntiles * std::max(1, n_cat_batch) * std::max<size_t>(1, p->programs.size());
+  Timeline tl{getenv("HYPHY_HIP_TIMELINE"), p->variant == 1, tl_waves,
+              p->variant == 1 ? tl_waves * 24 : (size_t)kTraceWG * p->NW * std::max(1, n_ops) * 4, nullptr};
+  if (tl.path && n_ops > 0 && s.T == 1) {
+    HIPCHK(pool_malloc((void **)&tl.buf, tl.n * sizeof(long long)));
+    HIPCHK(hipMemsetAsync(tl.buf, 0, tl.n * sizeof(long long), s.stream));
+    pa.timeline = tl.buf;
+  }
+  n_wg = prune_mfma_grid(pa);
+  // The fused combine saves 1.5-3 us per evaluation of a small shard (below two tiles per CU; 64 x 1 250: 69.1 -> 67.7 us, 32 x 5 000:
+  // 79.8 -> 77.0); at the headline size the gain shrinks to ~1 us while the pruning kernel's own duration grows by the 3-4 us of the
+  // serial tail, so larger shards keep the separate kernel.  HYPHY_HIP_FUSED_REDUCE=0/1 forces either.
+  const char *fuse_env = getenv("HYPHY_HIP_FUSED_REDUCE");
+  const bool walk = trunk_walk_applies(p, s) && !pa.timeline && n_ops > 0;  // (the trunk as one row-split walk per tile, repeats.hip)
+  const bool fuse_on = fuse_env ? atoi(fuse_env) != 0 : s.ntiles <= 2 * s.cus;  // (the walk at the headline: 90.0 / 89.8 us fused, 88.3 / 89.5 not)
+  if (fuse_on && fused_combine_allowed() && !pa.timeline &&
+      (walk ? (trunk_walk_fuses_reduce(p) && !getenv("HYPHY_HIP_WALK_TIMELINE")) : prune_fuses_reduce(pa))) {
+    wire_fused_combine(pa, s.frag_ctr + (size_t)p->C * (p->I + 2) * s.ntiles - 1);  // (a word of the arrival counters no schedule indexes; zero between launches)
+    pa.red_n = n_wg;
+  }
+  if (launch_prune_current(p, s, cat, n_cat_batch, &pa, walk)) return -1;
+  return pa.timeline ? dump_timeline(tl) : 0;
+}
+
+int EvalCtx::stage_export() {
+  s.exported = 0;
+  if (!(p->export_sites && rq.reduce && !rq.floor_log && n_cat_batch <= 1 && s.d_export)) return 0;
+  // per-pattern results for the caller, in ITS order, into host-mapped memory — in front of the kernel that publishes the result
+  // record, so that the record's sequence word says they have landed too
+  launch_site_export(site_lik(), site_cnt(), s.d_inv, (int)s.S, (p->export_sites & 1) ? s.d_export : nullptr,
+                     (p->export_sites & 2) ? reinterpret_cast<long long *>(s.d_export + s.S) : nullptr, s.stream);
+  s.exported = p->export_sites;
+  return 0;
+}
+
+int EvalCtx::stage_reduce() {
+  if (rq.reduce && !fused_reduce) {
     // synchronous entry points: the result record goes straight to host-mapped pinned memory (a
     // posted PCIe write from the kernel) — an SDMA device-to-host copy after the kernels costs far more
-    double *rec = s.d_hout ? s.d_hout : s.out;
+    double *const d_logl_out = rq.d_logl_out, *rec = s.d_hout ? s.d_hout : s.out;
     double *o0 = d_logl_out ? d_logl_out : rec, *o1 = d_logl_out ? s.out + 1 : rec + 1;
     const int *st = d_logl_out ? nullptr : s.status;
     const double seq = next_seq(s, !d_logl_out);
-    if (n_ops > 0 && !floor_log)  // the pruning kernel left per-workgroup partial sums
+    if (n_ops > 0 && !rq.floor_log)  // the pruning kernel left per-workgroup partial sums
       launch_wg_reduce(s.wg_sum, s.wg_cnt, s.wg_flag, n_wg, o0, o1, st, s.stream, seq);
     else  // nothing was recomputed (or category mode): reduce the stored per-pattern values
-      launch_site_reduce(site_lik, site_cnt, s.freq, s.S_pad, floor_log ? 1 : 0, o0, o1, st, s.stream, seq);
+      launch_site_reduce(site_lik(), site_cnt(), s.freq, s.S_pad, rq.floor_log ? 1 : 0, o0, o1, st, s.stream, seq);
   }
   if (p->all_timings) HIPCHK(hipEventRecord(s.ev[3], s.stream));
   HIPCHK(hipGetLastError());
   tr.lap("reduce+events");
   return 0;
+}
+
+int EvalCtx::enqueue_eval() {
+  if (stage_schedule() || stage_pi()) return -1;
+  stage_gen_decision();
+  if (rq.n_q > 0) {
+    if (stage_slot_table()) return -1;
+    if (rq.mix ? stage_expm_mixture() : stage_expm_plain()) return -1;
+  }
+  if (stage_stamps_open()) return -1;
+  if (p->mode == 1 && rep_launch(p, s, cat)) return -1;  // lower phase: the class tables this pass recomputes
+  if (p->nuc ? stage_prune_nuc() : stage_prune_mfma()) return -1;
+  if (stage_stamps_close()) return -1;
+  return stage_export() || stage_reduce() ? -1 : 0;
 }
 
 bool same_update(const hyphy_hip_partition *p, const int64_t *u, int64_t n, bool full) {
@@ -768,21 +739,6 @@ int begin_site_export(hyphy_hip_partition *p, bool want_lik, bool want_cnt) {
   p->export_sites = (want_lik ? 1 : 0) | (want_cnt ? 2 : 0);
   return 0;
 }
-int gather_sites(hyphy_hip_partition *p, int cat, double *site_lik_out, int64_t *site_scaler_out, bool mixed);
-// ... and collects them behind the wait for the result record (whatever was not exported comes through gather_sites)
-int finish_sites(hyphy_hip_partition *p, int cat, double *site_lik_out, int64_t *site_scaler_out) {
-  p->export_sites = 0;
-  if (!site_lik_out && !site_scaler_out) return 0;
-  Shard &s = p->shards[0];
-  const int have = p->shards.size() == 1 ? s.exported : 0;
-  s.exported = 0;
-  const bool lik_ok = !site_lik_out || (have & 1), cnt_ok = !site_scaler_out || (have & 2);
-  if (!(lik_ok && cnt_ok)) return gather_sites(p, cat, site_lik_out, site_scaler_out, false);
-  if (site_lik_out) memcpy(site_lik_out, s.h_export, (size_t)s.S * sizeof(double));
-  if (site_scaler_out) memcpy(site_scaler_out, s.h_export + s.S, (size_t)s.S * sizeof(int64_t));
-  return 0;
-}
-
 int gather_sites(hyphy_hip_partition *p, int cat, double *site_lik_out, int64_t *site_scaler_out, bool mixed) {
   for (Shard &s : p->shards) {
     HIPCHK(hipSetDevice(s.device));
@@ -803,6 +759,51 @@ int gather_sites(hyphy_hip_partition *p, int cat, double *site_lik_out, int64_t 
     }
     if (site_scaler_out)
       for (int64_t k = 0; k < s.S; k++) site_scaler_out[caller_pattern(p, s.s0 + k)] = hc[k];
+  }
+  return 0;
+}
+
+// ... (begin_site_export) and collects them behind the wait for the result record (whatever was not exported comes through gather_sites)
+int finish_sites(hyphy_hip_partition *p, int cat, double *site_lik_out, int64_t *site_scaler_out) {
+  p->export_sites = 0;
+  if (!site_lik_out && !site_scaler_out) return 0;
+  Shard &s = p->shards[0];
+  const int have = p->shards.size() == 1 ? s.exported : 0;
+  s.exported = 0;
+  const bool lik_ok = !site_lik_out || (have & 1), cnt_ok = !site_scaler_out || (have & 2);
+  if (!(lik_ok && cnt_ok)) return gather_sites(p, cat, site_lik_out, site_scaler_out, false);
+  if (site_lik_out) memcpy(site_lik_out, s.h_export, (size_t)s.S * sizeof(double));
+  if (site_scaler_out) memcpy(site_scaler_out, s.h_export + s.S, (size_t)s.S * sizeof(int64_t));
+  return 0;
+}
+
+// The tail of a synchronous entry point: wait for every shard's record, combine, hand out per-pattern values — each in the caller's way:
+enum TailCombine { kCombineShards, kCombineHost };  // combine_shards (comm.hip) as HYPHY_HIP_COMBINE says / the host's sum whatever it says
+enum TailTimings { kNoTimings, kRecordTimings };    // record_timings behind the wait
+enum TailSites { kSitesExported, kSitesGathered, kSitesGatheredMixed };  // finish_sites (export, else copies) / copies of the class's values / of the mixed ones
+int result_tail(hyphy_hip_partition *p, int cat, TailCombine comb, TailTimings tim, TailSites sites, double *logl_out,
+                double *site_lik_out, int64_t *site_scaler_out) {
+  if (collect_status(p)) return -1;
+  if (tim == kRecordTimings) record_timings(p);
+  if (combine_shards(p, logl_out, comb == kCombineShards)) return -1;
+  if (sites == kSitesExported) return finish_sites(p, cat, site_lik_out, site_scaler_out);
+  if (site_lik_out || site_scaler_out) return gather_sites(p, cat, site_lik_out, site_scaler_out, sites == kSitesGatheredMixed);
+  return 0;
+}
+
+// Category mode behind the per-class passes: weights to the device (`always`, or when they changed), mix the classes, reduce the mix
+int mix_and_reduce_categories(hyphy_hip_partition *p, const double *weights, bool always) {
+  const bool w_changed = always || p->cached_weights.size() != (size_t)p->C || memcmp(p->cached_weights.data(), weights, p->C * sizeof(double));
+  if (w_changed) p->cached_weights.assign(weights, weights + p->C);
+  for (Shard &s : p->shards) {
+    HIPCHK(hipSetDevice(s.device));
+    if (w_changed && upload_small(s, weights, (size_t)p->C, s.weights)) {
+      if (!always) p->cached_weights.clear();  // (the always-uploading entry point never cleared the cache on this path: kept)
+      return -1;
+    }
+    launch_mix_categories(s.site_lik, s.site_cnt, s.weights, (int)p->C, s.S_pad, s.mixed_lik, s.mixed_cnt, s.stream);
+    double *rec = s.d_hout ? s.d_hout : s.out;
+    launch_site_reduce(s.mixed_lik, s.mixed_cnt, s.freq, s.S_pad, 1, rec, rec + 1, s.status, s.stream, next_seq(s, rec == s.d_hout));
   }
   return 0;
 }
@@ -1175,8 +1176,9 @@ int ensure_resident(hyphy_hip_partition *p, int64_t cat) {
   for (int64_t k = 0; k < p->B; k++) all[k] = k;
   const std::vector<double> pi = p->cached_pi;
   const std::vector<char> lf = p->last_full;
-  if (eval_common(p, cat, all.data(), p->B, nullptr, 0, nullptr, false, 0, pi.data(), nullptr, true, false, false, true))
-    return -1;
+  EvalRequest rq = request_of(cat, UpdateList{all.data(), p->B}, MatrixList{nullptr, 0}, pi.data());  // a persisting full pass over the resident matrices
+  rq.reduce = true, rq.floor_log = false, rq.force_persist = true;
+  if (eval_common(p, rq)) return -1;
   p->last_full = lf;  // (an internal pass: the caller's own sequence of evaluations is what the policy looks at)
   return collect_status(p);
 }
@@ -1194,10 +1196,12 @@ int finish_pending_async(hyphy_hip_partition *p) {
   return 0;
 }
 
-int eval_common(hyphy_hip_partition *p, int64_t cat, const int64_t *update_nodes, int64_t n_update,
-                       const int64_t *q_nodes, int64_t n_q, const double *q, bool q_on_device, int q_is_probability,
-                       const double *root_freqs, double *d_logl_out, bool reduce, bool floor_log, bool batch,
-                       bool force_persist, const MixSpec *mix) {
+int eval_common(hyphy_hip_partition *p, const EvalRequest &rq) {
+  int64_t cat = rq.cat, n_update = rq.n_update;  // (rewritten below: class batching, new root frequencies)
+  const int64_t *update_nodes = rq.update_nodes, *const q_nodes = rq.q_nodes;
+  const int64_t n_q = rq.n_q;
+  const double *const root_freqs = rq.root_freqs;
+  const bool batch = rq.batch, force_persist = rq.force_persist;
   if (!p) return fail("partition == NULL");
   if (cat < 0) cat = 0;
   if (cat >= p->C) return fail("rate class out of range");
@@ -1212,7 +1216,7 @@ int eval_common(hyphy_hip_partition *p, int64_t cat, const int64_t *update_nodes
   if (batch) std::fill(p->bc_node.begin(), p->bc_node.end(), -1);
   else if (cat >= 0 && cat < (int64_t)p->bc_node.size()) p->bc_node[cat] = -1;
   if (!root_freqs) return fail("root_freqs == NULL");
-  if ((n_update > 0 && !update_nodes) || (n_q > 0 && (!q_nodes || !q))) return fail("null node / matrix list");
+  if ((n_update > 0 && !update_nodes) || (n_q > 0 && (!q_nodes || (rq.q_source != QSource::OwnStaged && !rq.q)))) return fail("null node / matrix list");
   if (n_q > p->B) return fail("more matrices than branches");
   if (!p->initialized[cat] && n_q < p->B)
     return fail("first evaluation of a rate class must supply all L+I-1 transition matrices");
@@ -1277,9 +1281,9 @@ int eval_common(hyphy_hip_partition *p, int64_t cat, const int64_t *update_nodes
   bool slots_changed = cs.size() != (size_t)n_q || (n_q > 0 && memcmp(cs.data(), q_nodes, n_q * sizeof(int64_t)));
   if (slots_changed) cs.assign(q_nodes, q_nodes + n_q);
   p->slots_batch_mode = batch ? 1 : 0;
-  for (Shard &s : p->shards)
-    if (enqueue_eval(p, s, (int)cat, batch ? (int)p->C : 1, changed, pi_changed, slots_changed, q_nodes, n_q, q,
-                     q_on_device, q_is_probability, root_freqs, d_logl_out, reduce, floor_log, mix)) {
+  for (Shard &s : p->shards) {
+    EvalCtx ctx{p, s, (int)cat, batch ? (int)p->C : 1, changed, pi_changed, slots_changed, rq};
+    if (ctx.enqueue_eval()) {
       // some shard may hold a stale schedule / slot table / frequency vector now: rebuild everything next time
       p->cached_valid = 0;
       p->cached_pi.clear();
@@ -1288,6 +1292,7 @@ int eval_common(hyphy_hip_partition *p, int64_t cat, const int64_t *update_nodes
       p->initialized[cat] = 0;
       return -1;
     }
+  }
   std::vector<char> &res_here = p->mode == 1 ? p->rep_resident : p->resident, &res_other = p->mode == 1 ? p->resident : p->rep_resident;
   if (batch)
     for (int64_t c = 0; c < p->C; c++) {
@@ -1336,19 +1341,35 @@ int hyphy_hip_evaluate(hyphy_hip_partition *p, int64_t cat, const int64_t *updat
                        const int64_t *q_nodes, int64_t n_q, const double *q_dense, int q_is_probability,
                        const double *root_freqs, double *logl_out, double *site_lik_out, int64_t *site_scaler_out) {
   if (p && begin_site_export(p, site_lik_out != nullptr, site_scaler_out != nullptr)) return -1;
-  if (eval_common(p, cat, update_nodes, n_update, q_nodes, n_q, q_dense, false, q_is_probability, root_freqs, nullptr,
-                  true, false)) {
+  EvalRequest rq = request_of(cat, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::HostDense, rq.q = q_dense, rq.q_is_probability = q_is_probability;
+  rq.reduce = true, rq.floor_log = false;
+  if (eval_common(p, rq)) {
     if (p) p->export_sites = 0;
     return -1;
   }
   p->export_sites = 0;
-  std::vector<double> parts;
-  if (collect_status(p)) return -1;
-  for (Shard &s : p->shards) parts.push_back(s.h_out[0]);
-  record_timings(p);
-  if (combine_shards(p, logl_out)) return -1;
-  return finish_sites(p, cat < 0 ? 0 : (int)cat, site_lik_out, site_scaler_out);
+  return result_tail(p, cat < 0 ? 0 : (int)cat, kCombineShards, kRecordTimings, kSitesExported, logl_out, site_lik_out, site_scaler_out);
 }
+
+}  // extern "C"
+
+// the two mixture entry points from the component counts onwards (`rq`: the lists and the matrix source)
+static int evaluate_mixture_common(hyphy_hip_partition *p, EvalRequest rq, const int64_t *n_components, const double *weights,
+                                   double *logl_out, double *site_lik_out, int64_t *site_scaler_out) {
+  MixSpec mix{n_components, weights, 0};
+  for (int64_t k = 0; k < rq.n_q; k++) {
+    if (n_components[k] < 1 || n_components[k] > kMixRows) return fail("mixture evaluation: 1..16 components per branch");
+    mix.n_tot += n_components[k];
+  }
+  rq.reduce = true, rq.floor_log = false;
+  rq.mix = rq.n_q > 0 ? &mix : nullptr;
+  if (eval_common(p, rq)) return -1;
+  // (unlike hyphy_hip_evaluate: the host's sum whatever HYPHY_HIP_COMBINE says, and copies instead of the export)
+  return result_tail(p, rq.cat < 0 ? 0 : (int)rq.cat, kCombineHost, kRecordTimings, kSitesGathered, logl_out, site_lik_out, site_scaler_out);
+}
+
+extern "C" {
 
 /* Branch-site mixtures on every branch (the reference's "explicit form" models: BUSTED / BS-REL whole-alignment
  * evaluation): P_b = sum_m weights exp(Q_bm), formed on the device. */
@@ -1358,21 +1379,9 @@ int hyphy_hip_evaluate_mixture(hyphy_hip_partition *p, int64_t cat, const int64_
                                int64_t *site_scaler_out) {
   if (!p) return fail("partition == NULL");
   if (n_q > 0 && (!n_components || !weights || !q_dense)) return fail("mixture evaluation: null argument");
-  MixSpec mix{n_components, weights, 0};
-  for (int64_t k = 0; k < n_q; k++) {
-    if (n_components[k] < 1 || n_components[k] > 16) return fail("mixture evaluation: 1..16 components per branch");
-    mix.n_tot += n_components[k];
-  }
-  if (eval_common(p, cat, update_nodes, n_update, q_nodes, n_q, q_dense, false, 0, root_freqs, nullptr, true, false, false, false,
-                  n_q > 0 ? &mix : nullptr))
-    return -1;
-  if (collect_status(p)) return -1;
-  std::vector<double> parts;
-  for (Shard &s : p->shards) parts.push_back(s.h_out[0]);
-  record_timings(p);
-  if (logl_out) *logl_out = combine(parts);
-  if (site_lik_out || site_scaler_out) return gather_sites(p, cat < 0 ? 0 : (int)cat, site_lik_out, site_scaler_out, false);
-  return 0;
+  EvalRequest rq = request_of(cat, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::HostDense, rq.q = q_dense;
+  return evaluate_mixture_common(p, rq, n_components, weights, logl_out, site_lik_out, site_scaler_out);
 }
 
 /* The same with the component rate matrices formed ON THE DEVICE (r04): Q_(b,m) = sum_k x_(b,m),k T_k over the templates of
@@ -1386,20 +1395,9 @@ int hyphy_hip_evaluate_mixture_built(hyphy_hip_partition *p, int64_t cat, const 
   if (!p->K) return fail("evaluate_mixture_built: templates not set");
   if (n_q > 0 && (!n_components || !weights)) return fail("mixture evaluation: null argument");
   if (n_q <= 0) return fail("evaluate_mixture_built: no matrices (use hyphy_hip_evaluate_built for a pure re-evaluation)");
-  MixSpec mix{n_components, weights, 0};
-  for (int64_t k = 0; k < n_q; k++) {
-    if (n_components[k] < 1 || n_components[k] > kMixRows) return fail("mixture evaluation: 1..16 components per branch");
-    mix.n_tot += n_components[k];
-  }
-  if (eval_common(p, cat, update_nodes, n_update, q_nodes, n_q, &kOwnQBuffer, true, 0, root_freqs, nullptr, true, false, false, false, &mix))
-    return -1;
-  if (collect_status(p)) return -1;
-  std::vector<double> parts;
-  for (Shard &s : p->shards) parts.push_back(s.h_out[0]);
-  record_timings(p);
-  if (logl_out) *logl_out = combine(parts);
-  if (site_lik_out || site_scaler_out) return gather_sites(p, cat < 0 ? 0 : (int)cat, site_lik_out, site_scaler_out, false);
-  return 0;
+  EvalRequest rq = request_of(cat, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::OwnStaged;
+  return evaluate_mixture_common(p, rq, n_components, weights, logl_out, site_lik_out, site_scaler_out);
 }
 
 /* Asynchronous pair (partitions of one likelihood function on different devices / streams overlap: the host enqueues
@@ -1426,9 +1424,10 @@ int hyphy_hip_evaluate_async(hyphy_hip_partition *p, int64_t cat, const int64_t 
     // (the previous asynchronous evaluation was collected or synchronised above: the staging buffer is free)
     memcpy(p->h_qstage, q_dense, n * sizeof(double));
   }
-  if (eval_common(p, cat, update_nodes, n_update, q_nodes, n_q, n > 0 ? p->h_qstage : nullptr, false, q_is_probability,
-                  root_freqs, nullptr, true, false))
-    return -1;
+  EvalRequest rq = request_of(cat, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::HostDense, rq.q = n > 0 ? p->h_qstage : nullptr, rq.q_is_probability = q_is_probability;
+  rq.reduce = true, rq.floor_log = false;
+  if (eval_common(p, rq)) return -1;
   p->async_pending = true;
   p->async_cat = cat < 0 ? 0 : cat;
   return 0;
@@ -1438,13 +1437,7 @@ int hyphy_hip_collect(hyphy_hip_partition *p, double *logl_out, double *site_lik
   if (!p) return fail("partition == NULL");
   if (!p->async_pending) return fail("collect: no asynchronous evaluation pending");
   p->async_pending = false;
-  if (collect_status(p)) return -1;
-  std::vector<double> parts;
-  for (Shard &s : p->shards) parts.push_back(s.h_out[0]);
-  record_timings(p);
-  if (logl_out) *logl_out = combine(parts);
-  if (site_lik_out || site_scaler_out) return gather_sites(p, (int)p->async_cat, site_lik_out, site_scaler_out, false);
-  return 0;
+  return result_tail(p, (int)p->async_cat, kCombineHost, kRecordTimings, kSitesGathered, logl_out, site_lik_out, site_scaler_out);
 }
 
 int hyphy_hip_evaluate_built_sites(hyphy_hip_partition *p, int64_t cat, const int64_t *update_nodes, int64_t n_update,
@@ -1462,9 +1455,10 @@ int hyphy_hip_evaluate_built(hyphy_hip_partition *p, int64_t cat, const int64_t 
                              const int64_t *q_nodes, int64_t n_q, const double *root_freqs, double *logl_out) {
   if (!p) return fail("partition == NULL");
   if (!p->K) return fail("evaluate_built: templates not set");
-  // q = each shard's own Q buffer (filled / staged by build_q on every shard)
-  if (eval_common(p, cat, update_nodes, n_update, q_nodes, n_q, &kOwnQBuffer, true, 0, root_freqs, nullptr, true, false))
-    return -1;
+  EvalRequest rq = request_of(cat, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::OwnStaged;  // (filled / staged by build_q on every shard)
+  rq.reduce = true, rq.floor_log = false;
+  if (eval_common(p, rq)) return -1;
   Trace tr("evaluate_built");
   if (collect_status(p)) return -1;
   tr.lap("wait");
@@ -1478,8 +1472,11 @@ int hyphy_hip_evaluate_device(hyphy_hip_partition *p, int64_t cat, const int64_t
   if (p->shards.size() != 1) return fail("evaluate_device needs a single-device partition");
   Trace tr("evaluate_device");
   struct Fin { Trace &t; ~Fin() { t.lap("total"); } } fin{tr};
-  return eval_common(p, cat, update_nodes, n_update, q_nodes, n_q, d_q, true, q_is_probability, root_freqs, d_logl_out,
-                     true, false);
+  EvalRequest rq = request_of(cat, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::DeviceDense, rq.q = d_q, rq.q_is_probability = q_is_probability;
+  rq.d_logl_out = d_logl_out;
+  rq.reduce = true, rq.floor_log = false;
+  return eval_common(p, rq);
 }
 
 /* A device scalar (the all-reduced log-likelihood of a multi-rank evaluation: hyphy_hip_evaluate_device + the caller's
@@ -1500,35 +1497,25 @@ int hyphy_hip_evaluate_categories(hyphy_hip_partition *p, const int64_t *update_
   if (!p) return fail("partition == NULL");
   if (!weights) return fail("weights == NULL");
   const int64_t D = p->D;
+  EvalRequest rq = request_of(0, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::HostDense, rq.q = q_dense, rq.q_is_probability = q_is_probability;
+  rq.reduce = false, rq.floor_log = true;  // (the per-pattern values of every class, floored: mixed and reduced below)
   if (!p->nuc) {
     // rate-class batching: ONE expm launch over C*n_q matrices and ONE pruning launch with a grid row
     // per class (3x the workgroups of a single pass: the matrix pipe finally has enough waves)
-    if (eval_common(p, 0, update_nodes, n_update, q_nodes, n_q, q_dense, false, q_is_probability, root_freqs, nullptr,
-                    false, true, /* batch = */ true))
-      return -1;
+    rq.batch = true;
+    if (eval_common(p, rq)) return -1;
   } else {
     for (int64_t c = 0; c < p->C; c++) {
       if (!p->initialized[c]) p->cached_valid = 0;
-      if (eval_common(p, c, update_nodes, n_update, q_nodes, n_q,
-                      q_dense ? q_dense + (size_t)c * n_q * D * D : nullptr, false, q_is_probability, root_freqs,
-                      nullptr, false, true))
-        return -1;
+      rq.cat = c;
+      rq.q = q_dense ? q_dense + (size_t)c * n_q * D * D : nullptr;
+      if (eval_common(p, rq)) return -1;
     }
   }
-  std::vector<double> parts;
-  p->cached_weights.assign(weights, weights + p->C);
-  for (Shard &s : p->shards) {
-    HIPCHK(hipSetDevice(s.device));
-    if (upload_small(s, weights, (size_t)p->C, s.weights)) return -1;
-    launch_mix_categories(s.site_lik, s.site_cnt, s.weights, (int)p->C, s.S_pad, s.mixed_lik, s.mixed_cnt, s.stream);
-    double *rec = s.d_hout ? s.d_hout : s.out;
-    launch_site_reduce(s.mixed_lik, s.mixed_cnt, s.freq, s.S_pad, 1, rec, rec + 1, s.status, s.stream, next_seq(s, rec == s.d_hout));
-  }
-  if (collect_status(p)) return -1;
-  for (Shard &s : p->shards) parts.push_back(s.h_out[0]);
-  if (logl_out) *logl_out = combine(parts);
-  if (site_lik_out || site_scaler_out) return gather_sites(p, 0, site_lik_out, site_scaler_out, true);
-  return 0;
+  // (this entry point uploads the weights at every call — a wait for the stream —, its built twin only when they change)
+  if (mix_and_reduce_categories(p, weights, /* always = */ true)) return -1;
+  return result_tail(p, 0, kCombineHost, kNoTimings, kSitesGatheredMixed, logl_out, site_lik_out, site_scaler_out);
 }
 
 int hyphy_hip_evaluate_categories_built_sites(hyphy_hip_partition *p, const int64_t *update_nodes, int64_t n_update,
@@ -1539,29 +1526,12 @@ int hyphy_hip_evaluate_categories_built_sites(hyphy_hip_partition *p, const int6
   if (!p->K) return fail("evaluate_categories_built: templates not set");
   if (p->nuc) return fail("evaluate_categories_built: MFMA partitions only (4-state: hyphy_hip_evaluate_categories)");
   if (!weights) return fail("weights == NULL");
-  if (eval_common(p, 0, update_nodes, n_update, q_nodes, n_q, &kOwnQBuffer, true, 0, root_freqs, nullptr, false, true, true))
-    return -1;
-  const bool w_changed = p->cached_weights.size() != (size_t)p->C ||
-                         memcmp(p->cached_weights.data(), weights, p->C * sizeof(double));
-  if (w_changed) p->cached_weights.assign(weights, weights + p->C);
-  for (Shard &s : p->shards) {
-    HIPCHK(hipSetDevice(s.device));
-    if (w_changed && upload_small(s, weights, (size_t)p->C, s.weights)) {
-      p->cached_weights.clear();
-      return -1;
-    }
-    launch_mix_categories(s.site_lik, s.site_cnt, s.weights, (int)p->C, s.S_pad, s.mixed_lik, s.mixed_cnt, s.stream);
-    double *rec = s.d_hout ? s.d_hout : s.out;
-    launch_site_reduce(s.mixed_lik, s.mixed_cnt, s.freq, s.S_pad, 1, rec, rec + 1, s.status, s.stream, next_seq(s, rec == s.d_hout));
-  }
-  if (collect_status(p)) return -1;
-  if (logl_out) {
-    std::vector<double> parts;
-    for (Shard &s : p->shards) parts.push_back(s.h_out[0]);
-    *logl_out = combine(parts);
-  }
-  if (site_lik_out || site_scaler_out) return gather_sites(p, 0, site_lik_out, site_scaler_out, true);
-  return 0;
+  EvalRequest rq = request_of(0, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::OwnStaged;
+  rq.reduce = false, rq.floor_log = true, rq.batch = true;
+  if (eval_common(p, rq)) return -1;
+  if (mix_and_reduce_categories(p, weights, /* always = */ false)) return -1;
+  return result_tail(p, 0, kCombineHost, kNoTimings, kSitesGatheredMixed, logl_out, site_lik_out, site_scaler_out);
 }
 
 int hyphy_hip_evaluate_categories_built(hyphy_hip_partition *p, const int64_t *update_nodes, int64_t n_update,
@@ -1793,17 +1763,8 @@ int hyphy_hip_branch_cache_evaluate(hyphy_hip_partition *p, int64_t cat, int64_t
     HIPCHK(hipSetDevice(s.device));
     HIPCHK(hipMemcpyAsync(s.bc_q, q_dense, (size_t)D * D * sizeof(double), hipMemcpyHostToDevice, s.stream));
     ExpmArgs ea;
-    ea.Q = s.bc_q;
-    ea.slots = s.bc_slot + cat;
-    ea.n = 1;
-    ea.D = (int)D;
-    ea.is_prob = q_is_probability;
+    ea.Q = s.bc_q, ea.slots = s.bc_slot + cat, ea.n = 1, ea.D = (int)D, ea.is_prob = q_is_probability;
     ea.status = s.status;
-    ea.templates = nullptr;
-    ea.coeffs = nullptr;
-    ea.K = 0;
-    ea.prof = 0;
-    ea.Prow = nullptr;
     ea.Pfrag = s.Pfrag + (size_t)cat * B * DP * DP;
     ea.PTg = s.PTg + (size_t)cat * B * DP * DP;
     launch_expm(ea, s.stream);
@@ -1835,12 +1796,7 @@ int hyphy_hip_branch_cache_evaluate(hyphy_hip_partition *p, int64_t cat, int64_t
     launch_wg_reduce(s.wg_sum, s.wg_cnt, s.wg_flag, s.ntiles, rec, rec + 1, s.status, s.stream, next_seq(s, rec == s.d_hout));
     HIPCHK(hipGetLastError());
   }
-  if (collect_status(p)) return -1;
-  std::vector<double> parts;
-  for (Shard &s : p->shards) parts.push_back(s.h_out[0]);
-  if (logl_out) *logl_out = combine(parts);
-  if (site_lik_out || site_scaler_out) return gather_sites(p, (int)cat, site_lik_out, site_scaler_out, false);
-  return 0;
+  return result_tail(p, (int)cat, kCombineHost, kNoTimings, kSitesGathered, logl_out, site_lik_out, site_scaler_out);
 }
 
 int hyphy_hip_expm_batch(int64_t D, int64_t n, const double *q_dense, double *p_out) {
@@ -1860,9 +1816,8 @@ int hyphy_hip_expm_batch(int64_t D, int64_t n, const double *q_dense, double *p_
   HIPCHK(hipMemset(st, 0, sizeof(int32_t)));
   HIPCHK(hipMemcpy(dq, q_dense, bytes, hipMemcpyHostToDevice));
   ExpmArgs ea;
-  ea.Q = dq; ea.slots = nullptr; ea.n = (int)n; ea.D = (int)D; ea.is_prob = 0;
-  ea.Prow = dp; ea.Pfrag = nullptr; ea.PTg = nullptr; ea.prof = 0; ea.status = st;
-  ea.templates = nullptr; ea.coeffs = nullptr; ea.K = 0;
+  ea.Q = dq; ea.n = (int)n; ea.D = (int)D;
+  ea.Prow = dp; ea.status = st;
   launch_expm(ea, nullptr);
   int32_t hst = 0;
   hipError_t e1 = hipMemcpy(p_out, dp, bytes, hipMemcpyDeviceToHost);

@@ -41,8 +41,9 @@ int rccl_load() {
 
 // Sum of the shard partials of a single-process, multi-device partition (every shard's record has been collected):
 // the reference's Neumaier combine on the host (likefunc.cpp:11046-11093), or — HYPHY_HIP_COMBINE=rccl behind
-// hyphy_hip_comm_init_all — ONE group all-reduce over xGMI (every shard ends up with the total; shard 0's copy is returned).
-int combine_shards(hyphy_hip_partition *p, double *logl_out) {
+// hyphy_hip_comm_init_all, unless the entry point never took it (`allow_rccl`) — ONE group all-reduce over xGMI (every shard ends up
+// with the total; shard 0's copy is returned).
+int combine_shards(hyphy_hip_partition *p, double *logl_out, bool allow_rccl) {
   if (!logl_out) return 0;
   if (p->shards.size() == 1) {
     *logl_out = p->shards[0].h_out[0];
@@ -51,6 +52,7 @@ int combine_shards(hyphy_hip_partition *p, double *logl_out) {
   std::vector<double> parts;
   for (Shard &s : p->shards) parts.push_back(s.h_out[0]);
   *logl_out = combine(parts);
+  if (!allow_rccl) return 0;  // (these entry points never read the switch)
   const char *mode = getenv("HYPHY_HIP_COMBINE");
   if (!(mode && !strcmp(mode, "rccl") && p->shards[0].comm)) return 0;
   for (Shard &s : p->shards) {
@@ -247,11 +249,13 @@ int hyphy_hip_allreduce_device(hyphy_hip_partition *p, double *d_value) {
   return 0;
 }
 
-// The collective + read-back behind a local evaluation that left this rank's partial in s.ar_buf.  A rank whose local
+// The local evaluation `rq` with this rank's partial into s.ar_buf, then the collective + read-back.  A rank whose local
 // evaluation FAILED (validation, a HIP error) still joins the collective — with NaN — so that the other ranks are not left
 // waiting in it; every rank then sees NaN and the failing one returns its own error.
-static int allreduce_and_fetch(hyphy_hip_partition *p, int local_rc, double *logl_out) {
+static int allreduce_and_fetch(hyphy_hip_partition *p, EvalRequest rq, double *logl_out) {
   Shard &s = p->shards[0];
+  rq.d_logl_out = s.ar_buf, rq.reduce = true, rq.floor_log = false;
+  int local_rc = eval_common(p, rq);
   std::string local_error = g_last_error;
   // Nothing returns before the all-reduce has been enqueued: the peers read their result by spinning on a host-mapped record
   // and would never leave the collective.  Failures on the way (device selection, the NaN upload, timing events) only mark
@@ -302,10 +306,10 @@ int hyphy_hip_evaluate_allreduce(hyphy_hip_partition *p, int64_t cat, const int6
                                  const double *root_freqs, double *logl_out) {
   if (!p) return fail("partition == NULL");
   if (p->shards.size() != 1 || !p->shards[0].comm) return fail("evaluate_allreduce: hyphy_hip_comm_init_rank first");
-  Shard &s = p->shards[0];
   // partial log-L of this rank's patterns into a device scalar, summed over the ranks in-stream, one double back
-  const int rc = eval_common(p, cat, update_nodes, n_update, q_nodes, n_q, q_dense, false, q_is_probability, root_freqs, s.ar_buf, true, false);
-  return allreduce_and_fetch(p, rc, logl_out);
+  EvalRequest rq = request_of(cat, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::HostDense, rq.q = q_dense, rq.q_is_probability = q_is_probability;
+  return allreduce_and_fetch(p, rq, logl_out);
 }
 
 /* The same behind hyphy_hip_build_q (template models: coefficients, not matrices, cross PCIe): the step a site-sharded
@@ -316,9 +320,9 @@ int hyphy_hip_evaluate_built_allreduce(hyphy_hip_partition *p, int64_t cat, cons
   if (!p) return fail("partition == NULL");
   if (!p->K) return fail("evaluate_built_allreduce: templates not set");
   if (p->shards.size() != 1 || !p->shards[0].comm) return fail("evaluate_built_allreduce: hyphy_hip_comm_init_rank first");
-  Shard &s = p->shards[0];
-  const int rc = eval_common(p, cat, update_nodes, n_update, q_nodes, n_q, &kOwnQBuffer, true, 0, root_freqs, s.ar_buf, true, false);
-  return allreduce_and_fetch(p, rc, logl_out);
+  EvalRequest rq = request_of(cat, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::OwnStaged;
+  return allreduce_and_fetch(p, rq, logl_out);
 }
 
 double hyphy_hip_last_allreduce_ms(const hyphy_hip_partition *p) { return p ? p->allreduce_ms : 0.; }
@@ -364,7 +368,9 @@ int hyphy_hip_comm_init_host(hyphy_hip_partition *p, const char *name, int rank,
   return 0;
 }
 
-static int exchange_after(hyphy_hip_partition *p, int local_rc, double *logl_out) {
+static int evaluate_and_exchange(hyphy_hip_partition *p, EvalRequest rq, double *logl_out) {
+  rq.reduce = true, rq.floor_log = false;
+  const int local_rc = eval_common(p, rq);
   const std::string local_error = g_last_error;
   double local = 0., total = 0.;
   bool failed = local_rc != 0;
@@ -392,8 +398,9 @@ int hyphy_hip_evaluate_exchange(hyphy_hip_partition *p, int64_t cat, const int64
                                 int64_t n_q, const double *q_dense, int q_is_probability, const double *root_freqs, double *logl_out) {
   if (!p) return fail("partition == NULL");
   if (p->shards.size() != 1 || !p->xch) return fail("evaluate_exchange: hyphy_hip_comm_init_host first");
-  const int rc = eval_common(p, cat, update_nodes, n_update, q_nodes, n_q, q_dense, false, q_is_probability, root_freqs, nullptr, true, false);
-  return exchange_after(p, rc, logl_out);
+  EvalRequest rq = request_of(cat, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::HostDense, rq.q = q_dense, rq.q_is_probability = q_is_probability;
+  return evaluate_and_exchange(p, rq, logl_out);
 }
 
 int hyphy_hip_evaluate_built_exchange(hyphy_hip_partition *p, int64_t cat, const int64_t *update_nodes, int64_t n_update,
@@ -401,8 +408,9 @@ int hyphy_hip_evaluate_built_exchange(hyphy_hip_partition *p, int64_t cat, const
   if (!p) return fail("partition == NULL");
   if (!p->K) return fail("evaluate_built_exchange: templates not set");
   if (p->shards.size() != 1 || !p->xch) return fail("evaluate_built_exchange: hyphy_hip_comm_init_host first");
-  const int rc = eval_common(p, cat, update_nodes, n_update, q_nodes, n_q, &kOwnQBuffer, true, 0, root_freqs, nullptr, true, false);
-  return exchange_after(p, rc, logl_out);
+  EvalRequest rq = request_of(cat, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::OwnStaged;
+  return evaluate_and_exchange(p, rq, logl_out);
 }
 
 int hyphy_hip_xch_open(const char *name, int rank, int n_ranks, void **handle_out) {

@@ -279,22 +279,22 @@ struct SiteFitArgs {
 constexpr int kMaxTwin = 32;  // longest path (in edges) between the given root and the root a re-rooted schedule computes at
 
 struct ExpmArgs {
-  const double *Q;           // [n][D*D] row-major (rate matrices, or probabilities if is_prob)
-  const int32_t *slots;      // [n] destination branch slot (node code) or nullptr -> identity
-  int n;
-  int D;
-  int is_prob;
-  double *Prow;              // optional [.][D*D] row-major output (slot-indexed)
+  const double *Q = nullptr;      // [n][D*D] row-major (rate matrices, or probabilities if is_prob)
+  const int32_t *slots = nullptr; // [n] destination branch slot (node code) or nullptr -> identity
+  int n = 0;
+  int D = 0;
+  int is_prob = 0;
+  double *Prow = nullptr;    // optional [.][D*D] row-major output (slot-indexed)
   double *PTrow = nullptr;   // optional (4 states): the transposed matrices [.][16], read by prune_nuc2_kernel
-  double *Pfrag;             // optional [.][NW][NKK*64]
-  double *PTg;               // optional [.][DP][NW][16]  column-gather image (leaf edges): [code][wb][g][r] = P[16wb + 4r + g][code]
-  int32_t *status;           // [1] set to nonzero if any matrix failed (NaN / ill-conditioned)
+  double *Pfrag = nullptr;   // optional [.][NW][NKK*64]
+  double *PTg = nullptr;     // optional [.][DP][NW][16]  column-gather image (leaf edges): [code][wb][g][r] = P[16wb + 4r + g][code]
+  int32_t *status = nullptr; // [1] set to nonzero if any matrix failed (NaN / ill-conditioned)
   // optional fused rate-matrix construction: Q_m = sum_k coeffs[m][k] * templates[k]
   // off-diagonal, diagonal = -(row sum); when templates != nullptr, Q is ignored
-  const double *templates;   // [K][D*D]
-  const double *coeffs;      // [n][K]
-  int K;
-  int prof;                  // diagnostic: workgroup 0 stamps its phases (HYPHY_HIP_EXPM_PROF)
+  const double *templates = nullptr;  // [K][D*D]
+  const double *coeffs = nullptr;     // [n][K]
+  int K = 0;
+  int prof = 0;              // diagnostic: workgroup 0 stamps its phases (HYPHY_HIP_EXPM_PROF)
   const unsigned char *need = nullptr;  // (expm64_kernel, r06) per branch [need_B]: bit 0 its consumers read the A-operand image, bit 1 the
   int need_B = 0;                       // column-gather image; nullptr: both are written.  Slot s belongs to branch s % need_B
   int fixed_degree = 0;      // expm64_kernel: 1 = always degree 12 (HYPHY_HIP_EXPM_DEGREE=12); 0 = degree from the scaled norm

@@ -4,6 +4,9 @@
 //   tuner.hip     the run-time schedule tuner and the launch of the current schedule
 //   comm.hip      RCCL (loaded on first use) and the all-reduce entry points
 // Host-side bookkeeping only — all arithmetic of the hot path happens in expm.hip / prune.hip / sitefit.hip.
+// An evaluation: an entry point fills an EvalRequest by name, eval_common validates it and settles the schedule, enqueue_eval
+// (api.hip) runs its stages per shard over one stack context, and result_tail collects.  The schedule upload and the pruning
+// step (upload_schedule, prune_args_current, launch_prune_current: tuner.hip) exist once, for evaluations and the tuner's passes.
 #pragma once
 #include <math.h>
 #include <stdio.h>
@@ -442,9 +445,6 @@ inline void rows_to_caller(const hyphy_hip_partition *p, const Shard &s, const T
     for (int64_t k = 0; k < n; k++) out[(size_t)r * p->S + caller_pattern(p, s.s0 + (list ? list[k] : k))] = src[(size_t)r * stride + k];
 }
 
-// "use the shard's own Q buffer" (filled / staged by hyphy_hip_build_q on every shard): compared by address
-extern const double kOwnQBuffer;
-
 // branch-site mixture: matrix k of the evaluation is sum_m weights[off_k + m] exp(q[off_k + m]), count[k] components
 constexpr int64_t kMixRows = 16;  // most components of an explicit-form mixture per branch
 struct MixSpec {
@@ -452,6 +452,41 @@ struct MixSpec {
   const double *weights;
   int64_t n_tot;
 };
+
+// One evaluation as eval_common takes it; callers fill it by name.
+enum class QSource {
+  HostDense,    // `q`: dense matrices in host memory (copied to the shard's buffer in-stream)
+  DeviceDense,  // `q`: dense matrices in device memory
+  OwnStaged     // each shard's own buffer as hyphy_hip_build_q staged / filled it (`q` unused)
+};
+struct EvalRequest {
+  int64_t cat = 0;                       // rate class (batch: ignored)
+  const int64_t *update_nodes = nullptr, *q_nodes = nullptr;  // update list; matrix list: branch of matrix k
+  int64_t n_update = 0, n_q = 0;
+  QSource q_source = QSource::HostDense;
+  const double *q = nullptr;
+  int q_is_probability = 0;              // (either dense source can carry rate matrices or probabilities)
+  const double *root_freqs = nullptr;
+  double *d_logl_out = nullptr;          // device scalar the result goes to (asynchronous callers), nullptr: the shard's host-mapped record
+  bool reduce = false;                   // finish with the final reduction
+  bool floor_log = false;                // ... of the stored per-pattern values, floored (category mode)
+  bool batch = false;                    // all rate classes in one launch (MFMA path)
+  bool force_persist = false;            // store every node, under the partition's own tree (restores behind downloads / the branch cache)
+  const MixSpec *mix = nullptr;          // explicit-form branch-site mixture
+};
+// The two node lists of an entry point, each under a type of its own: a call that swaps them does not compile.
+struct UpdateList { const int64_t *nodes; int64_t n; };
+struct MatrixList { const int64_t *nodes; int64_t n; };
+inline EvalRequest request_of(int64_t cat, UpdateList update, MatrixList matrices, const double *root_freqs) {
+  EvalRequest rq;
+  rq.cat = cat;
+  rq.update_nodes = update.nodes;
+  rq.n_update = update.n;
+  rq.q_nodes = matrices.nodes;
+  rq.n_q = matrices.n;
+  rq.root_freqs = root_freqs;
+  return rq;
+}
 
 // schedule.hip
 void init_plain_view(hyphy_hip_partition *p);
@@ -461,17 +496,15 @@ void build_schedule(hyphy_hip_partition *p, const int64_t *update_nodes, int64_t
 void reroot_path(hyphy_hip_partition *p);
 void sort_patterns(hyphy_hip_partition *p, const int64_t *leaf_codes, int64_t L, int64_t S);
 // tuner.hip
-int upload_schedule(hyphy_hip_partition *p, Shard &s);
-int launch_prune_current(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch);  // -1: nothing launched (fail() set)
+int upload_schedule(hyphy_hip_partition *p, Shard &s, bool sync_always);
+PruneArgs prune_args_current(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch);
+int launch_prune_current(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch, const PruneArgs *eval = nullptr, bool eval_walk = false);  // -1: fail() set
 int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch);
 // api.hip
 void refresh_twins(hyphy_hip_partition *p, Shard &s);
 PruneArgs base_prune_args(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch);
 int ensure_deposits(hyphy_hip_partition *p, Shard &s);
-int eval_common(hyphy_hip_partition *p, int64_t cat, const int64_t *update_nodes, int64_t n_update, const int64_t *q_nodes,
-                int64_t n_q, const double *q, bool q_on_device, int q_is_probability, const double *root_freqs,
-                double *d_logl_out, bool reduce, bool floor_log, bool batch = false, bool force_persist = false,
-                const MixSpec *mix = nullptr);
+int eval_common(hyphy_hip_partition *p, const EvalRequest &request);
 int finish_pending_async(hyphy_hip_partition *p);
 int ensure_resident(hyphy_hip_partition *p, int64_t cat);  // persisted conditionals of class cat current (re-runs a persisting pass)
 int collect_status(hyphy_hip_partition *p);
@@ -498,6 +531,6 @@ int rep_sync_stride();
 // marginal.hip
 std::vector<int4> plan_marginal_program(int64_t L, int64_t I, const int64_t *parents, int *maxk_out);
 // comm.hip
-int combine_shards(hyphy_hip_partition *p, double *logl_out);
+int combine_shards(hyphy_hip_partition *p, double *logl_out, bool allow_rccl = true);
 
 }  // namespace hyhip

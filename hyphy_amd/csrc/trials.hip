@@ -327,20 +327,11 @@ int trials_common(const char *what, hyphy_hip_partition *p, int64_t n_trials, co
     HIPCHK(hipMemcpyAsync(d_idx, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
     // trial images: one launch of the exponential kernels into the call's own slots (slot = trial * C + class)
     ExpmArgs ea;
-    ea.Q = q_dense ? src : nullptr;
-    ea.slots = nullptr;
-    ea.n = (int)nm;
-    ea.D = (int)D;
-    ea.is_prob = q_dense ? q_is_probability : 0;
-    ea.Prow = nuc ? img : nullptr;
-    ea.Pfrag = nuc ? nullptr : img;
-    ea.PTg = nullptr;
-    ea.status = status;
-    ea.templates = coeffs ? s.templates : nullptr;
-    ea.templates_pad = coeffs ? s.templates_pad : nullptr;
-    ea.coeffs = coeffs ? src : nullptr;
-    ea.K = coeffs ? (int)p->K : 0;
-    ea.prof = 0;
+    ea.n = (int)nm, ea.D = (int)D, ea.status = status;
+    if (nuc) ea.Prow = img;
+    else ea.Pfrag = img;
+    if (q_dense) ea.Q = src, ea.is_prob = q_is_probability;
+    if (coeffs) ea.templates = s.templates, ea.templates_pad = s.templates_pad, ea.coeffs = src, ea.K = (int)p->K;
     const char *expm_before = last_expm_kernel();
     launch_expm(ea, s.stream);
     set_last_expm_kernel(expm_before);

@@ -7,12 +7,10 @@
 
 namespace hyhip {
 
-
-// Upload the current schedule to one shard and launch its pruning kernel(s) (no expm, no reduction): the body of an
-// evaluation's pruning step, shared with the schedule tuner.
-int upload_schedule(hyphy_hip_partition *p, Shard &s) {
-  HIPCHK(hipSetDevice(s.device));
-  HIPCHK(hipStreamSynchronize(s.stream));
+// Upload the current schedule.  sync_always (the tuner): select the device and wait even with nothing to upload; else only before a copy.
+int upload_schedule(hyphy_hip_partition *p, Shard &s, bool sync_always) {
+  if (sync_always) HIPCHK(hipSetDevice(s.device));
+  if (sync_always || !p->ops_host.empty()) HIPCHK(hipStreamSynchronize(s.stream));
   if (p->ops_host.empty()) return 0;
   memcpy(s.h_ops, p->ops_host.data(), p->ops_host.size() * sizeof(int4));
   HIPCHK(hipMemcpyAsync(s.ops, s.h_ops, p->ops_host.size() * sizeof(int4), hipMemcpyHostToDevice, s.stream));
@@ -27,26 +25,40 @@ int upload_schedule(hyphy_hip_partition *p, Shard &s) {
   return 0;
 }
 
-int launch_prune_current(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch) {
+// The pruning step of the current schedule (no expm, no reduction), for evaluations and the tuner's passes alike: prune_args_current
+// brings the twin images up to date and completes a PruneArgs from the partition, launch_prune_current walks the levels, or the trunk
+// walk, under it.  An evaluation adds what is its own (timeline buffer, fused-combine block) and hands the arguments back as `eval`.
+PruneArgs prune_args_current(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch) {
   if (p->rr_active && p->chain && s.twins_dirty) refresh_twins(p, s);
   PruneArgs pa = base_prune_args(p, s, cat, n_cat_batch);
-  int n_ops = 0;
-  for (const auto &pr : p->programs) n_ops = std::max(n_ops, pr.n);
-  pa.ops = s.ops;
-  pa.n_ops = n_ops;
+  for (const auto &pr : p->programs) pa.n_ops = std::max(pa.n_ops, pr.n);  // longest program
+  pa.ops = s.ops, pa.prog = s.prog;
   pa.n_prog_total = p->chain ? (int)p->I : (int)p->programs.size();
   pa.chain = p->chain ? 1 : 0;
-  pa.jn = s.jn;
-  pa.deposits = s.deposits;
-  pa.cs_deposits = s.deposits_class_stride;
+  pa.jn = s.jn, pa.deposits = s.deposits, pa.cs_deposits = s.deposits_class_stride;
   if (const char *ab = getenv("HYPHY_HIP_ABLATE")) pa.ablate = atoi(ab);
-  if (trunk_walk_applies(p, s))  // (the trunk of a class-compressed partition as one row-split walk per tile, repeats.hip)
-    return launch_trunk_walk(p, s, cat, n_cat_batch, false);
-  for (size_t lv = 0; lv < p->levels.size(); lv++) {
+  return pa;
+}
+
+int launch_prune_current(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch, const PruneArgs *eval, bool eval_walk) {
+  PruneArgs pa = eval ? *eval : prune_args_current(p, s, cat, n_cat_batch);
+  // the trunk of a class-compressed partition, lazy full pass: one row-split walk per tile instead of the schedule (repeats.hip)
+  const bool walk = eval ? eval_walk : trunk_walk_applies(p, s);  // (an evaluation has decided already: its fused combine depends on it)
+  if (walk) {
+    if (launch_trunk_walk(p, s, cat, n_cat_batch, eval != nullptr, &pa)) return -1;  // (its own timeline: evaluations only)
+    if (eval) s.last_walk = true;  // (hyphy_hip_prune_kernel_name speaks of evaluations: the tuner's passes leave it alone)
+    return 0;
+  }
+  if (eval) s.last_walk = false;
+  double *const red_out = pa.red_out;
+  for (size_t lv = 0; lv < p->levels.size(); lv++) {  // one launch per level of subtree fragments
     pa.prog = s.prog + p->levels[lv].first;
     pa.n_prog = p->levels[lv].count;
     pa.do_root = (lv + 1 == p->levels.size()) ? 1 : 0;
-    if (launch_prune_mfma(pa, s.stream)) return fail("internal: no pruning kernel for this launch form (variant " + std::to_string(p->variant) + ")");
+    pa.red_out = pa.do_root ? red_out : nullptr;  // (the launch that finalises the roots carries the fused final combine)
+    if (launch_prune_mfma(pa, s.stream))  // (the two messages differed before the copies were joined: kept)
+      return fail("internal: no pruning kernel for this launch form (variant " + std::to_string(p->variant) +
+                  (eval ? ", " + std::to_string(p->NW) + " row blocks)" : ")"));
   }
   return 0;
 }
@@ -94,7 +106,7 @@ int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch) {
   int err = 0;
   auto time_it = [&](const Cand &c) -> double {  // fastest of two passes behind a warm-up pass, ms; < 0: not measured
     if (!apply(c)) return -1.;
-    if (upload_schedule(p, s)) {
+    if (upload_schedule(p, s, true)) {
       err = -1;
       return -1.;
     }
