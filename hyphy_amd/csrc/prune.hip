@@ -566,7 +566,11 @@ __global__ __launch_bounds__(64 * NW, (T == 1 ? HYPHY_OCC : 1)) void prune_mfma_
       const int4 jp = jn[par];
       const int need = jp.y & 0xff;
       int *ctr = a.frag_ctr + (size_t)par * a.ntiles + tile;
-      const bool pred = need <= 1 || s_early[lvl & 1] == need - 1;  // (uniform over the workgroup)
+      // (three or more deposited children: (a x b) x c and (c x a) x b differ in the last bit, so the node is formed from ALL its
+      //  entries in schedule order, the finishing workgroup's own product read back from its deposit slot like the others —
+      //  such a join always deposits and counts its arrival, the shortcut below is for joins of two)
+      const bool ordered = need >= 3;
+      const bool pred = need <= 1 || (!ordered && s_early[lvl & 1] == need - 1);  // (uniform over the workgroup)
       asm volatile("" ::: "memory");
       const int4 *tops = ops0 + jp.z;  // (followed by a no-op entry: one entry ahead is always readable)
       int4 op = tops[0];
@@ -611,8 +615,8 @@ __global__ __launch_bounds__(64 * NW, (T == 1 ? HYPHY_OCC : 1)) void prune_mfma_
                                                      __HIP_MEMORY_SCOPE_AGENT);
       }
       // `par`: own product, leaf columns, the deposited products of the other children
-      acc[0] = prod;
-      cnt[0] = pcnt;
+      acc[0] = ordered ? (f64x4){1., 1., 1., 1.} : prod;
+      cnt[0] = ordered ? 0 : pcnt;
       int lastx = 0;
       auto consume = [&](const int4 &o, const Item &it) {
         lastx = o.x;
@@ -640,7 +644,7 @@ __global__ __launch_bounds__(64 * NW, (T == 1 ? HYPHY_OCC : 1)) void prune_mfma_
             }
             acc[0] *= d;
           }
-        } else if (o.w != c) {  // OPK_DEP: deposited by the workgroup that computed it (its arrival was counted)
+        } else if (o.w != c || ordered) {  // OPK_DEP: deposited by the workgroup that computed it (its arrival was counted)
           acc[0] *= (f64x4){it.v[0][0], it.v[0][1], it.v[1][0], it.v[1][1]};
           cnt[0] += it.cnt;
         }
@@ -1181,6 +1185,7 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
         else return (f64x2){bch[k2 >> 1][(k2 & 1) * 2], bch[k2 >> 1][(k2 & 1) * 2 + 1]};
       }, pre, last ? nullptr : ctr, jp.x >= 0 ? (jp.x >> 16) : -1);
       cnt = bcnt;
+      bool deposited = false;  // (uniform)
       if (!last) {
         // (the counter was sampled two k-steps before the end of the product: its round trip is covered)
         const int seen = __builtin_amdgcn_readfirstlane(polled);
@@ -1210,6 +1215,7 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
             __hip_atomic_store(a.hand_cnt + ((size_t)c * a.ntiles + tile0) * 32 + sl, cnt, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          deposited = true;
           int old = 0;
           if (lane == 0) old = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           old = __builtin_amdgcn_readfirstlane(old);
@@ -1227,7 +1233,30 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
       if (jp.x >= 0 && (jn[jp.x & 0xffff].y & 0xff) > 1 && lane == 0)
         early = __hip_atomic_load(a.frag_ctr + (size_t)(jp.x & 0xffff) * a.ntiles + tile0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       HYPHY_TR(5)
-      run_ops(ops + jp.z, jp.w, c, pre != nullptr, pre_cnt);
+      int own = c;
+      if (need >= 3) {
+        // Three or more deposited children: own x b x c and c x own x b differ in the last bit, and which wave finishes p is a
+        // matter of timing.  The finishing wave's product goes through its deposit slot like everybody else's (it is there
+        // already unless the wave saw all siblings arrived before or during its own product), and p is formed from the entries
+        // in schedule order — one more L2 round trip at such a join, the same bits whoever arrives last.
+        if (!deposited) {
+          double *out = a.deposits + ((size_t)c * a.ntiles + tile0) * TILE;  // uniform
+#pragma unroll
+          for (int w = 0; w < NW; w++) {
+            st16_agent(out, (unsigned)((2 * w) * 64 + lane) * 16u, (f64x2){acc[w][0], acc[w][1]});
+            st16_agent(out, (unsigned)((2 * w + 1) * 64 + lane) * 16u, (f64x2){acc[w][2], acc[w][3]});
+          }
+          if (g == 0)
+            __hip_atomic_store(a.hand_cnt + ((size_t)c * a.ntiles + tile0) * 32 + sl, cnt, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+#pragma unroll
+        for (int w = 0; w < NW; w++) acc[w] = ones;
+        cnt = 0;
+        own = -1;
+      }
+      run_ops(ops + jp.z, jp.w, own, pre != nullptr, pre_cnt);
       if constexpr (TRACE) tr_levels += 1 + (pre ? 100 : 0);
       c = p;
     }

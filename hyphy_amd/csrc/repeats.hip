@@ -1877,7 +1877,8 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
     // HYPHY_HIP_TRUNK_WALK=1: the walk without asking the tuner (tests, A/B runs), at every NW it has a plan for.  No tuner at all
     // (HYPHY_HIP_TUNE=0): the walk at NW = 4 — it is the faster form wherever the static rule turns compression on, and with the
     // one-workgroup-per-tile kernel behind it for the other passes nothing in this mode depends on an order of arrival: the same
-    // bits on every run (tested).  (NW 2 / 3: the walk's speed is unmeasured; without the switch only the tuner offers it.)
+    // bits on every run (tested).  (The chain schedules of the wave and row-split trunks do join by order of arrival, but form every
+    // node in schedule order — schedule.hip, prune.hip — so their bits do not depend on it either.)  (NW 2 / 3: the walk's speed is unmeasured; without the switch only the tuner offers it.)
     const char *tw = getenv("HYPHY_HIP_TRUNK_WALK");
     const bool tune_off = getenv("HYPHY_HIP_TUNE") && atoi(getenv("HYPHY_HIP_TUNE")) == 0;
     const hyphy_hip_partition::View &tv = p->views[1];

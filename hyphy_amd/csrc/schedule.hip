@@ -333,8 +333,13 @@ void build_schedule_impl(hyphy_hip_partition *p, const int64_t *update_nodes, in
         // schedule — the transposed twin of the branch of the NEXT node on the path (expm.hip; slot behind the branch cache's)
         const int slot = (rr && on_path[n] >= 0) ? (int)(p->B + (p->I + 2) + on_path[n]) : v.slot[L + n];
         int4 j = make_int4(rpar[n] < 0 ? -1 : (rpar[n] | (slot << 16)), (int)ich[n].size() | (sum << 8), 0, 0);
-        if (!in_source[n]) {  // trunk node: its leaf groups, one OPK_DEP entry per internal child, finalisation flags
+        if (!in_source[n]) {  // trunk node: one OPK_DEP entry per internal child, its leaf groups, finalisation flags.
+          // The DEP entries come FIRST: the wave that finishes n holds the product of ONE internal child (whichever arrived last)
+          // and multiplies the entries onto it in this order.  With two internal children the product so far is a x b either
+          // way round — the same bits — and the leaf columns follow in a fixed order; behind the leaf groups it was
+          // (a x leaves) x b or (b x leaves) x a by order of arrival, which differ in the last bit.
           j.z = (int)p->ops_host.size();
+          for (int c : ich[n]) p->ops_host.push_back(make_int4(OPK_DEP | (0xff << 24), n, v.slot[L + c], c));
           std::vector<int> leaves;
           for (int c : v.children[n])
             if (c < L) leaves.push_back(c);
@@ -346,7 +351,6 @@ void build_schedule_impl(hyphy_hip_partition *p, const int64_t *update_nodes, in
             p->ops_host.push_back(make_int4(OPK_LEAF | (amb0 ? OPF_AMBIG : 0) | (nl << 8) | (0xff << 24), n, (int)(l0 | (l1 << 16)), 0));
             k += nl;
           }
-          for (int c : ich[n]) p->ops_host.push_back(make_int4(OPK_DEP | (0xff << 24), n, v.slot[L + c], c));
           p->ops_host.back().x |= OPF_LAST | (lazy ? OPF_NOPERSIST : 0);
           j.w = (int)p->ops_host.size() - j.z;
         }
