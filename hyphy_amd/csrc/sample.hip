@@ -25,6 +25,7 @@
 // 4 states (sample_nuc_kernel): one thread per draw, matrices row-major (Prow), conditionals from the [I][4][S_pad] planes.
 // The host scatters the bytes to [replicate][node][site] in the caller's site order.
 #include "partition.h"
+#include "philox.h"
 
 using namespace hyhip;
 
@@ -32,23 +33,6 @@ namespace hyhip {
 namespace {
 
 constexpr int kSlice = 1024;  // draws of a workgroup
-
-struct Philox {
-  uint32_t x[4];
-};
-__host__ __device__ inline Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-  for (int round = 0; round < 10; round++) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1, c3 = (uint32_t)p0, c0 = n0, c2 = n2;
-    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-  }
-  return Philox{{c0, c1, c2, c3}};
-}
-__host__ __device__ inline double philox_uniform(uint64_t seed, uint32_t site, uint32_t node, uint32_t rep) {
-  const Philox r = philox4x32_10(site, node, rep, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
-  return (double)(((uint64_t)(r.x[0] >> 5) << 26) + (uint64_t)(r.x[1] >> 6)) * (1.0 / 9007199254740992.0);
-}
 
 struct SampleArgs {
   int NW, D, L, I, S_pad, ntiles;
@@ -122,7 +106,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
       const size_t o = ((size_t)rr * I + n) * a.Ec + e;
       int st = -1;
       if (ps >= 0) {
-        const double u = a.u ? a.u[o] : philox_uniform(a.seed, (uint32_t)a.esite[e], (uint32_t)n, (uint32_t)(a.r0 + rr));
+        const double u = a.u ? a.u[o] : philox_uniform(a.seed, (uint32_t)a.esite[e], (uint32_t)n, (uint32_t)(a.r0 + rr), kPhiloxSample);
         st = draw_state(Pl + ps * LD, cv + (a.epat[e] & 15) * LD, 1, D, u);
       }
       a.out[o] = (int8_t)st;
@@ -144,7 +128,7 @@ __global__ __launch_bounds__(256) void sample_nuc_kernel(SampleArgs a) {
     const size_t o = (rr * I + n) * a.Ec + e;
     int st = -1;
     if (ps >= 0) {
-      const double u = a.u ? a.u[o] : philox_uniform(a.seed, (uint32_t)a.esite[e], (uint32_t)n, (uint32_t)(a.r0 + rr));
+      const double u = a.u ? a.u[o] : philox_uniform(a.seed, (uint32_t)a.esite[e], (uint32_t)n, (uint32_t)(a.r0 + rr), kPhiloxSample);
       const double *row = n == I - 1 ? a.pi : a.Prow + (size_t)(L + n) * 16 + 4 * ps;
       st = draw_state(row, a.partials + (size_t)n * 4 * a.S_pad + pat, a.S_pad, 4, u);
     }
@@ -169,7 +153,7 @@ int hyphy_hip_sample_uniforms(uint64_t seed, int64_t n_rep, int64_t I, int64_t n
   for (int64_t r = 0; r < n_rep; r++)
     for (int64_t n = 0; n < I; n++) {
       double *row = out + ((size_t)r * I + n) * n_sites;
-      for (int64_t j = 0; j < n_sites; j++) row[j] = philox_uniform(seed, (uint32_t)j, (uint32_t)n, (uint32_t)r);
+      for (int64_t j = 0; j < n_sites; j++) row[j] = philox_uniform(seed, (uint32_t)j, (uint32_t)n, (uint32_t)r, kPhiloxSample);
     }
   return 0;
 }

@@ -23,7 +23,7 @@ EXPORTS = [
     "hyphy_hip_expm_batch", "hyphy_hip_set_q_templates", "hyphy_hip_build_q", "hyphy_hip_q_buffer",
     "hyphy_hip_evaluate_built", "hyphy_hip_evaluate_built_sites", "hyphy_hip_update_q_templates", "hyphy_hip_evaluate_categories_built", "hyphy_hip_evaluate_categories_built_sites", "hyphy_hip_prune_timings", "hyphy_hip_prune_launches",
     "hyphy_hip_prune_kernel_name", "hyphy_hip_branch_cache_build", "hyphy_hip_branch_cache_evaluate",
-    "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_joint_ancestral", "hyphy_hip_sample_ancestral", "hyphy_hip_sample_uniforms", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
+    "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_joint_ancestral", "hyphy_hip_sample_ancestral", "hyphy_hip_sample_uniforms", "hyphy_hip_simulate", "hyphy_hip_simulate_uniforms", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
     "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
     "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error", "hyphy_hip_last_expm_kernel",
     "hyphy_hip_version",
@@ -151,6 +151,10 @@ def load():
     lib.hyphy_hip_sample_ancestral.argtypes = [vp, C.c_int64, C.c_int64, lp, lp, C.c_uint64, dp, C.POINTER(C.c_int8)]
     lib.hyphy_hip_sample_uniforms.restype = C.c_int
     lib.hyphy_hip_sample_uniforms.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, dp]
+    lib.hyphy_hip_simulate.restype = C.c_int
+    lib.hyphy_hip_simulate.argtypes = [vp, C.c_int64, C.c_int64, lp, lp, C.c_uint64, dp, C.c_int, C.POINTER(C.c_int8)]
+    lib.hyphy_hip_simulate_uniforms.restype = C.c_int
+    lib.hyphy_hip_simulate_uniforms.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, dp]
     lib.hyphy_hip_branch_trials.restype = C.c_int
     lib.hyphy_hip_branch_trials.argtypes = [vp, C.c_int64, lp, dp, C.c_int, dp, dp, dp, lp]
     lib.hyphy_hip_branch_trials_built.restype = C.c_int
@@ -340,6 +344,14 @@ def sample_uniforms(seed: int, n_rep: int, I: int, n_sites: int) -> np.ndarray:
     supplied (Philox4x32-10, counter = (site, node, replicate, 0))."""
     out = np.zeros((int(n_rep), int(I), int(n_sites)))
     _check(load().hyphy_hip_sample_uniforms(C.c_uint64(int(seed) & (2 ** 64 - 1)), int(n_rep), int(I), int(n_sites), _d(out)))
+    return out
+
+
+def simulate_uniforms(seed: int, n_rep: int, n_nodes: int, n_sites: int) -> np.ndarray:
+    """Host-only: the uniforms [n_rep, n_nodes, n_sites] (nodes by node code) that ``HipPartition.simulate`` draws with under
+    ``seed`` when none are supplied (Philox4x32-10, counter = (site, node code, replicate, 1))."""
+    out = np.zeros((int(n_rep), int(n_nodes), int(n_sites)))
+    _check(load().hyphy_hip_simulate_uniforms(C.c_uint64(int(seed) & (2 ** 64 - 1)), int(n_rep), int(n_nodes), int(n_sites), _d(out)))
     return out
 
 
@@ -755,6 +767,33 @@ class HipPartition:
         out = np.full((int(n_rep), self.I, n_sites), -2, dtype=np.int8)
         _check(self._lib.hyphy_hip_sample_ancestral(self._h, int(n_rep), n_sites, _l(pos), _l(cls), C.c_uint64(int(seed) & (2 ** 64 - 1)),
                                                     _d(u), out.ctypes.data_as(C.POINTER(C.c_int8))))
+        return out
+
+    def simulate(self, n_rep: int, n_sites: int, class_of_site=None, root_states=None, seed: int = 0, uniforms=None,
+                 with_internal: bool = False) -> np.ndarray:
+        """Alignments drawn down the tree (the reference's ``SimulateDataSet``) under the matrices of the last evaluation of each
+        referenced class and the root frequencies on the device: int8 [n_rep, L (+ I with ``with_internal``), n_sites] by node
+        code (leaves, then internal nodes, the root last), -1 where a row has no positive total.  ``class_of_site``
+        [n_rep, n_sites]: the rate class of each column (default: class 0); ``root_states`` [n_rep, n_sites]: the root's state
+        (default: drawn from pi); ``uniforms`` [n_rep, L + I, n_sites] in [0, 1): the uniform of every draw (default:
+        Philox4x32-10 keyed by ``seed``, see ``simulate_uniforms``).  Nothing on the device changes."""
+        n_rep, n_sites = int(n_rep), int(n_sites)
+        rows = self.L + self.I
+
+        def per_column(x):
+            if x is None:
+                return None
+            x = np.ascontiguousarray(x, dtype=np.int64)
+            assert x.shape == (n_rep, n_sites)
+            return x
+        cls, root = per_column(class_of_site), per_column(root_states)
+        u = None
+        if uniforms is not None:
+            u = np.ascontiguousarray(uniforms, dtype=np.float64)
+            assert u.shape == (n_rep, rows, n_sites)
+        out = np.full((max(n_rep, 0), rows if with_internal else self.L, max(n_sites, 0)), -2, dtype=np.int8)
+        _check(self._lib.hyphy_hip_simulate(self._h, n_rep, n_sites, _l(cls), _l(root), C.c_uint64(int(seed) & (2 ** 64 - 1)), _d(u),
+                                            int(bool(with_internal)), out.ctypes.data_as(C.POINTER(C.c_int8))))
         return out
 
     # -- trial matrices on any number of branches from one outside pass ----------------------------

@@ -515,6 +515,55 @@ int hyphy_hip_sample_ancestral(hyphy_hip_partition *p, int64_t n_rep, int64_t n_
 /* host-only, no device: the uniforms the call above would use with uniforms == NULL, out[n_rep][I][n_sites] */
 int hyphy_hip_sample_uniforms(uint64_t seed, int64_t n_rep, int64_t I, int64_t n_sites, double *out);
 
+/* ---- simulation down the tree --------------------------------------------------------------------------------
+ * Replaces _LikelihoodFunction::Simulate with BuildLeafProbs / SingleBuildLeafProbs (src/core/likefunc.cpp:12584-13259) and
+ * DrawFromDiscrete (src/core/include/function_templates.h:404-413): HBL's SimulateDataSet, the draw behind every parametric
+ * bootstrap.  A column is (replicate r, site j); its rate class is c = class_of_site[r][j].  Sites are free: n_sites has nothing
+ * to do with the partition's pattern count.  Nodes are visited parent-first; per node n of a column:
+ *   row:    the root (node code L+I-1) uses row = pi; any other node uses row = P_n^(c)[state of the parent]
+ *   sum:    cum_i = row[0] + ... + row[i] in ascending i, every addition rounded;  total = cum_{D-1};  x = u * total
+ *   state:  the smallest i with cum_i >= x and cum_i > 0
+ *   total <= 0 or NaN gives -1, and every descendant of a -1 node is -1
+ *   with root_states the root takes the given state (validated to lie in [0, D)); the root's uniform is then unused
+ * (the device searches the running maximum max(cum_0..cum_i), which gives the same i, also for rows with tiny negative entries).
+ * Three deviations from the reference:
+ *   1. x = u * total instead of x = u.  Rows sum to 1 within a few ulp; the reference returns index D, past the row, when u
+ *      exceeds the rounded sum.
+ *   2. u == 0 picks the first state of positive weight.
+ *   3. -1 (and -1 below it) replaces indexing with a bad state when a row has no positive total.
+ *   class_of_site   [n_rep][n_sites] rate class of each column; NULL: class 0 everywhere.  Category draws and HMM paths are the
+ *                   caller's: this call does not draw classes.
+ *   root_states     [n_rep][n_sites] state of the root of each column (the reference's spawnValues); NULL: drawn from pi
+ *   uniforms        [n_rep][L+I][n_sites] by node code (leaf l -> l, internal i -> L + i), each in [0, 1), validated before anything
+ *                   runs.  NULL: Philox4x32-10 as in hyphy_hip_sample_ancestral, key = (seed low 32 bits, seed high 32 bits),
+ *                   counter = (j, node code, r, 1), the same 53-bit conversion; the last counter word (sample_ancestral: 0) keeps
+ *                   the two streams disjoint under one seed.  A draw depends on (seed, r, j, node) only, not on chunks, slices
+ *                   or the sort of the columns by class
+ *   with_internal   0: states_out has the L leaf rows; otherwise the I internal rows follow them
+ *   states_out      [n_rep][L (+ I)][n_sites] signed bytes by node code; -1 or [0, D)
+ * Reads only the matrix images of the last evaluation of each referenced class (a class no column refers to need not have been
+ * evaluated) and the root frequencies currently on the device: no conditionals and no leaf data.  So it works behind a plain,
+ * lazy, class-compressed, re-rooted, generated, mixture or template pass, with a pin active, and after
+ * hyphy_hip_branch_cache_evaluate (the device keeps that trial matrix: it is the one simulated).  Which image: 4 states the
+ * row-major matrices; otherwise a leaf's branch from its column-gather image and an internal node's from its A-operand image,
+ * the image every writer of matrices leaves for that branch.  Multi-shard partitions use shard 0 (every shard holds every matrix).
+ * Leaves no state behind: matrices, images, schedules, tuner state, class tables, branch-cache slots, lazy-persistence flags and
+ * hyphy_hip_last_expm_kernel are unchanged, and two identical calls give identical arrays.  Scratch comes from the pool and is
+ * returned before the call returns: one table of cumulative rows per referenced class ((L+I) x DP x (DP+1) doubles, about 4 MB at
+ * 64 taxa x 61 states), and per column L+I bytes (plus L+I doubles with `uniforms`, and 4 bytes when more than one class is
+ * referenced); HYPHY_HIP_SIMULATE_MB (default 1024, read at every call) bounds the per-column part: a chunk is as many whole
+ * replicates as fit, otherwise site ranges of one replicate, at least one column.
+ * Returns < 0 on a NULL partition or output, a negative count or one above 2^31 - 1, a class id out of range, a referenced class
+ * never evaluated, a supplied uniform outside [0, 1) or a root state out of range; n_rep == 0 or n_sites == 0 returns 0 and
+ * writes nothing. */
+int hyphy_hip_simulate(hyphy_hip_partition *p, int64_t n_rep, int64_t n_sites,
+                       const int64_t *class_of_site /* [n_rep][n_sites] or NULL: class 0 */,
+                       const int64_t *root_states /* [n_rep][n_sites] or NULL: drawn from pi */, uint64_t seed,
+                       const double *uniforms /* [n_rep][L+I][n_sites] by node code, or NULL */, int with_internal,
+                       int8_t *states_out /* [n_rep][L (+ I)][n_sites] by node code */);
+/* host-only, no device: the uniforms the call above would use with uniforms == NULL, out[n_rep][n_nodes][n_sites] */
+int hyphy_hip_simulate_uniforms(uint64_t seed, int64_t n_rep, int64_t n_nodes, int64_t n_sites, double *out);
+
 /* ---- branch cache ---------------------------------------------------------------------
  * Replaces _TheTree::ComputeBranchCache (src/core/tree_evaluator.cpp:4286-4845) and
  * _TheTree::ComputeLLWithBranchCache (src/core/tree.cpp:3383-3936), driven by the policy code of
