@@ -62,8 +62,7 @@ int upload_small(Shard &s, const double *src, size_t n, double *dst) {
 
 // Sequence number for the result record of a synchronous evaluation (0: the caller must wait for the stream).
 double next_seq(Shard &s, bool host_record) {
-  static const bool spin = !(getenv("HYPHY_HIP_SPIN") && atoi(getenv("HYPHY_HIP_SPIN")) == 0);
-  if (!spin || !host_record || !s.d_hout) {
+  if (!sw::spin() || !host_record || !s.d_hout) {
     s.seq_wait = 0.;
     return 0.;
   }
@@ -108,7 +107,7 @@ int ensure_deposits(hyphy_hip_partition *p, Shard &s) {
   s.deposits_cap = need;
   s.deposits_class_stride = class_stride;
   s.dev_bytes += need * sizeof(double);
-  if (getenv("HYPHY_HIP_POISON")) {
+  if (sw::poison()) {
     HIPCHK(hipMemset(s.deposits, 0xff, need * sizeof(double)));
     HIPCHK(hipDeviceSynchronize());
   }
@@ -162,7 +161,7 @@ PruneArgs base_prune_args(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_b
   pa.cs_wg = (size_t)s.ntiles / s.T;
   pa.frag_ctr = s.frag_ctr;
   pa.hand_cnt = s.hand_cnt;
-  pa.wave_variant = getenv("HYPHY_HIP_WAVE_VARIANT") ? atoi(getenv("HYPHY_HIP_WAVE_VARIANT")) : p->wave_variant;
+  pa.wave_variant = sw::wave_variant(p->wave_variant);
   return pa;
 }
 
@@ -224,17 +223,17 @@ int EvalCtx::stage_pi() {  // root frequencies, zero padded (uploaded only when 
 }
 
 // 4 states: a schedule that keeps coming back runs as straight-line code compiled at run time (nucgen.hip) — requested after
-// nucgen_after() evaluations under it, used from the evaluation that finds it compiled; the interpreter until then and for
+// HYPHY_HIP_NUCGEN_AFTER evaluations under it, used from the evaluation that finds it compiled; the interpreter until then and for
 // everything the generator does not cover (pinned states, the trunk of a class-compressed partition, one-leaf entries)
 void EvalCtx::stage_gen_decision() {
   for (const auto &pr : p->programs) n_ops = std::max(n_ops, pr.n);
   if (!(p->nuc && p->mode == 0 && p->nucgen_key != 0 && n_ops > 0 && p->pin_node < 0 && p->nuc_leaf_pairs && p->programs.size() == 1 &&
         s.S_pad % 256 == 0))
     return;
-  const int gm = nucgen_mode();
+  const int gm = sw::nucgen();  // 0 off, 1 background compilation (default), 2 synchronous
   if (gm == 0) return;
   use_gen = nucgen_ready(p->nucgen_key);
-  if (!use_gen && (gm == 2 || ++p->nucgen_uses >= nucgen_after()) && !p->nucgen_asked) {
+  if (!use_gen && (gm == 2 || ++p->nucgen_uses >= sw::nucgen_after()) && !p->nucgen_asked) {
     p->nucgen_asked = true;
     nucgen_request(p->nucgen_key, p->ops_host.data() + p->programs[0].off, p->programs[0].n, (int)p->L, !p->cached_persist, p->nucgen_small, (int)p->B, gm == 2);
     use_gen = nucgen_ready(p->nucgen_key);
@@ -348,15 +347,14 @@ int EvalCtx::stage_expm_plain() {
   }
   ExpmArgs ea = expm_args_common(q_from_templates);  // (fused build: coefficients were staged by hyphy_hip_build_q)
   ea.Q = dq, ea.slots = d_slots(), ea.n = (int)n_mat, ea.is_prob = q_is_prob;
-  ea.prof = getenv("HYPHY_HIP_EXPM_PROF") ? 1 : 0;
+  ea.prof = sw::expm_prof_now() ? 1 : 0;
   if (p->nuc) {
     ea.Prow = s.Prow + (size_t)cat * B * 16;
     ea.PTrow = s.Prow + ((size_t)p->C * B + (size_t)cat * B) * 16;  // (transposed copies behind the row-major ones)
   } else {
     ea.Pfrag = s.Pfrag + (size_t)cat * B * DP * DP;
     ea.PTg = s.PTg + (size_t)cat * B * DP * DP;
-    static const bool mask_on = !(getenv("HYPHY_HIP_EXPM_MASK") && atoi(getenv("HYPHY_HIP_EXPM_MASK")) == 0);
-    if (mask_on && s.expm_need) {
+    if (sw::expm_mask() && s.expm_need) {
       ea.need = s.expm_need;
       ea.need_B = (int)B;
     }
@@ -390,7 +388,7 @@ int EvalCtx::stage_expm_plain() {
 // headline size): one evaluation in 16 by default — an optimiser's sweep should not pay for a profile nobody reads —,
 // HYPHY_HIP_TIMING_EVERY=n keeps one in n (bench.py: 4, the rocprofv3 runs: 1)
 int EvalCtx::stage_stamps_open() {
-  static const int timing_every = getenv("HYPHY_HIP_TIMING_EVERY") ? std::max(1, atoi(getenv("HYPHY_HIP_TIMING_EVERY"))) : 16;
+  const int timing_every = sw::timing_every();
   stamp = timing_every == 1 || p->all_timings || (s.eval_count++ % (uint64_t)timing_every) == 0;
   s.last_stamped = stamp;
   ring_slot = (size_t)(s.ring_count % kTimingRing) * 2;
@@ -448,8 +446,7 @@ int EvalCtx::stage_prune_nuc() {
     na.gtab = s.rep_tab + (size_t)cat * s.rep_rows * 4, na.gcnt = s.rep_cnt + (size_t)cat * s.rep_rows;
   }
   n_wg = prune_nuc_grid(na);
-  const char *fuse_env = getenv("HYPHY_HIP_FUSED_REDUCE");
-  if (!(fuse_env && atoi(fuse_env) == 0) && p->mode == 0 && fused_combine_allowed() &&
+  if (sw::fused_reduce() != 0 && p->mode == 0 && fused_combine_allowed() &&
       (use_gen ? p->nucgen_small : prune_nuc_fuses_reduce(na, have_folded)))
     wire_fused_combine(na, s.wg_flag + (size_t)p->C * s.wg_cap + 3);  // (the spare words behind the flags; zeroed at creation)
   const ExpmArgs *folded = have_folded ? &folded_expm : nullptr;
@@ -502,7 +499,7 @@ int EvalCtx::dump_timeline(const Timeline &tl) {
 int EvalCtx::stage_prune_mfma() {
   PruneArgs pa = prune_args_current(p, s, cat, n_cat_batch);
   const size_t tl_waves = (size_t)s.ntiles * std::max(1, n_cat_batch) * std::max<size_t>(1, p->programs.size());
-  Timeline tl{getenv("HYPHY_HIP_TIMELINE"), p->variant == 1, tl_waves,
+  Timeline tl{sw::timeline(), p->variant == 1, tl_waves,
               p->variant == 1 ? tl_waves * 24 : (size_t)kTraceWG * p->NW * std::max(1, n_ops) * 4, nullptr};
   if (tl.path && n_ops > 0 && s.T == 1) {
     HIPCHK(pool_malloc((void **)&tl.buf, tl.n * sizeof(long long)));
@@ -513,11 +510,11 @@ int EvalCtx::stage_prune_mfma() {
   // The fused combine saves 1.5-3 us per evaluation of a small shard (below two tiles per CU; 64 x 1 250: 69.1 -> 67.7 us, 32 x 5 000:
   // 79.8 -> 77.0); at the headline size the gain shrinks to ~1 us while the pruning kernel's own duration grows by the 3-4 us of the
   // serial tail, so larger shards keep the separate kernel.  HYPHY_HIP_FUSED_REDUCE=0/1 forces either.
-  const char *fuse_env = getenv("HYPHY_HIP_FUSED_REDUCE");
+  const int fuse_forced = sw::fused_reduce();
   const bool walk = trunk_walk_applies(p, s) && !pa.timeline && n_ops > 0;  // (the trunk as one row-split walk per tile, repeats.hip)
-  const bool fuse_on = fuse_env ? atoi(fuse_env) != 0 : s.ntiles <= 2 * s.cus;  // (the walk at the headline: 90.0 / 89.8 us fused, 88.3 / 89.5 not)
+  const bool fuse_on = fuse_forced >= 0 ? fuse_forced != 0 : s.ntiles <= 2 * s.cus;  // (the walk at the headline: 90.0 / 89.8 us fused, 88.3 / 89.5 not)
   if (fuse_on && fused_combine_allowed() && !pa.timeline &&
-      (walk ? (trunk_walk_fuses_reduce(p) && !getenv("HYPHY_HIP_WALK_TIMELINE")) : prune_fuses_reduce(pa))) {
+      (walk ? (trunk_walk_fuses_reduce(p) && !sw::walk_timeline()) : prune_fuses_reduce(pa))) {
     wire_fused_combine(pa, s.frag_ctr + (size_t)p->C * (p->I + 2) * s.ntiles - 1);  // (a word of the arrival counters no schedule indexes; zero between launches)
     pa.red_n = n_wg;
   }
@@ -610,7 +607,7 @@ int prepare_schedule(hyphy_hip_partition *p, int cat, const int64_t *update_node
   // (small-shard form — matrices in LDS, exponentials and final combine inside the launch — for shards of at most two workgroups
   //  per CU: the interpreter's LP rule; HYPHY_HIP_NUCGEN_SMALL=0/1 forces either)
   p->nucgen_small = !p->shards.empty() && p->shards[0].S_pad / 256 <= 2 * p->shards[0].cus && p->B <= 1024;
-  if (const char *e = getenv("HYPHY_HIP_NUCGEN_SMALL")) p->nucgen_small = atoi(e) != 0 && p->B <= 1024;
+  if (const int f = sw::nucgen_small(); f >= 0) p->nucgen_small = f != 0 && p->B <= 1024;
   p->nucgen_key = (p->nuc && p->mode == 0 && full && p->programs.size() == 1 && p->L <= 256)
                       ? nucgen_key(p->ops_host.data() + p->programs[0].off, p->programs[0].n, (int)p->L, !persist_all, p->nucgen_small, (int)p->B) : 0;
   p->nucgen_uses = 0;
@@ -622,7 +619,7 @@ int prepare_schedule(hyphy_hip_partition *p, int cat, const int64_t *update_node
 
 // Wait for every shard and read its host-mapped result record [log-L, scaler sum, status].
 int collect_status(hyphy_hip_partition *p) {
-  static const bool expm_prof = getenv("HYPHY_HIP_EXPM_PROF") != nullptr;
+  const bool expm_prof = sw::expm_prof();
   for (Shard &s : p->shards) {
     HIPCHK(hipSetDevice(s.device));
     if (!s.d_hout) HIPCHK(hipMemcpyAsync(s.h_out, s.out, 3 * sizeof(double), hipMemcpyDeviceToHost, s.stream));
@@ -703,10 +700,8 @@ namespace {
 // HYPHY_HIP_SITE_EXPORT=0 keeps the copies of gather_sites) ...
 int begin_site_export(hyphy_hip_partition *p, bool want_lik, bool want_cnt) {
   if (!p) return 0;
-  const char *env = getenv("HYPHY_HIP_SITE_EXPORT");  // (read per call: the tests run both paths in one process)
-  const bool on = !(env && atoi(env) == 0);
   p->export_sites = 0;
-  if (!on || p->shards.size() != 1 || !(want_lik || want_cnt)) return 0;
+  if (!sw::site_export() || p->shards.size() != 1 || !(want_lik || want_cnt)) return 0;
   Shard &s = p->shards[0];
   if (s.S <= 0 || s.s0 != 0) return 0;
   HIPCHK(hipSetDevice(s.device));
@@ -845,6 +840,14 @@ int64_t hyphy_hip_prune_timings(hyphy_hip_partition *p, double *out_ms, int64_t 
 }
 const char *hyphy_hip_version(void) { return "hyphy_hip 0.1 (gfx950, FP64 MFMA)"; }
 
+int64_t hyphy_hip_plan_switches(char *out, int64_t cap) {
+  const std::string t = sw::plan_text();
+  const int64_t need = (int64_t)t.size() + 1;  // (with the terminating zero)
+  if (!out || cap < need) return -need;
+  memcpy(out, t.c_str(), (size_t)need);
+  return need;
+}
+
 int hyphy_hip_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -880,8 +883,7 @@ int hyphy_hip_create(hyphy_hip_partition **out, int64_t D, int64_t S, int64_t L,
   }
   int ndev = hyphy_hip_device_count();
   if (ndev <= 0) return fail("no HIP device available (this library has no CPU fallback)");
-  int force = 0;
-  if (const char *e = getenv("HYPHY_HIP_FORCE_SHARDS")) force = atoi(e);
+  const int force = sw::force_shards();
   if (device_count < 1) device_count = 1;
   if (!force && (device_first < 0 || device_first + device_count > ndev)) return fail("device range out of bounds");
   if (force > 0 && device_first >= ndev) return fail("device out of bounds");
@@ -910,7 +912,7 @@ int hyphy_hip_create(hyphy_hip_partition **out, int64_t D, int64_t S, int64_t L,
   p->bc_use_pi.assign(C, 0);
   p->resident.assign(C, 0);
   p->last_full.assign(C, 0);
-  if (const char *e = getenv("HYPHY_HIP_CACHE")) p->cache_policy = strcmp(e, "always") == 0 ? 0 : 1;
+  p->cache_policy = sw::cache_always() ? 0 : 1;
   p->leaf_has_ambig.assign(L, 0);
   for (int64_t l = 0; l < L; l++)
     for (int64_t k = 0; k < S; k++)
@@ -921,10 +923,8 @@ int hyphy_hip_create(hyphy_hip_partition **out, int64_t D, int64_t S, int64_t L,
 
   const int DP = p->DP;
   const int64_t B = p->B;
-  int tiles_override = 0;
-  if (const char *e = getenv("HYPHY_HIP_TILES")) tiles_override = atoi(e);
-  if (!p->nuc && !(getenv("HYPHY_HIP_SORT_PATTERNS") && atoi(getenv("HYPHY_HIP_SORT_PATTERNS")) == 0))
-    sort_patterns(p, leaf_codes, L, S);
+  const int tiles_override = sw::tiles();
+  if (!p->nuc && sw::sort_patterns()) sort_patterns(p, leaf_codes, L, S);
   init_plain_view(p);
   if (!p->nuc && C == 1) reroot_path(p);
   auto src_pattern = [&](int64_t j) -> int64_t { return p->perm.empty() ? j : p->perm[j]; };
@@ -972,8 +972,8 @@ int hyphy_hip_create(hyphy_hip_partition **out, int64_t D, int64_t S, int64_t L,
       //  keeps its shorter critical path.  The schedule tuner re-checks the choice on the first steady-state pass.)
       p->variant = tiles >= (int64_t)cus / 4 ? 1 : 0;
       p->kernel_forced = false;
-      if (const char *e = getenv("HYPHY_HIP_KERNEL")) {  // (diagnostic override)
-        p->variant = std::max(0, std::min(2, atoi(e)));  // 0: workgroup per tile, 1: wave per tile, 2: workgroup per tile on chain schedules
+      if (const int k = sw::kernel(); k >= 0) {  // (diagnostic override)
+        p->variant = k;  // 0: workgroup per tile, 1: wave per tile, 2: workgroup per tile on chain schedules
         p->kernel_forced = true;
       }
       if (T != 1) {
@@ -986,7 +986,7 @@ int hyphy_hip_create(hyphy_hip_partition **out, int64_t D, int64_t S, int64_t L,
         const size_t tile_bytes = (size_t)p->NW * 4 * 64 * sizeof(double), codes_bytes = (size_t)p->L * 16 * sizeof(int16_t);
         p->n_slots_wave = 2 * tile_bytes + codes_bytes <= 20480 ? 4 : 3;
       }
-      if (const char *e = getenv("HYPHY_HIP_SLOTS")) p->n_slots_wave = std::max(2, std::min(4, atoi(e)));
+      if (const int n = sw::slots()) p->n_slots_wave = n;
       p->n_slots = p->variant == 1 ? p->n_slots_wave : lds_slots(T);
     }
     if (p->nuc) {
@@ -1000,7 +1000,7 @@ int hyphy_hip_create(hyphy_hip_partition **out, int64_t D, int64_t S, int64_t L,
     }
     // HYPHY_HIP_POISON=1 (tests): fill every fresh allocation with 0xff bytes (NaN / -1), so that anything read before
     // it is written shows up even in a process whose recycled device memory happens to hold zeros
-    const bool poison = getenv("HYPHY_HIP_POISON") != nullptr;
+    const bool poison = sw::poison();
 #define A_(ptr, n)                                                                                           \
   {                                                                                                          \
     if (pool_malloc((void **)&(ptr), (n)) != hipSuccess) {                                                     \
@@ -1008,7 +1008,7 @@ int hyphy_hip_create(hyphy_hip_partition **out, int64_t D, int64_t S, int64_t L,
       return fail("hipMalloc failed (" #ptr ")");                                                            \
     }                                                                                                        \
     s.dev_bytes += (size_t)(n);                                                                              \
-    if (poison && !getenv("HYPHY_HIP_NOPOISON_" #ptr)) {                                                     \
+    if (poison && !sw::nopoison(#ptr)) {                                                                    \
       hipMemset((ptr), 0xff, (n));                                                                           \
       hipDeviceSynchronize();                                                                                \
     }                                                                                                        \
@@ -1116,8 +1116,7 @@ int hyphy_hip_create(hyphy_hip_partition **out, int64_t D, int64_t S, int64_t L,
     hipMemcpy(s.freq, fr.data(), fr.size() * sizeof(double), hipMemcpyHostToDevice);
     hipMemcpy(s.ambig, amb.data(), amb.size() * sizeof(double), hipMemcpyHostToDevice);
     {  // (the host copy is only kept for the class computation of subtree repeats)
-      const char *re = getenv("HYPHY_HIP_REPEATS");
-      if (re && atoi(re) == 0) std::vector<int16_t>().swap(shard_codes.back());
+      if (sw::repeats() == 0) std::vector<int16_t>().swap(shard_codes.back());
     }
     if (hipStreamSynchronize(s.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
       hyphy_hip_destroy(p);
@@ -1230,12 +1229,12 @@ int eval_common(hyphy_hip_partition *p, const EvalRequest &rq) {
   }
   // the view this evaluation runs under: the class-compressed one wherever it exists, except with pinned states and for the
   // internal passes that restore the per-pattern copies of every node (branch cache, downloads)
-  if (p->rep_on && p->rep_enabled && !p->rep_decided && !getenv("HYPHY_HIP_REPEATS") && getenv("HYPHY_HIP_TUNE") && atoi(getenv("HYPHY_HIP_TUNE")) == 0) {
+  if (p->rep_on && p->rep_enabled && !p->rep_decided && !sw::given(sw::REPEATS) && !sw::tune()) {
     //  no measurement will ever settle on / off for this partition (the tuner is disabled): the static rule instead
     p->rep_decided = true;
     if (!rep_static_decision(p)) p->rep_enabled = false;
     p->rep_report = std::string("repeats: no measurement (HYPHY_HIP_TUNE=0), static rule -> ") + (p->rep_enabled ? "on" : "off");
-    if (getenv("HYPHY_HIP_VERBOSE")) fprintf(stderr, "[hyphy_hip] %s\n", p->rep_report.c_str());
+    sw::note("%s\n", p->rep_report.c_str());
   }
   // New root frequencies and nothing to update: ComputeBlock applies theProbs at the root on every call, while the stored per-pattern
   // values hold the old ones — one child of the root is listed, so the root is combined again from all of its children.  (Per class:
@@ -1256,13 +1255,12 @@ int eval_common(hyphy_hip_partition *p, const EvalRequest &rq) {
   }
   if (prepare_schedule(p, (int)cat, update_nodes, n_update, &changed, force_persist, q_nodes, n_q, batch ? (int)p->C : 1)) return -1;
   {
-    const bool tune_on = p->tuned_for != p->batch_classes && !(getenv("HYPHY_HIP_TUNE") && atoi(getenv("HYPHY_HIP_TUNE")) == 0) && !getenv("HYPHY_HIP_CHAIN_M") &&
-                                !getenv("HYPHY_HIP_CUT") && !getenv("HYPHY_HIP_FRAGMENT");
+    const bool tune_on = p->tuned_for != p->batch_classes && sw::tune() && !sw::schedule_forced();
     if (tune_on && !p->nuc && (p->variant >= 1 || (!p->kernel_forced && p->shards[0].ntiles >= 32)) && p->shards[0].T == 1 && p->sched_full && !p->sched_persist &&
         p->tuned_for != p->batch_classes && p->initialized[cat]) {
       if (tune_schedule(p, (int)cat, batch ? (int)p->C : 1)) return -1;
       // class-compressed or plain?  settled once per partition by timing both (repeats.hip), unless the caller or the environment chose
-      if (p->mode == 1 && !p->rep_decided && !getenv("HYPHY_HIP_REPEATS") && rep_decide(p, (int)cat, batch ? (int)p->C : 1)) return -1;
+      if (p->mode == 1 && !p->rep_decided && !sw::given(sw::REPEATS) && rep_decide(p, (int)cat, batch ? (int)p->C : 1)) return -1;
       build_schedule(p, nullptr, 0, true);  // the chosen cut (a full pass: no update list)
       if (p->ops_host.size() > ops_capacity(p)) return fail("internal: schedule overflow");
       changed = true;
@@ -1936,7 +1934,7 @@ int hyphy_hip_build_q(hyphy_hip_partition *p, int64_t n, const double *coeffs) {
   // When the matrices are consumed by the next hyphy_hip_evaluate_device(q_buffer) — the normal use —
   // the construction is fused into the expm kernel (no Q round trip through HBM, one launch less).
   // HYPHY_HIP_MATERIALIZE_Q=1 keeps the stand-alone kernel so that q_buffer can be read back.
-  const bool fuse = getenv("HYPHY_HIP_MATERIALIZE_Q") == nullptr;
+  const bool fuse = !sw::materialize_q();
   for (Shard &s : p->shards) {
     HIPCHK(hipSetDevice(s.device));
     const size_t nbytes = (size_t)n * p->K * sizeof(double);

@@ -53,8 +53,7 @@ int combine_shards(hyphy_hip_partition *p, double *logl_out, bool allow_rccl) {
   for (Shard &s : p->shards) parts.push_back(s.h_out[0]);
   *logl_out = combine(parts);
   if (!allow_rccl) return 0;  // (these entry points never read the switch)
-  const char *mode = getenv("HYPHY_HIP_COMBINE");
-  if (!(mode && !strcmp(mode, "rccl") && p->shards[0].comm)) return 0;
+  if (!(sw::combine_rccl() && p->shards[0].comm)) return 0;
   for (Shard &s : p->shards) {
     HIPCHK(hipSetDevice(s.device));
     HIPCHK(hipMemcpyAsync(s.ar_buf, &s.h_out[0], sizeof(double), hipMemcpyHostToDevice, s.stream));
@@ -107,10 +106,6 @@ static double xch_now() {
   clock_gettime(CLOCK_MONOTONIC, &t);
   return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
 }
-static double xch_timeout_s() {
-  const char *e = getenv("HYPHY_HIP_EXCHANGE_TIMEOUT_S");
-  return e ? atof(e) : 120.;
-}
 
 HostExchange *xch_open(const char *name, int rank, int n_ranks) {
   if (!name || !*name || n_ranks < 1 || rank < 0 || rank >= n_ranks) {
@@ -154,7 +149,7 @@ HostExchange *xch_open(const char *name, int rank, int n_ranks) {
     __atomic_store_n(&mine.epoch, (uint64_t)0, __ATOMIC_RELAXED);
     __atomic_store_n(&mine.ready, nonce, __ATOMIC_RELEASE);
   }
-  const double t0 = xch_now(), limit = xch_timeout_s();
+  const double t0 = xch_now(), limit = sw::exchange_timeout_s();
   for (int r = 0; r < n_ranks; r++)
     for (int b = 0; b < 2; b++)
       while (__atomic_load_n(&x->slots[(size_t)b * n_ranks + r].ready, __ATOMIC_ACQUIRE) != nonce) {
@@ -185,7 +180,7 @@ int xch_sum(HostExchange *x, double local, bool local_failed, double *sum_out) {
   row[x->rank].value = local_failed ? NAN : local;
   __atomic_store_n(&row[x->rank].epoch, e, __ATOMIC_RELEASE);
   std::vector<double> parts((size_t)x->n);
-  const double limit = xch_timeout_s();
+  const double limit = sw::exchange_timeout_s();
   double t0 = 0.;
   for (int r = 0; r < x->n; r++) {
     for (long spins = 1; __atomic_load_n(&row[r].epoch, __ATOMIC_ACQUIRE) != e; spins++) {

@@ -238,8 +238,6 @@ struct NucGenExpm {          // what the small-shard form reads of ExpmArgs (dec
   int K;
   int coef_inline;
 };
-int nucgen_mode();                                     // HYPHY_HIP_NUCGEN: 0 off, 1 background compilation (default), 2 synchronous
-int nucgen_after();                                    // evaluations under one schedule before its kernel is requested
 uint64_t nucgen_key(const int4 *ops, int n_ops, int L, bool lazy, bool small, int n_branches);
 void nucgen_request(uint64_t key, const int4 *ops, int n_ops, int L, bool lazy, bool small, int n_branches, bool sync);
 bool nucgen_ready(uint64_t key);

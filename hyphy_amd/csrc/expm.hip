@@ -13,6 +13,7 @@
 // (SURVEY §2.1 K10).  With ||Q/2^p|| <= 1/4 the truncation error is < 2.5e-18.
 #include "common.h"
 #include "expm4.h"
+#include "switches.h"
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
@@ -1075,9 +1076,8 @@ void expm_read_profile(long long out[8]) { hipMemcpyFromSymbol(out, HIP_SYMBOL(g
 // view of the (host-mapped) ring slot and is dereferenced HERE, by the caller's thread — staged before this call
 // (hyphy_hip_build_q).  true: the launch no longer reads the ring slot.
 bool fill_coef_inline(ExpmArgs &b, CoefInline &ci) {
-  static const int coef_mode = getenv("HYPHY_HIP_COEF_INLINE") ? atoi(getenv("HYPHY_HIP_COEF_INLINE")) : 1;
   b.coef_inline = 0;
-  if (b.templates && b.coeffs_host && coef_mode && (size_t)b.n * b.K <= (size_t)kCoefInline) {
+  if (b.templates && b.coeffs_host && sw::coef_inline() && (size_t)b.n * b.K <= (size_t)kCoefInline) {
     memcpy(ci.c, b.coeffs_host, (size_t)b.n * b.K * sizeof(double));
     b.coef_inline = 1;
   }
@@ -1123,7 +1123,7 @@ bool launch_expm(const ExpmArgs &a, hipStream_t stream) {
       hipLaunchKernelGGL((expm_mfma_kernel<3, 1>), dim3(a.n), dim3(192), lds, stream, a);
       break;
     default: {
-      static const int mode = getenv("HYPHY_HIP_EXPM") ? atoi(getenv("HYPHY_HIP_EXPM")) : -1;  // 0: r02 kernel; 1/2/4: panels forced
+      const int mode = sw::expm();  // 0: r02 kernel; 1/2/4: panels forced
       if (mode == 0) {
         if (!attr_done[dev][4]) {
           hipFuncSetAttribute(reinterpret_cast<const void *>(expm_mfma_kernel<4, 2>),
@@ -1157,8 +1157,7 @@ bool launch_expm(const ExpmArgs &a, hipStream_t stream) {
       // Coefficients of the fused construction in the kernel-argument block when they fit: `coeffs` is host-mapped
       // memory and is dereferenced HERE, on the host — the caller staged it before this call (hyphy_hip_build_q).
       ExpmArgs b = a;
-      static const bool fixed12 = getenv("HYPHY_HIP_EXPM_DEGREE") && atoi(getenv("HYPHY_HIP_EXPM_DEGREE")) == 12;
-      b.fixed_degree = fixed12 ? 1 : 0;
+      b.fixed_degree = sw::expm_degree12() ? 1 : 0;
       CoefInline ci;
       if (b.templates_pad) fill_coef_inline(b, ci);
       t_last_expm_kernel = H == 4 ? "expm64_kernel<4>" : (H == 2 ? "expm64_kernel<2>" : "expm64_kernel<1>");

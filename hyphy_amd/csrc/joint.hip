@@ -410,7 +410,7 @@ int hyphy_hip_joint_ancestral(hyphy_hip_partition *p, int do_leaves, const int64
     for (int64_t c = 0; c < L + I - 1; c++) kids[(size_t)fill[(size_t)p->parents[(size_t)c]]++] = (int32_t)c;
   }
   const std::vector<double> pi_pad = padded_pi(p);
-  const double budget = scratch_budget("HYPHY_HIP_JOINT_MB");
+  const double budget = sw::scratch_budget(sw::JOINT_MB);
   const int TP = nuc ? 64 : 16;                                                  // patterns of a tile
   const size_t tile_msg = nuc ? (size_t)4 * 64 : (size_t)16 * DP;                // doubles of one node's msg per tile
   const size_t tile_bp = nuc ? (size_t)64 : (size_t)64 * NW;                     // words of its backpointers

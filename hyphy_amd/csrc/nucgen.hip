@@ -71,8 +71,6 @@ Rtc &rtc() {
   return r;
 }
 
-bool verbose() { return getenv("HYPHY_HIP_VERBOSE") != nullptr; }
-
 // ---- the generator ------------------------------------------------------------------------------------------------------------
 const char *kPrologue = R"SRC(
 typedef double f64x2 __attribute__((ext_vector_type(2)));
@@ -359,7 +357,7 @@ void compile_entry(std::shared_ptr<GenEntry> en, std::string src, uint64_t key) 
       r.destroy(&prog);
     }
   }
-  if (const char *dump = getenv("HYPHY_HIP_NUCGEN_DUMP")) {  // diagnostic: the generated source (and, beside it, the code object)
+  if (const char *dump = sw::nucgen_dump()) {  // diagnostic: the generated source (and, beside it, the code object)
     char path[512];
     snprintf(path, sizeof path, "%s/nucgen_%016llx.hip", dump, (unsigned long long)key);
     if (FILE *f = fopen(path, "w")) {
@@ -381,22 +379,11 @@ void compile_entry(std::shared_ptr<GenEntry> en, std::string src, uint64_t key) 
     en->state = en->code.empty() ? -1 : 1;
   }
   g_cv.notify_all();
-  if (verbose()) {
-    if (en->state == 1) fprintf(stderr, "[hyphy_hip] nucgen: kernel %016llx compiled (%zu bytes of source, %zu of code object)\n", (unsigned long long)key, src.size(), en->code.size());
-    else fprintf(stderr, "[hyphy_hip] nucgen: kernel %016llx NOT available (%s): the interpreter stays\n", (unsigned long long)key, err.c_str());
-  }
+  if (en->state == 1) sw::note("nucgen: kernel %016llx compiled (%zu bytes of source, %zu of code object)\n", (unsigned long long)key, src.size(), en->code.size());
+  else sw::note("nucgen: kernel %016llx NOT available (%s): the interpreter stays\n", (unsigned long long)key, err.c_str());
 }
 
 }  // namespace
-
-int nucgen_mode() {  // 0 off, 1 background compilation (default), 2 synchronous
-  const char *e = getenv("HYPHY_HIP_NUCGEN");
-  return e ? atoi(e) : 1;
-}
-int nucgen_after() {
-  const char *e = getenv("HYPHY_HIP_NUCGEN_AFTER");
-  return e ? std::max(1, atoi(e)) : 8;
-}
 
 uint64_t nucgen_key(const int4 *ops, int n_ops, int L, bool lazy, bool small, int n_branches) {
   // (the source is a function of the entries and L alone: hash those, generate only when a kernel is actually requested)
@@ -462,7 +449,7 @@ static hipFunction_t nucgen_function(uint64_t key) {
     (void)hipGetLastError();
     en.state = -1;
     en.error = "hipModuleLoadData failed";
-    if (verbose()) fprintf(stderr, "[hyphy_hip] nucgen: kernel %016llx could not be loaded: the interpreter stays\n", (unsigned long long)key);
+    sw::note("nucgen: kernel %016llx could not be loaded: the interpreter stays\n", (unsigned long long)key);
     return nullptr;
   }
   en.loaded[dev] = std::make_pair(mod, fn);

@@ -3,6 +3,7 @@
 //   schedule.hip  the schedule compiler (post-order programs, chain / level-peeled cuts, re-rooting, pattern order)
 //   tuner.hip     the run-time schedule tuner and the launch of the current schedule
 //   comm.hip      RCCL (loaded on first use) and the all-reduce entry points
+// The environment is read in switches.h alone (sw::...): one table row and one accessor per HYPHY_HIP_* switch.
 // Host-side bookkeeping only — all arithmetic of the hot path happens in expm.hip / prune.hip / sitefit.hip.
 // An evaluation: an entry point fills an EvalRequest by name, eval_common validates it and settles the schedule, enqueue_eval
 // (api.hip) runs its stages per shard over one stack context, and result_tail collects.  The schedule upload and the pruning
@@ -21,6 +22,7 @@
 
 #include "../../include/hyphy_hip.h"
 #include "common.h"
+#include "switches.h"
 
 namespace hyhip {
 
@@ -75,7 +77,7 @@ struct Trace {
     clock_gettime(CLOCK_MONOTONIC, &ts);
     return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3;
   }
-  explicit Trace(const char *w) : on(getenv("HYPHY_HIP_TRACE") != nullptr), t0(0), what(w) {
+  explicit Trace(const char *w) : on(sw::trace()), t0(0), what(w) {
     if (on) t0 = now();
   }
   void lap(const char *stage) {
@@ -372,7 +374,7 @@ struct hyphy_hip_partition {
   std::vector<Level> levels;                 // launches: programs [first, first+count) run concurrently
   int64_t batch_classes = 1;                 // rate classes batched into the pruning launch being scheduled
   int slots_batch_mode = -1;                 // whether the slot table on the device was written for a class batch
-  bool all_timings = getenv("HYPHY_HIP_ALL_TIMINGS") != nullptr;  // also stamp expm / reduction (2 more event records)
+  bool all_timings = hyhip::sw::all_timings();  // also stamp expm / reduction (2 more event records)
   bool coeffs_pending = false;               // build_q staged coefficients; the next evaluate_device(q_buffer) fuses
                                              // the rate-matrix construction into the expm kernel
   int64_t K = 0;                             // Q templates
@@ -428,12 +430,6 @@ inline std::vector<double> padded_pi(const hyphy_hip_partition *p) {
   std::vector<double> pi((size_t)(p->nuc ? 4 : p->DP), 0.);
   std::copy(p->cached_pi.begin(), p->cached_pi.begin() + p->D, pi.begin());
   return pi;
-}
-
-// a scratch budget in bytes from an environment variable in MB (read per call; default 1024, also for anything not positive)
-inline double scratch_budget(const char *env) {
-  const char *mb = getenv(env);
-  return (mb && atof(mb) > 0. ? atof(mb) : 1024.) * 1048576.;
 }
 
 // rows of a shard's result on the host (pattern k of the shard, or list[k], at src[row * stride + k], k < n) into the caller's pattern

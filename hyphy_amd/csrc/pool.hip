@@ -22,12 +22,7 @@ Pool &pool() {
   return *p;
 }
 size_t cap_bytes() {
-  static const size_t cap = [] {
-    const char *e = getenv("HYPHY_HIP_POOL_MB");
-    const long mb = e ? atol(e) : 1024;
-    return (size_t)(mb < 0 ? 0 : mb) << 20;  // (a negative value means "off", not 2^64 bytes)
-  }();
-  return cap;
+  return sw::pool_cap_bytes();
 }
 constexpr size_t kMaxCachedBlock = (size_t)64 << 20;
 

@@ -22,6 +22,7 @@
 #include "devutil.h"
 #include "expm4.h"
 #include "combine.h"
+#include "switches.h"
 
 #ifndef HYPHY_OCC
 #define HYPHY_OCC 3  // waves per SIMD the T = 1 pruning kernel is compiled for
@@ -2171,9 +2172,7 @@ int launch_prune_T(const PruneArgs &a, hipStream_t stream) {
   // tile dimension padded to a multiple of 8 (the surplus workgroups retire at once) every chain of a tile — and so every
   // join of its trunk — sits on ONE XCD: deposits and arrival counters are then L2 hits instead of trips to memory.
   // (HYPHY_HIP_XCD_PAD=0: the bare tile count.)
-  const char *pad_env = getenv("HYPHY_HIP_XCD_PAD");  // (read per launch: the tests run both placements in one process)
-  const bool xcd_pad = !(pad_env && atoi(pad_env) == 0);
-  const int gx_chain = (a.chain && a.T == 1 && xcd_pad && !a.timeline) ? ((a.ntiles + 7) & ~7) : a.ntiles / a.T;
+  const int gx_chain = (a.chain && a.T == 1 && sw::xcd_pad() && !a.timeline) ? ((a.ntiles + 7) & ~7) : a.ntiles / a.T;
   const dim3 grid(a.chain ? gx_chain : a.ntiles / a.T, a.n_cat > 0 ? a.n_cat : 1, a.n_prog > 0 ? a.n_prog : 1), block(64 * NW);
   const size_t lds = CLDS ? (size_t)a.L * a.T * 16 * sizeof(int16_t) : 0;
   const dim3 gridw = a.chain ? dim3(gx_chain, a.n_cat > 0 ? a.n_cat : 1, a.n_prog > 0 ? a.n_prog : 1)   // chains: source-major
@@ -2297,10 +2296,7 @@ int launch_prune_mfma(const PruneArgs &a, hipStream_t stream) {
 }
 
 // prune_nuc2_kernel: NP patterns per thread while the leaf matrices (128 bytes each) and the parking slots fit LDS
-static int nuc_forced() {
-  static const int forced = getenv("HYPHY_HIP_NUC") ? atoi(getenv("HYPHY_HIP_NUC")) : -1;  // 0: r02 kernel, 1 / 2: patterns per thread
-  return forced;
-}
+static int nuc_forced() { return sw::nuc(); }  // 0: r02 kernel, 1 / 2: patterns per thread
 bool prune_nuc_takes_leaf_pairs(int L) { return nuc_forced() != 0 && L <= 256; }
 static int nuc2_np(const NucArgs &a) {
   const int forced = nuc_forced();
@@ -2320,9 +2316,9 @@ static bool nuc_uses_lp(const NucArgs &a, int np, bool folded, int dev) {
     hipDeviceProp_t pr;
     cus_n[dev] = (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
   }
-  const char *lp_env = getenv("HYPHY_HIP_NUC_LP");
+  const int lp_forced = sw::nuc_lp();
   (void)folded;
-  return np == 1 && (lp_env ? atoi(lp_env) != 0 : a.S_pad / 256 <= 2 * cus_n[dev]) && nuc2_lds(a, 1, true) <= (size_t)(112 * 1024);
+  return np == 1 && (lp_forced >= 0 ? lp_forced != 0 : a.S_pad / 256 <= 2 * cus_n[dev]) && nuc2_lds(a, 1, true) <= (size_t)(112 * 1024);
 }
 
 // true when launch_prune_nuc can take the evaluation's matrix exponentials along (ex != nullptr): the r03 kernel on a shard of
@@ -2330,9 +2326,7 @@ static bool nuc_uses_lp(const NucArgs &a, int np, bool folded, int dev) {
 bool prune_nuc_folds_expm(int L, int S_pad, int n_ops) {
   // (late r03: on by default — with the Paterson-Stockmeyer 4 x 4 exponential and the coefficients in the kernel-argument block the
   //  folded launch is 41 us per step at 50 000 sites against 42.5-43 with a launch of its own; HYPHY_HIP_NUC_FOLD=0 turns it off)
-  const char *fe = getenv("HYPHY_HIP_NUC_FOLD");
-  const bool on = !(fe && atoi(fe) == 0);
-  return on && n_ops > 0 && prune_nuc_takes_leaf_pairs(L) && nuc_forced() != 2 && S_pad % 256 == 0 && S_pad / 256 <= 512;
+  return sw::nuc_fold() && n_ops > 0 && prune_nuc_takes_leaf_pairs(L) && nuc_forced() != 2 && S_pad % 256 == 0 && S_pad / 256 <= 512;
 }
 
 // true when launch_prune_nuc will pick the LDS-schedule instantiation (LP) — the one that can also carry the fused final
@@ -2439,8 +2433,8 @@ void launch_site_reduce(const double *site_lik, const int32_t *site_cnt, const d
 
 void launch_wg_reduce(const double *wg_sum, const long long *wg_cnt, const int *wg_flag, int n, double *out_logl,
                       double *out_cnt, const int *status, hipStream_t stream, double seq) {
-  static const bool block_form = getenv("HYPHY_HIP_REDUCE") && !strcmp(getenv("HYPHY_HIP_REDUCE"), "block");
-  static const bool multi_off = getenv("HYPHY_HIP_REDUCE") && !strcmp(getenv("HYPHY_HIP_REDUCE"), "wave");
+  const int form = sw::reduce_form();
+  const bool block_form = form == 1, multi_off = form == 2;
   if (block_form)
     hipLaunchKernelGGL(wg_reduce_kernel, dim3(1), dim3(256), 0, stream, wg_sum, wg_cnt, wg_flag, n, out_logl, out_cnt, status, seq);
   else if (n >= 2048 && !multi_off)

@@ -1182,7 +1182,7 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
 int rep_setup(hyphy_hip_partition *p, const std::vector<std::vector<int16_t>> &codes) {
   const int rc = rep_setup_impl(p, codes);
   if (rc != 0 || !p->rep_on) {
-    if (rc != 0 && getenv("HYPHY_HIP_VERBOSE")) fprintf(stderr, "[hyphy_hip] subtree repeats not set up (%s): plain evaluation\n", g_last_error.c_str());
+    if (rc != 0) sw::note("subtree repeats not set up (%s): plain evaluation\n", g_last_error.c_str());
     rep_release(p);
     (void)hipGetLastError();
     g_last_error.clear();
@@ -1336,8 +1336,7 @@ int rep_setup_nuc(hyphy_hip_partition *p, const std::vector<std::vector<int16_t>
     {
       size_t free_b = 0, total_b = 0, limit = (size_t)1 << 30;
       const size_t need_b = (size_t)p->C * rows * 36 + maps.size() * 4 + ct.size() * 2;
-      if (const char *e = getenv("HYPHY_HIP_REP_MAX_MB")) limit = (size_t)std::max(0L, atol(e)) << 20;
-      else if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) limit = free_b / 4;
+      if (!sw::rep_max_mb(&limit) && hipMemGetInfo(&free_b, &total_b) == hipSuccess) limit = free_b / 4;
       if (need_b > limit) return fail("class tables would take more than a quarter of the free device memory (or than HYPHY_HIP_REP_MAX_MB)");
     }
 #define R_(ptr, bytes)                                                                  \
@@ -1351,7 +1350,7 @@ int rep_setup_nuc(hyphy_hip_partition *p, const std::vector<std::vector<int16_t>
     R_(s.rep_codes_tile, ct.size() * sizeof(int16_t));
     R_(s.rep_leaf, lt.size() * sizeof(int2));
 #undef R_
-    if (getenv("HYPHY_HIP_POISON")) {
+    if (sw::poison()) {
       hipMemset(s.rep_tab, 0xff, (size_t)p->C * rows * 4 * sizeof(double));
       hipMemset(s.rep_cnt, 0xff, (size_t)p->C * rows * sizeof(int32_t));
     }
@@ -1374,7 +1373,7 @@ int rep_setup_nuc(hyphy_hip_partition *p, const std::vector<std::vector<int16_t>
   ms.nuc_leaf_pairs = false;  // (the trunk goes through prune_nuc_kernel: one leaf per entry)
   p->rep_on = true;
   p->rep_decided = true;       // (4 states: decided here, by the arithmetic above)
-  if (getenv("HYPHY_HIP_VERBOSE")) {
+  if (sw::verbose()) {
     long long rows = 0, lower = 0;
     for (int d = 0; d < ND; d++) {
       rows += p->shards[0].rep_tabs[d].rows;
@@ -1473,23 +1472,20 @@ static WalkPlan plan_trunk_walk(const hyphy_hip_partition::View &v) {
 namespace {
 int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t>> &codes) {
   p->rep_on = false;
-  const char *env = getenv("HYPHY_HIP_REPEATS");
-  if (env && atoi(env) == 0) return 0;
+  const int env = sw::repeats();  // -1 not given, 0 never, 2 always and past the size rules, 1 always
+  if (env == 0) return 0;
   if (p->shards.empty()) return 0;
-  if (!env)  // (the diagnostic switches that force a kernel, an instantiation or a cut are about the per-pattern kernels)
-    for (const char *sw : {"HYPHY_HIP_KERNEL", "HYPHY_HIP_WAVE_VARIANT", "HYPHY_HIP_CUT", "HYPHY_HIP_CHAIN_M", "HYPHY_HIP_FRAGMENT",
-                           "HYPHY_HIP_SLOTS", "HYPHY_HIP_REROOT", "HYPHY_HIP_TILES", "HYPHY_HIP_TIMELINE", "HYPHY_HIP_ABLATE"})
-      if (getenv(sw)) return 0;
+  if (env < 0 && sw::per_pattern_forced()) return 0;  // (the diagnostic switches that force a kernel, an instantiation or a cut are about the per-pattern kernels)
   for (const Shard &s : p->shards)
     if (s.T != 1) return 0;
-  if (!p->nuc && p->variant != 1 && !(env && atoi(env) == 2)) return 0;  // (tiny shards: the workgroup-per-tile kernel keeps the whole tree)
+  if (!p->nuc && p->variant != 1 && env != 2) return 0;  // (tiny shards: the workgroup-per-tile kernel keeps the whole tree)
   // 4 states: only on request (HYPHY_HIP_REPEATS=1 / 2).  Measured, it loses: a class row is 36 bytes gathered past the L2 per pattern
   // and generalised leaf, where prune_nuc2_kernel computes a whole node from registers for 16 multiply-adds — gtr_32x50k 35.0 us plain
   // against 16.5 (walks) + 26.0 (trunk of 5 nodes) compressed, gtr_32x1m 123.8 against 14.5 + 238.9
-  if (p->nuc && !env) return 0;
+  if (p->nuc && env < 0) return 0;
   const int L = (int)p->L, I = (int)p->I, DP = p->DP;
   if (I < 2) return 0;
-  const bool forced = env && atoi(env) == 2;
+  const bool forced = env == 2;
   // (before any work: a partition of a few tiles — FEL makes one per site — has nothing to compress, and the class arrays of a
   //  very large one are host memory this analysis should not take: 4 bytes per internal node and pattern)
   if (!forced && (p->nuc ? p->shards[0].S_pad < 8192 : p->shards[0].ntiles < 8)) return 0;  // (4 states: a small shard is one launch
@@ -1504,8 +1500,8 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
   // theta: the share of the patterns below which a node's classes are worth a table.  0.3-0.4 is the flat optimum of the headline
   // alignment (0.2: 100 us of pruning launches, 0.3: 89, 0.4: 89, 0.5: 101, 0.7: 106): above it the walks of the lower phase get long
   // and few, below it the trunk keeps nodes that repeat heavily
-  double theta = 0.35;
-  if (const char *e = getenv("HYPHY_HIP_REP_THETA")) theta = atof(e);
+  bool theta_given = false;
+  const double theta = sw::rep_theta(0.35, &theta_given);
   const size_t nsh = p->shards.size();
   // ---- classes per shard ----
   std::vector<std::vector<std::vector<int>>> cls(nsh);  // [shard][internal node][pattern]
@@ -1514,7 +1510,7 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
   // ---- compressed set: the same on every shard (one schedule serves them all) ----
   std::vector<int> spads;
   for (const Shard &s : p->shards) spads.push_back(s.S_pad);
-  std::vector<char> comp = compressed_set(p->children, L, I, U, spads, p->nuc && !getenv("HYPHY_HIP_REP_THETA") ? 0.9 : theta);
+  std::vector<char> comp = compressed_set(p->children, L, I, U, spads, p->nuc && !theta_given ? 0.9 : theta);
   for (size_t k = 0; k < nsh; k++)  // (only the classes of compressed nodes are read again: tables, maps, the trunk's leaf table)
     for (int n = 0; n < I; n++)
       if (!comp[n]) std::vector<int>().swap(cls[k][n]);
@@ -1525,7 +1521,7 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
       full += p->shards[0].S_pad;
       rep += comp[n] ? (U[0][n] + 15) / 16 * 16 : p->shards[0].S_pad;
     }
-    const double need = getenv("HYPHY_HIP_REP_MIN_GAIN") ? atof(getenv("HYPHY_HIP_REP_MIN_GAIN")) : 0.15;
+    const double need = sw::rep_min_gain();
     if (!forced && rep > (1.0 - need) * full) return 0;
   }
   // ---- descriptors: leaves with ambiguity codes first (level 0), then the paths, inputs before the paths that read them ----
@@ -1539,8 +1535,7 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
   // 2 048.  (Before the per-level launches, with the ticket protocol: 785 us at 0.6 against 726 at 0.)  HYPHY_HIP_REP_RHO overrides.
   // (r06, row-split walks in both phases, pruning launches at 128 x 100 k: 625 us at 0, 537 at 0.15, 501 at 0.3, 489 at 0.5, 485 at 0.6,
   //  504 at 0.7, 508 at 1 and 2: the default there moved from 0.3 to 0.5)
-  double rho = p->shards[0].ntiles >= 2048 ? 0.5 : 0.;
-  if (const char *e = getenv("HYPHY_HIP_REP_RHO")) rho = atof(e);
+  const double rho = sw::rep_rho(p->shards[0].ntiles >= 2048 ? 0.5 : 0.);
   std::vector<int> heavy(I, -1);     // the compressed child a node's path continues into
   std::vector<char> continued(I, 0); // the node is inside its parent's path (no table of its own)
   std::vector<int> path_inputs(I, 0), path_len(I, 0);
@@ -1576,7 +1571,8 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
   // path that reads it (publish, drain, counter, poll, gather: ~8 us with the item's fixed costs) to save a few products.  Such a
   // chain is walked INSIDE the item of the path it hangs off: the running product is parked in the wave's LDS tile, the chain
   // is walked from ones, and its edge product is multiplied back in (one parking slot: inlined chains do not nest).
-  const bool inline_chains = getenv("HYPHY_HIP_REP_INLINE") ? atoi(getenv("HYPHY_HIP_REP_INLINE")) != 0 : rho == 0.;
+  const int inline_forced = sw::rep_inline();
+  const bool inline_chains = inline_forced >= 0 ? inline_forced != 0 : rho == 0.;
   auto chain_of = [&](int top) {
     std::vector<int> down;
     for (int x = top; x >= 0; x = heavy[x]) down.push_back(x);
@@ -1773,10 +1769,8 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
     {  // the tables must leave the device room for everything else the partition allocates later (deposits, mixtures, site fits)
       size_t free_b = 0, total_b = 0;
       const size_t need_b = (size_t)p->C * rows * (DP * sizeof(double) + sizeof(int32_t)) + maps.size() * sizeof(int32_t) + ct.size() * sizeof(int16_t);
-      size_t limit = 0;
-      if (const char *e = getenv("HYPHY_HIP_REP_MAX_MB")) limit = (size_t)std::max(0L, atol(e)) << 20;  // (the caller's bound on the tables)
-      else if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) limit = free_b / 4;
-      else limit = (size_t)1 << 30;
+      size_t limit = (size_t)1 << 30;
+      if (!sw::rep_max_mb(&limit) && hipMemGetInfo(&free_b, &total_b) == hipSuccess) limit = free_b / 4;  // (given: the caller's bound on the tables)
       if (need_b > limit) return fail("class tables would take more than a quarter of the free device memory (or than HYPHY_HIP_REP_MAX_MB)");
     }
 #define R_(ptr, bytes)                                                                  \
@@ -1791,7 +1785,7 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
     R_(s.rep_codes_tile, ct.size() * sizeof(int16_t));
     R_(s.rep_leaf, lt.size() * sizeof(int2));
 #undef R_
-    if (getenv("HYPHY_HIP_POISON")) {
+    if (sw::poison()) {
       hipMemset(s.rep_tab, 0xff, (size_t)p->C * rows * DP * sizeof(double));
       hipMemset(s.rep_cnt, 0xff, (size_t)p->C * rows * sizeof(int32_t));
     }
@@ -1834,7 +1828,7 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
         for (size_t k = 0; k < inputs.size(); k++) prog[in_base + k] = make_int4(inputs[k], lt[inputs[k]].x, lt[inputs[k]].y, 0);
         if (&s == &p->shards[0]) {
           p->rep_walk_host = prog;
-          if (getenv("HYPHY_HIP_VERBOSE")) {
+          if (sw::verbose()) {
             fprintf(stderr, "[hyphy_hip] trunk walk: %d nodes, waiting products at most %d deep", one_range[1] - one_range[0], max_depth);
             if (two) fprintf(stderr, "; two chains per tile: %d + %d nodes", two_range[1] - two_range[0], two_range[3] - two_range[2]);
             fprintf(stderr, "\n");
@@ -1864,8 +1858,8 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
   ms.rr_cands.clear();
   // (r06: the trunk under the row-split workgroup kernel, prune_mfma_kernel<.., REP> — the tuner offers it on shards below eight tiles
   //  per CU; HYPHY_HIP_TRUNK_KERNEL=0 / 2 forces it — whole trunk per workgroup / on chain schedules — for tests and A/B runs)
-  if (const char *tk = getenv("HYPHY_HIP_TRUNK_KERNEL")) {
-    const int kv = atoi(tk);
+  {
+    const int kv = sw::trunk_kernel();  // (-1: not given)
     const hyphy_hip_partition::View &tv = p->views[1];
     if ((kv == 0 || kv == 2) && p->NW == 4 && !p->nuc && (size_t)tv.L * 32 + (size_t)(tv.L + tv.I) * 16 <= 24576) {
       ms.variant = kv;
@@ -1879,10 +1873,10 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
     // one-workgroup-per-tile kernel behind it for the other passes nothing in this mode depends on an order of arrival: the same
     // bits on every run (tested).  (The chain schedules of the wave and row-split trunks do join by order of arrival, but form every
     // node in schedule order — schedule.hip, prune.hip — so their bits do not depend on it either.)  (NW 2 / 3: the walk's speed is unmeasured; without the switch only the tuner offers it.)
-    const char *tw = getenv("HYPHY_HIP_TRUNK_WALK");
-    const bool tune_off = getenv("HYPHY_HIP_TUNE") && atoi(getenv("HYPHY_HIP_TUNE")) == 0;
+    const int tw = sw::trunk_walk_at_create();
+    const bool tune_off = !sw::tune();
     const hyphy_hip_partition::View &tv = p->views[1];
-    if ((tw ? atoi(tw) == 1 : tune_off && p->NW == 4) && !p->rep_walk_host.empty() && (size_t)tv.L * 32 + (size_t)(tv.L + tv.I) * 16 <= 24576) {
+    if ((tw >= 0 ? tw == 1 : tune_off && p->NW == 4) && !p->rep_walk_host.empty() && (size_t)tv.L * 32 + (size_t)(tv.L + tv.I) * 16 <= 24576) {
       ms.trunk_walk = true;
       ms.variant = trunk_walk_backing(p);
       ms.n_slots = ms.variant == 1 ? p->n_slots_wave : lds_slots(1);
@@ -1903,7 +1897,7 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
     p->rr_cands.swap(cands0);
   }
   p->rep_on = true;
-  if (getenv("HYPHY_HIP_VERBOSE")) {
+  if (sw::verbose()) {
     long long rows = 0, lower = 0;
     for (int d = 0; d < ND; d++) {
       rows += p->shards[0].rep_tabs[d].rows;
@@ -2007,9 +2001,8 @@ void rep_translate_update(hyphy_hip_partition *p, const int64_t *update_nodes, i
 // matrix pipe: two walks on one SIMD take twice as long each, and the launch ends with its longest walk), two per SIMD beyond.
 static int rep_wave_count(const Shard &s, size_t n_items) {
   const int n = (int)((n_items + kRepQueues - 1) / kRepQueues * kRepQueues);
-  int w = n <= 8 * s.cus ? std::min(n, s.cus * 4) : s.cus * 8;
-  if (const char *e = getenv("HYPHY_HIP_REP_WAVES")) w = std::max(1, std::min(n, atoi(e)));
-  return std::max(1, w);
+  const int w = n <= 8 * s.cus ? std::min(n, s.cus * 4) : s.cus * 8;
+  return std::max(1, sw::rep_waves(n, w));
 }
 
 int rep_build_items(const hyphy_hip_partition *p, const Shard &s, const std::vector<int> &dirty, int cat0, int n_classes,
@@ -2047,7 +2040,7 @@ int rep_build_items(const hyphy_hip_partition *p, const Shard &s, const std::vec
   }
   const int nw = rep_wave_count(s, all.size());
   if (n_waves) *n_waves = nw;
-  const bool lpt_on = !(getenv("HYPHY_HIP_REP_LPT") && atoi(getenv("HYPHY_HIP_REP_LPT")) == 0);
+  const bool lpt_on = sw::rep_lpt();
   // Items dealt by position: wave w takes positions w, 2 w_n - 1 - w, 2 w_n + w, ... (class_table_kernel).  Which item sits where
   // decides when the launch ends: 1 519 walks of 8-24 us on 1 024 waves are two rounds at most, and in order of descriptor
   // priority the waves whose first walk was a 15-us one got a second 15-us one (31.6 us) while 23-us walks sat alone and 16-us
@@ -2094,10 +2087,9 @@ int rep_build_items(const hyphy_hip_partition *p, const Shard &s, const std::vec
     std::stable_sort(its.begin(), its.end(), [&](const int4 &x, const int4 &y) { return cost[x.x] > cost[y.x]; });
     for (size_t i = 0; i < its.size(); i++) its[i].z = (int)i, its[i].w = 0;
   };
-  const bool verbose2 = getenv("HYPHY_HIP_VERBOSE") && atoi(getenv("HYPHY_HIP_VERBOSE")) >= 2;
+  const bool verbose2 = sw::verbose_level() >= 2;
   if (launches) launches->clear();
-  const bool levels_on = launches && !(getenv("HYPHY_HIP_REP_LEVELS") && atoi(getenv("HYPHY_HIP_REP_LEVELS")) == 0) &&
-                         !(getenv("HYPHY_HIP_REP_STATIC") && atoi(getenv("HYPHY_HIP_REP_STATIC")) == 0);
+  const bool levels_on = launches && sw::rep_levels() && sw::rep_static();
   if (n_static && *n_static == 0 && !all.empty() && levels_on) {
     // Tables that read tables of the same pass: ONE LAUNCH PER LEVEL of that dependency (level 0: no table of this pass among the
     // inputs), each dealt by position like a pass without dependencies — the launch boundary is the hand-off (2-3 us for everybody at
@@ -2238,11 +2230,11 @@ int rep_prepare_pass(hyphy_hip_partition *p, const int64_t *update_nodes, int64_
     }
     std::vector<int4> queues;
     int n_static = 0, n_waves = 1;
-    ps.team = p->NW >= 2 && !(getenv("HYPHY_HIP_REP_TEAM") && atoi(getenv("HYPHY_HIP_REP_TEAM")) == 0) &&
-              !(getenv("HYPHY_HIP_REP_STATIC") && atoi(getenv("HYPHY_HIP_REP_STATIC")) == 0);
+    const bool static_on = sw::rep_static();
+    ps.team = p->NW >= 2 && sw::rep_team() && static_on;
     ps.launches.clear();
     const int per_q = dirty.empty() ? 0 : rep_build_items(p, s, dirty, cat0, n_classes, queues, &n_static, &n_waves, &ps.launches, ps.team);
-    ps.n_static = getenv("HYPHY_HIP_REP_STATIC") && atoi(getenv("HYPHY_HIP_REP_STATIC")) == 0 ? 0 : n_static;
+    ps.n_static = static_on ? n_static : 0;
     const size_t words = (size_t)kRepQueues * std::max(1, per_q) + (size_t)(ND + 3) / 4;  // queues, then the live flags
     {
       // (sized for a full pass of every class: partial passes never need more)
@@ -2253,7 +2245,7 @@ int rep_prepare_pass(hyphy_hip_partition *p, const int64_t *update_nodes, int64_
     if (per_q > 0) memcpy(ps.h_items, queues.data(), (size_t)kRepQueues * per_q * sizeof(int4));
     int *live = reinterpret_cast<int *>(ps.h_items + (size_t)kRepQueues * std::max(1, per_q));
     for (int d = 0; d < ND; d++) live[d] = 0;
-    for (int d : dirty) live[d] = getenv("HYPHY_HIP_REP_NODEPS") ? 0 : 1;  // (diagnostic: nobody waits, results invalid)
+    for (int d : dirty) live[d] = sw::rep_nodeps() ? 0 : 1;  // (diagnostic: nobody waits, results invalid)
     HIPCHK(hipMemcpyAsync(ps.items, ps.h_items, words * sizeof(int4), hipMemcpyHostToDevice, s.stream));
     HIPCHK(hipEventRecord(ps.ev, s.stream));  // (re-recorded behind every launch that reads the slot: rep_launch)
     ps.ev_recorded = true;
@@ -2317,7 +2309,7 @@ static int rep_launch_impl(hyphy_hip_partition *p, Shard &s, int cat0) {
   // that take hundreds — class tables that read class tables of the same pass, rho > 0 or partial updates)
   if (s.rep_sync_dirty) HIPCHK(hipMemsetAsync(s.rep_sync, 0, rep_sync_words(p) * kRepHeadStride * sizeof(int), s.stream));
   s.rep_sync_dirty = a.n_static == 0 && s.rep_launches.empty();
-  const char *tl = getenv("HYPHY_HIP_REP_TIMELINE");
+  const char *tl = sw::rep_timeline();
   if (tl && p->NW == 4) {  // diagnostic: synchronous, one file per launch (the last launch survives)
     size_t traced = s.rep_launches.size();  // (several launches per pass: the LAST level is the traced one, the others run plain before it)
     for (size_t k = 0; k < s.rep_launches.size(); k++) {
@@ -2364,13 +2356,9 @@ static int rep_launch_impl(hyphy_hip_partition *p, Shard &s, int cat0) {
 }
 
 // ---- the trunk's lazy full pass as one row-split walk per tile (trunk_walk_kernel) ----
-static bool trunk_walk_allowed() {  // (per call: tests and A/B runs switch it)
-  const char *e = getenv("HYPHY_HIP_TRUNK_WALK");
-  return !(e && atoi(e) == 0);
-}
 bool trunk_walk_applies(const hyphy_hip_partition *p, const Shard &s) {
   return p->mode == 1 && p->trunk_walk && !p->nuc && s.rep_walk && s.T == 1 && p->sched_full && !p->sched_persist && p->pin_node < 0 &&
-         (size_t)p->views[1].L * 32 <= 32768 && trunk_walk_allowed();
+         (size_t)p->views[1].L * 32 <= 32768 && sw::trunk_walk();
 }
 // The kernel that serves the trunk's passes the walk does not (persisting passes, partial updates, the restore of the copies): the
 // row-split workgroup kernel where its trunk form exists (NW = 4, leaf codes in LDS), else the wave-per-tile kernel, which has a trunk
@@ -2384,7 +2372,7 @@ int launch_trunk_walk(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch
   const int DP = p->DP, n_cat = std::max(1, n_cat_batch);
   // two workgroups per tile where that still fits the chip in one round (five workgroups per CU); HYPHY_HIP_WALK_CHAINS=1/2 forces
   int chains = (p->rep_walk_host[0].y > 0 && (size_t)2 * s.ntiles * n_cat <= (size_t)5 * s.cus) ? 2 : 1;
-  if (const char *e = getenv("HYPHY_HIP_WALK_CHAINS")) chains = (atoi(e) == 2 && p->rep_walk_host[0].y > 0) ? 2 : 1;
+  if (const int wc = sw::walk_chains()) chains = (wc == 2 && p->rep_walk_host[0].y > 0) ? 2 : 1;
   TrunkWalkArgs a;
   a.Pfrag = s.Pfrag + (size_t)cat * p->B * DP * DP;
   a.PTg = s.PTg + (size_t)cat * p->B * DP * DP;
@@ -2423,7 +2411,7 @@ int launch_trunk_walk(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch
   }
   const dim3 grid(s.ntiles, n_cat, chains), block(64 * p->NW);
   const size_t lds = (size_t)a.L * 32;
-  const char *tl = timeline ? getenv("HYPHY_HIP_WALK_TIMELINE") : nullptr;
+  const char *tl = timeline ? sw::walk_timeline() : nullptr;
   if (tl && p->NW == 4) {  // diagnostic: synchronous, one record per workgroup (the lower phase's format: tools/rep_team_timeline.py)
     const size_t n = (size_t)grid.x * grid.y * grid.z * 16;
     HIPCHK(pool_malloc((void **)&a.dbg, n * sizeof(long long)));
@@ -2495,14 +2483,14 @@ int rep_decide(hyphy_hip_partition *p, int cat, int n_classes) {
   p->rep_decided = true;
   Shard &s = p->shards[0];
   HIPCHK(hipSetDevice(s.device));
-  static const bool cache_on = !(getenv("HYPHY_HIP_TUNE_CACHE") && atoi(getenv("HYPHY_HIP_TUNE_CACHE")) == 0);
+  const bool cache_on = sw::tune_cache();
   const RepDecisionKey dkey = rep_decision_key(p, n_classes);
   if (cache_on) {
     std::lock_guard<std::mutex> lock(g_rep_decisions_mutex);
     auto hit = g_rep_decisions.find(dkey);
     if (hit != g_rep_decisions.end()) {
       p->rep_report = "(same tree, trunk, shard size and class batch as an earlier partition of this process) " + hit->second.second;
-      if (getenv("HYPHY_HIP_VERBOSE")) fprintf(stderr, "[hyphy_hip] %s\n", p->rep_report.c_str());
+      sw::note("%s\n", p->rep_report.c_str());
       if (!hit->second.first) {
         p->rep_enabled = false;
         switch_mode(p, 0);
@@ -2540,7 +2528,7 @@ int rep_decide(hyphy_hip_partition *p, int cat, int n_classes) {
   snprintf(b, sizeof b, "repeats: lower phase %.1fus + trunk %.1fus against %.1fus without -> %s", 1e3 * lower_ms, 1e3 * trunk_ms, 1e3 * plain_ms,
            off ? "off" : "on");
   p->rep_report = b;
-  if (getenv("HYPHY_HIP_VERBOSE")) fprintf(stderr, "[hyphy_hip] %s\n", b);
+  sw::note("%s\n", b);
   if (cache_on) {
     std::lock_guard<std::mutex> lock(g_rep_decisions_mutex);
     g_rep_decisions[dkey] = std::make_pair(!off, std::string(b));

@@ -194,7 +194,7 @@ int hyphy_hip_sample_ancestral(hyphy_hip_partition *p, int64_t n_rep, int64_t n_
   std::vector<int32_t> parent((size_t)(L + I), -1);
   for (int64_t c = 0; c < L + I - 1; c++) parent[(size_t)c] = (int32_t)p->parents[(size_t)c];
   const std::vector<double> pi_pad = padded_pi(p);
-  const double budget = scratch_budget("HYPHY_HIP_SAMPLE_MB");
+  const double budget = sw::scratch_budget(sw::SAMPLE_MB);
   const double draw_bytes = (double)I * (uniforms ? 9. : 1.);  // scratch of one entry and replicate: a byte (and a uniform) per node
   // device pattern (over all shards) of every caller pattern
   std::vector<int64_t> dev_of((size_t)S);

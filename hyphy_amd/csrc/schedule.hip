@@ -196,7 +196,7 @@ void build_schedule_impl(hyphy_hip_partition *p, const int64_t *update_nodes, in
     const Shard &s0 = p->shards[0];
     const long wgs = std::max(1, s0.ntiles / std::max(1, s0.T)) * (long)std::max<int64_t>(1, p->batch_classes);
     const long target = 6L * s0.cus;
-    if (const char *e = getenv("HYPHY_HIP_FRAGMENT")) max_frag = std::max(1, atoi(e));
+    if (const int f = sw::fragment()) max_frag = f;
     else if (wgs < target) max_frag = (int)std::max<long>(4, (long)I * wgs / target);
   }
   p->chain = false;
@@ -210,15 +210,14 @@ void build_schedule_impl(hyphy_hip_partition *p, const int64_t *update_nodes, in
   // dispatched source-major with the sources sorted by their distance to the root, so that every tile's critical path
   // starts first and the short chains that join near the root fill the end of the launch.
   // (HYPHY_HIP_CUT=levels or an explicit HYPHY_HIP_FRAGMENT keep the level-peeled fragments; HYPHY_HIP_CHAIN_M sets m)
-  const bool want_levels = (getenv("HYPHY_HIP_CUT") && !strcmp(getenv("HYPHY_HIP_CUT"), "levels")) ||
-                           (getenv("HYPHY_HIP_FRAGMENT") && !getenv("HYPHY_HIP_CHAIN_M")) ||
-                           (p->chain_m_forced < 0 && !getenv("HYPHY_HIP_CHAIN_M"));
+  const bool want_levels = sw::cut_levels() || (sw::given(sw::FRAGMENT) && !sw::given(sw::CHAIN_M)) ||
+                           (p->chain_m_forced < 0 && !sw::given(sw::CHAIN_M));
   if (full && !p->nuc && p->variant >= 1 && !p->shards.empty() && !want_levels) {
     const Shard &s0 = p->shards[0];
     // Topology the schedule is built on: the given one, or (re-rooted schedules) the same unrooted tree hung from rr_path.back();
     // the edges of rr_path are then reversed.  rpar = parent, order = children before parents, on_path = index along rr_path.
     const bool lazy_full = !p->sched_persist;
-    const int rr_env = getenv("HYPHY_HIP_REROOT") ? atoi(getenv("HYPHY_HIP_REROOT")) : -1;  // (1: always, 0: never, unset: the tuner decides)
+    const int rr_env = sw::reroot();  // (1: always, 0: never, unset: the tuner decides)
     const bool rr = !p->rr_path.empty() && (rr_env == 1 || (rr_env != 0 && p->rr_use)) && lazy_full && p->pin_node < 0 &&
                     p->batch_classes <= 1 && p->C == 1;
     std::vector<int> rpar(I, -1), on_path(I, -1), order;
@@ -264,7 +263,7 @@ void build_schedule_impl(hyphy_hip_partition *p, const int64_t *update_nodes, in
     const long wgs = std::max(1, s0.ntiles) * (long)std::max<int64_t>(1, p->batch_classes);
     const long target = 24L * s0.cus;  // >= 3 rounds of the 8 resident waves per CU
     int m = 1;
-    if (const char *e = getenv("HYPHY_HIP_CHAIN_M")) m = std::max(1, atoi(e));
+    if (const int cm = sw::chain_m()) m = cm;
     else if (p->chain_m_forced > 0) m = p->chain_m_forced;
     else {
       if (wgs >= target) m = I;  // enough tiles: one wave walks the whole tree
@@ -299,7 +298,7 @@ void build_schedule_impl(hyphy_hip_partition *p, const int64_t *update_nodes, in
       // remainder of the trunk while the chip drains: dispatched FIRST they deposit and retire in a few microseconds,
       // and the long chains that arrive later go on with the trunk (HYPHY_HIP_TINY_FIRST = largest source size moved up).
       {
-        const int tiny = getenv("HYPHY_HIP_TINY_FIRST") ? atoi(getenv("HYPHY_HIP_TINY_FIRST")) : 0;
+        const int tiny = sw::tiny_first();
         if (tiny > 0) std::stable_partition(srcs.begin(), srcs.end(), [&](const Src &x) { return size[x.root] <= tiny; });
       }
       p->jn_host.assign(I, make_int4(-1, 0, 0, 0));
@@ -360,7 +359,7 @@ void build_schedule_impl(hyphy_hip_partition *p, const int64_t *update_nodes, in
       p->levels.push_back({0, (int)p->programs.size()});
       p->chain = true;
       p->rr_active = rr;
-      if (getenv("HYPHY_HIP_VERBOSE")) {
+      if (sw::verbose()) {
         fprintf(stderr, "[hyphy_hip] chain schedule: m = %d, %zu sources (root node / distance):", m, srcs.size());
         for (const Src &sr : srcs) fprintf(stderr, " %d/%d", sr.root, sr.prio);
         fprintf(stderr, "\n");
@@ -437,7 +436,7 @@ void build_schedule_impl(hyphy_hip_partition *p, const int64_t *update_nodes, in
       }
     }
     p->levels.push_back({first_prog, (int)frags.size()});
-    if (getenv("HYPHY_HIP_VERBOSE")) {
+    if (sw::verbose()) {
       fprintf(stderr, "[hyphy_hip] level %zu: %zu fragment(s), internal nodes:", p->levels.size() - 1, frags.size());
       for (const std::vector<int> &f : frags) fprintf(stderr, " %zu", f.size());
       fprintf(stderr, "\n");

@@ -295,7 +295,7 @@ int hyphy_hip_simulate(hyphy_hip_partition *p, int64_t n_rep, int64_t n_sites, c
     HIPCHK(hipGetLastError());
   }
   // ---- chunks: as many whole replicates as fit the budget, else site ranges of one replicate (at least one column) ------------
-  const double budget = scratch_budget("HYPHY_HIP_SIMULATE_MB");
+  const double budget = sw::scratch_budget(sw::SIMULATE_MB);
   const double col_bytes = (double)rows * (uniforms ? 9. : 1.);  // scratch of one column: a byte (and a uniform) per node
   int64_t Rc = 1, ncap = n_sites;
   if (col_bytes * (double)n_sites <= budget && n_sites <= kMaxChunkCols) {

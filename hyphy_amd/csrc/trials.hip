@@ -275,7 +275,7 @@ int trials_common(const char *what, hyphy_hip_partition *p, int64_t n_trials, co
     }
   tr_off.push_back((int)n_trials);
   const int n_branch = (int)branch.size();
-  const double budget = scratch_budget("HYPHY_HIP_TRIALS_MB");
+  const double budget = sw::scratch_budget(sw::TRIALS_MB);
   const size_t MS = nuc ? 16 : (size_t)DP * DP;     // doubles of a trial matrix on the device
   const size_t TILE = nuc ? 256 : (size_t)16 * DP;  // doubles of one tile of one node
   const int TP = nuc ? 64 : 16;                     // its patterns

@@ -36,7 +36,7 @@ PruneArgs prune_args_current(hyphy_hip_partition *p, Shard &s, int cat, int n_ca
   pa.n_prog_total = p->chain ? (int)p->I : (int)p->programs.size();
   pa.chain = p->chain ? 1 : 0;
   pa.jn = s.jn, pa.deposits = s.deposits, pa.cs_deposits = s.deposits_class_stride;
-  if (const char *ab = getenv("HYPHY_HIP_ABLATE")) pa.ablate = atoi(ab);
+  pa.ablate = sw::ablate();
   return pa;
 }
 
@@ -149,7 +149,7 @@ int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch) {
   struct Choice { Cand cand; double ms; };
   static std::map<Key, Choice> cache;
   static std::mutex cache_mutex;
-  static const bool cache_on = !(getenv("HYPHY_HIP_TUNE_CACHE") && atoi(getenv("HYPHY_HIP_TUNE_CACHE")) == 0);
+  const bool cache_on = sw::tune_cache();
   uint64_t topo = 1469598103934665603ull;  // FNV-1a over the parent vector
   for (int64_t v : p->vw().parents) topo = (topo ^ (uint64_t)v) * 1099511628211ull;
   if (p->mode == 1)  // (the trunk depends on the alignment: leaves that are class tables gather differently from plain ones)
@@ -161,7 +161,7 @@ int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch) {
     if (hit != cache.end() && apply(hit->second.cand)) {
       p->tuned_ms = hit->second.ms;
       p->tune_report = "(same tree, shard size and class batch as an earlier partition of this process) -> " + label(hit->second.cand);
-      if (getenv("HYPHY_HIP_VERBOSE")) fprintf(stderr, "[hyphy_hip] schedule tuner (%d classes per launch): %s\n", n_cat_batch, p->tune_report.c_str());
+      sw::note("schedule tuner (%d classes per launch): %s\n", n_cat_batch, p->tune_report.c_str());
       return 0;
     }
   }
@@ -176,14 +176,12 @@ int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch) {
   const bool small = T0 == 1 && s.ntiles < 2 * s.cus;   // below two tiles per CU
   const bool medium = T0 == 1 && s.ntiles < 4 * s.cus;
   if ((forced < 0 && small) || forced == 0) stage1.push_back({0, 0, 0, -1});  // one workgroup walks the whole tree of its tile
-  static const bool team_on = !(getenv("HYPHY_HIP_TEAM") && atoi(getenv("HYPHY_HIP_TEAM")) == 0);
-  if (((forced < 0 && medium && team_on) || forced == 2) && T0 == 1)
+  if (((forced < 0 && medium && sw::team()) || forced == 2) && T0 == 1)
     for (int m : {3, 5, 8, 12, 16, 24})
       if (m < I) stage1.push_back({2, m, 0, -1});
   // r06: the trunk of a class-compressed partition under row-split workgroups (prune_mfma_kernel<.., REP>): a trunk is a handful of
   // nodes, its launch is bound by a tile's critical path — a team's edge product is a quarter of a wave's
-  const bool rep_team_on = !(getenv("HYPHY_HIP_TRUNK_TEAM") && atoi(getenv("HYPHY_HIP_TRUNK_TEAM")) == 0);  // (per call: tests run both)
-  if (p->mode == 1 && forced == 1 && rep_team_on && T0 == 1 && p->NW == 4 && s.ntiles < 8 * s.cus &&
+  if (p->mode == 1 && forced == 1 && sw::trunk_team() && T0 == 1 && p->NW == 4 && s.ntiles < 8 * s.cus &&
       (size_t)p->vw().L * 32 + (size_t)(p->vw().L + p->vw().I) * 16 <= 24576) {
     stage1.push_back({0, 0, 0, -1});
     for (int m : {1, 2, 3, 5, 8})
@@ -210,7 +208,7 @@ int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch) {
   // slot, no register prefetch of deposits) on its three fastest cuts — it wins where waves are plentiful ----
   const double stage1_ms = best_ms;
   int wave_wv = 0;  // instantiation the wave kernel's candidates of the third stage use
-  if (best.kernel == 1 && best.m > 0 && p->NW == 4 && !getenv("HYPHY_HIP_WAVE_VARIANT") && !getenv("HYPHY_HIP_SLOTS"))
+  if (best.kernel == 1 && best.m > 0 && p->NW == 4 && !sw::wave_form_forced())
     for (size_t k = 0; k < ranked[1].size() && k < 3; k++) {
       const Cand c{1, ranked[1][k].second, 2, -1};
       const double t = time_it(c);
@@ -226,7 +224,7 @@ int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch) {
     }
   // ---- third stage: the same tree hung from the node that minimises its height (re-rooted schedules): shorter critical
   // path per tile, the same work — wins on small and medium shards of unbalanced trees ----
-  if (best.m > 0 && !p->rr_path.empty() && n_cat_batch <= 1 && !getenv("HYPHY_HIP_REROOT")) {
+  if (best.m > 0 && !p->rr_path.empty() && n_cat_batch <= 1 && !sw::given(sw::REROOT)) {
     const int kn = best.kernel;
     bool rr_won = false;
     for (size_t ci = 0; ci < p->rr_cands.size(); ci++)
@@ -250,7 +248,7 @@ int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch) {
   }
   p->tuned_ms = best_ms;
   p->tune_report += " -> " + label(best);
-  if (getenv("HYPHY_HIP_VERBOSE")) fprintf(stderr, "[hyphy_hip] schedule tuner (%d classes per launch): %s\n", n_cat_batch, p->tune_report.c_str());
+  sw::note("schedule tuner (%d classes per launch): %s\n", n_cat_batch, p->tune_report.c_str());
   return 0;
 }
 

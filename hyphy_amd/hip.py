@@ -24,7 +24,7 @@ EXPORTS = [
     "hyphy_hip_evaluate_built", "hyphy_hip_evaluate_built_sites", "hyphy_hip_update_q_templates", "hyphy_hip_evaluate_categories_built", "hyphy_hip_evaluate_categories_built_sites", "hyphy_hip_prune_timings", "hyphy_hip_prune_launches",
     "hyphy_hip_prune_kernel_name", "hyphy_hip_branch_cache_build", "hyphy_hip_branch_cache_evaluate",
     "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_joint_ancestral", "hyphy_hip_sample_ancestral", "hyphy_hip_sample_uniforms", "hyphy_hip_simulate", "hyphy_hip_simulate_uniforms", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
-    "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
+    "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_plan_switches", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
     "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error", "hyphy_hip_last_expm_kernel",
     "hyphy_hip_version",
 ]
@@ -181,6 +181,8 @@ def load():
     lib.hyphy_hip_xch_close.argtypes = [C.c_void_p]
     lib.hyphy_hip_plan_nucgen.restype = C.c_int64
     lib.hyphy_hip_plan_nucgen.argtypes = [C.c_int64, C.c_int64, lp, lp, C.c_int64, C.c_char_p, C.c_int64, lp]
+    lib.hyphy_hip_plan_switches.restype = C.c_int64
+    lib.hyphy_hip_plan_switches.argtypes = [C.c_char_p, C.c_int64]
     lib.hyphy_hip_last_error.restype = C.c_char_p
     lib.hyphy_hip_last_expm_kernel.restype = C.c_char_p
     lib.hyphy_hip_last_expm_kernel.argtypes = []
@@ -302,6 +304,19 @@ def plan_nucgen(flat_parents, L: int, leaf_has_ambig=None, compile_it: bool = Tr
     if n < 0:
         raise HipError("plan_nucgen: bad arguments")
     return buf.value.decode(), bool(ok[0])
+
+
+def plan_switches() -> list:
+    """Host-only: the library's environment switches (csrc/switches.h, docs/switches.md), one dict per row with ``name`` (without
+    the HYPHY_HIP_ prefix), ``kind``, ``when`` (process | create | call), ``audience`` (integrator | diagnostic), ``default`` and
+    ``value``: what the switch parses to in the environment as it is now (a fresh read, also of what the library caches per process)."""
+    lib = load()
+    need = -lib.hyphy_hip_plan_switches(None, 0)
+    buf = C.create_string_buffer(need)
+    if lib.hyphy_hip_plan_switches(buf, need) != need:
+        raise HipError("plan_switches: the table changed size between two calls")
+    keys = ("name", "kind", "when", "audience", "default", "value")
+    return [dict(zip(keys, line.split("\t"))) for line in buf.value.decode().splitlines()]
 
 
 class HostExchange:

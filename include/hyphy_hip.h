@@ -42,10 +42,12 @@ extern "C" {
 typedef struct hyphy_hip_partition hyphy_hip_partition; /* device-side state of ONE (filter, tree) partition */
 
 /*
- * Environment switches.  A host integrator needs at most these TEN; the library works without any of them:
+ * Environment switches.  The library works without any of them; a host integrator needs at most the ones listed here (the rows marked
+ * `integrator` of the table in hyphy_amd/csrc/switches.h, which is the one place that reads the environment; docs/switches.md is that
+ * table as a page, hyphy_hip_plan_switches() returns it with what every switch parses to right now):
  *   HYPHY_HIP_VERBOSE=1           what was decided and why (schedule tuner, subtree repeats on / off, generated kernels) on stderr
  *   HYPHY_HIP_POOL_MB=n           device / pinned blocks of destroyed partitions kept for the next one of the same shape (MiB per kind,
- *                                 default 1024; 0: nothing is kept)
+ *                                 default 1024; 0: nothing is kept); read once per process
  *   HYPHY_HIP_CACHE=always        every pass stores every node's conditionals (default: lazy persistence, see hyphy_hip_download_partials)
  *   HYPHY_HIP_TUNE=0              no run-time schedule measurement (with HYPHY_HIP_CUT=levels: bit-identical repeats, see below)
  *   HYPHY_HIP_CUT=levels          fixed multiplication order, no arrival-order joins
@@ -54,12 +56,18 @@ typedef struct hyphy_hip_partition hyphy_hip_partition; /* device-side state of 
  *   HYPHY_HIP_NUCGEN_AFTER=n      ... evaluations under one schedule before its kernel is compiled in the background (default 8)
  *   HYPHY_HIP_COMBINE=rccl        one process, several devices: sum the shard partials by one RCCL group all-reduce instead of on the host
  *   HYPHY_HIP_EXCHANGE_TIMEOUT_S  one process per GPU, host-side exchange: how long a rank waits for the others (default 120)
- * Everything else that starts with HYPHY_HIP_ (about forty names: HYPHY_HIP_KERNEL, _CHAIN_M, _WAVE_VARIANT, _SLOTS, _REROOT, _FRAGMENT,
- * _TILES, _REP_*, _TRUNK_*, _NUC*, _EXPM*, _FUSED_REDUCE, _SITE_EXPORT, _SPIN, _XCD_PAD, _TIMELINE, _ABLATE, _POISON, _TRACE, ...) is a
- * DIAGNOSTIC of the kernels' authors: it forces one of the forms the tuner chooses between, turns a mechanism off for an A/B run or
- * writes a trace.  The tests use them to reach every form; a host should not.  (The adapter of INTEGRATION.md has a handful of its own:
- * HYPHY_HIP=1 turns it on, HYPHY_HIP_DEVICE(S), HYPHY_HIP_WORLD / _RANK / _LOCAL_RANK / _RUN_ID / _UID_FILE / _COLLECTIVE for one
- * process per GPU, HYPHY_HIP_DEVICE_EXPM, HYPHY_HIP_TEMPLATES, HYPHY_HIP_MIXTURES, HYPHY_HIP_CAT_BATCH.)
+ *   HYPHY_HIP_TIMING_EVERY=n      one evaluation in n carries the kernel-duration stamp (default 16; read once per process):
+ *                                 hyphy_hip_last_timings, hyphy_hip_prune_timings
+ *   HYPHY_HIP_ALL_TIMINGS         (set to anything) the initial state of hyphy_hip_set_timing_detail
+ *   HYPHY_HIP_TRIALS_MB, HYPHY_HIP_JOINT_MB, HYPHY_HIP_SAMPLE_MB, HYPHY_HIP_SIMULATE_MB
+ *                                 scratch budgets (MiB, default 1024, read at every call) of hyphy_hip_branch_trials, _joint_ancestral,
+ *                                 _sample_ancestral and _simulate, described at those entry points
+ * The table says of every switch WHEN it is read: once per process (then cached), while a partition is created, or by every call.
+ * Everything else that starts with HYPHY_HIP_ is a DIAGNOSTIC of the kernels' authors: it forces one of the forms the tuner chooses
+ * between, turns a mechanism off for an A/B run or writes a trace; docs/switches.md lists them all, with the file that consults each.
+ * The tests use them to reach every form; a host should not.  (The adapter of INTEGRATION.md has a handful of variables of its own, which
+ * the library never reads: HYPHY_HIP=1 turns it on, HYPHY_HIP_DEVICE(S), HYPHY_HIP_WORLD / _RANK / _LOCAL_RANK / _RUN_ID / _UID_FILE /
+ * _COLLECTIVE for one process per GPU, HYPHY_HIP_DEVICE_EXPM, HYPHY_HIP_TEMPLATES, HYPHY_HIP_MIXTURES, HYPHY_HIP_CAT_BATCH.)
  */
 
 /* Number of usable gfx950 devices (0 if none / no HIP runtime). */
@@ -671,6 +679,14 @@ int64_t hyphy_hip_plan_trunk_walk(int64_t L, int64_t I, const int64_t *parents, 
  *                           generator does not cover the schedule, < 0 on bad arguments; *compiled_out = 1 when it compiled for gfx950. */
 int64_t hyphy_hip_plan_nucgen(int64_t L, int64_t I, const int64_t *flat_parents, const int64_t *leaf_has_ambig, int64_t small, char *src_out,
                               int64_t cap, int64_t *compiled_out);
+
+/*   hyphy_hip_plan_switches  host-only (no device): the table of the library's environment switches (see the top of this file,
+ * docs/switches.md), one line per switch: NAME<TAB>kind<TAB>when<TAB>audience<TAB>default<TAB>value, NAME without the prefix, `when` one of
+ * process | create | call, `audience` integrator | diagnostic, `value` what the switch parses to in the environment as it is NOW (a fresh
+ * read, also of the switches the library caches per process; sizes in bytes).  Behind the switches, the predicates the library forms from
+ * groups of them (kind "predicate").  Returns the bytes needed, the terminating zero included; with out = NULL or cap too small nothing
+ * is written and the negated requirement is returned. */
+int64_t hyphy_hip_plan_switches(char *out, int64_t cap);
 
 const char *hyphy_hip_last_error(void);
 const char *hyphy_hip_version(void);
