@@ -823,6 +823,23 @@ const char *hyphy_hip_prune_kernel_name(const hyphy_hip_partition *p) {
   return p->variant == 1 ? "prune_wave_kernel" : "prune_mfma_kernel";  // (variant 2: the same kernel on a chain schedule)
 }
 
+const char *hyphy_hip_last_prune_form(const hyphy_hip_partition *p) {
+  if (!p || p->nuc) return "";
+  static thread_local std::string out;
+  if (p->last_form_walk) return (out = "trunk_walk_kernel NW=" + std::to_string(p->NW)).c_str();
+  if (p->last_cut < 0) return "";
+  const hyhip::PruneDispatch &d = p->last_dispatch;
+  char b[160];
+  int n = snprintf(b, sizeof b, "%s NW=%d", d.kernel, d.NW);
+  if (d.park >= 0) n += snprintf(b + n, sizeof b - n, " park=%d", d.park);
+  else n += snprintf(b + n, sizeof b - n, " T=%d%s", d.T, d.on_chain ? " on-chain" : "");
+  if (d.inst[0]) n += snprintf(b + n, sizeof b - n, " %s", d.inst);
+  if (p->last_cut > 0) n += snprintf(b + n, sizeof b - n, "; chain m=%d", p->last_cut);
+  else n += snprintf(b + n, sizeof b - n, "; levels");
+  if (p->last_rerooted) snprintf(b + n, sizeof b - n, "; re-rooted");
+  return (out = b).c_str();
+}
+
 int64_t hyphy_hip_prune_timings(hyphy_hip_partition *p, double *out_ms, int64_t n) {
   if (!p || !out_ms || n <= 0 || p->shards.empty()) return 0;
   Shard &s = p->shards[0];
@@ -1602,7 +1619,9 @@ int hyphy_hip_download_partials(hyphy_hip_partition *p, int64_t cat, double *ino
 int hyphy_hip_set_pinned_states(hyphy_hip_partition *p, int64_t node, const int64_t *states) {
   if (!p) return fail("partition == NULL");
   if (node < 0 || !states) {
-    if (p->pin_node >= 0 && p->rr_use) p->cached_valid = 0;  // (back to the re-rooted form of the steady-state passes)
+    // (back to the re-rooted form of the steady-state passes, the tuner's or HYPHY_HIP_REROOT=1's: the pinned passes' schedule is
+    //  not one, and an unchanged update list would keep it)
+    if (p->pin_node >= 0 && (p->rr_use || sw::reroot() == 1)) p->cached_valid = 0;
     p->pin_node = -1;
     return 0;
   }

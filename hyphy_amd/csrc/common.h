@@ -342,6 +342,15 @@ void launch_mix_images(const double *P, const int *off, const double *w, const i
                        double *PTg, double *Prow, hipStream_t stream, double *PTrow = nullptr);
 void launch_site_fit(const SiteFitArgs &a, hipStream_t stream);
 int launch_prune_mfma(const PruneArgs &a, hipStream_t stream);  // -1: no instantiation serves this launch form (nothing launched)
+// the instantiation the calling thread's last launch_prune_mfma dispatched, as its launcher recorded it (hyphy_hip_last_prune_form)
+struct PruneDispatch {
+  const char *kernel = "";  // prune_wave_kernel / prune_mfma_kernel ("": nothing launched yet)
+  int NW = 0, T = 0;        // row blocks; tiles per workgroup
+  int park = -1;            // wave kernel: parking slots in LDS (0 / 1 / 2)
+  const char *inst = "";    // wave kernel: occ2 / occ3 / occ3+pre (waves per SIMD it is compiled for, deposit prefetch); either: trunk, trace
+  bool on_chain = false;    // row-split kernel: the chain-schedule instantiation
+};
+const PruneDispatch &last_prune_dispatch();
 void launch_prune_nuc(const NucArgs &a, hipStream_t stream, const ExpmArgs *ex = nullptr);  // ex: matrix exponentials folded into the launch
 bool prune_nuc_folds_expm(int L, int S_pad, int n_ops);
 bool prune_nuc_fuses_reduce(const NucArgs &a, bool folded);  // launch_prune_nuc will run the instantiation that carries the fused final combine

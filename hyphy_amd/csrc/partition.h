@@ -365,6 +365,12 @@ struct hyphy_hip_partition {
   int chain_m_forced = 0;                    // cut chosen by the schedule tuner: > 0 source size limit m, -1 level-peeled fragments, 0 heuristic
   int64_t tuned_for = 0;                     // batch_classes the tuner ran for (0: not yet)
   std::string tune_report;                   // what the tuner measured (hyphy_hip_schedule_info)
+  int chain_m_used = 0;                      // source size limit m of the current chain schedule (build_schedule; 0: not a chain schedule)
+  // the pruning launch of the last evaluation, for hyphy_hip_last_prune_form (which puts it into words): what the launcher
+  // dispatched, the cut it ran under (-1: none yet / nothing to prune, 0: levels, > 0: chain with that m), re-rooted, the trunk walk
+  hyhip::PruneDispatch last_dispatch;
+  int last_cut = -1;
+  bool last_rerooted = false, last_form_walk = false;
   double tuned_ms = 0.;                      // duration of the pruning pass under the schedule it chose
   bool rep_decided = false;                  // subtree repeats on / off has been settled by measurement (or by the caller)
   std::string rep_report;                    // ... and what was measured

@@ -2166,6 +2166,13 @@ __global__ void unpack_partials_kernel(const double *__restrict__ partials, int 
   out[idx] = partials[((size_t)node * ntiles + tile) * TILE + within];
 }
 
+// What the launcher below dispatched, written down at the branch that picks the instantiation (host side only: the kernels and
+// PruneArgs know nothing of it).  hyphy_hip_last_prune_form reports it, so that a launch that quietly took another instantiation
+// than the one asked for can be seen.
+thread_local PruneDispatch g_dispatch;
+void note_wave_dispatch(int NW, int park, const char *inst) { g_dispatch = PruneDispatch{"prune_wave_kernel", NW, 1, park, inst, false}; }
+void note_team_dispatch(int NW, int T, bool on_chain, const char *inst) { g_dispatch = PruneDispatch{"prune_mfma_kernel", NW, T, -1, inst, on_chain}; }
+
 template <int NW, bool CLDS>
 int launch_prune_T(const PruneArgs &a, hipStream_t stream) {
   // Chain grids (tiles, classes, sources): workgroup b runs on XCD b mod 8 and the grid is linearised x-fastest, so with the
@@ -2181,22 +2188,26 @@ int launch_prune_T(const PruneArgs &a, hipStream_t stream) {
     const dim3 block1(64);
     const size_t lds1 = CLDS ? (size_t)a.L * 16 * sizeof(int16_t) : 0;
     if (a.leaf_tab && a.timeline && NW == 4 && CLDS) {  // tracing build of the trunk (HYPHY_HIP_TIMELINE with HYPHY_HIP_REPEATS=1)
+      note_wave_dispatch(4, a.n_slots <= 3 ? 1 : 2, "occ2 trace trunk");
       if (a.n_slots <= 3) hipLaunchKernelGGL((prune_wave_kernel<4, 1, true, true, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       else hipLaunchKernelGGL((prune_wave_kernel<4, 2, true, true, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       return 0;
     }
     if (a.leaf_tab && NW == 4 && CLDS && (a.wave_variant == 2 || a.wave_variant == 3) && a.n_slots <= 2) {  // three waves per SIMD, see below
+      note_wave_dispatch(4, 0, a.wave_variant == 2 ? "occ3 trunk" : "occ3+pre trunk");
       if (a.wave_variant == 2) hipLaunchKernelGGL((prune_wave_kernel<4, 0, true, false, true, 3, false, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       else hipLaunchKernelGGL((prune_wave_kernel<4, 0, true, false, true, 3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       return 0;
     }
     if (a.leaf_tab) {  // the trunk of a class-compressed partition
+      note_wave_dispatch(NW, a.n_slots <= 2 ? 0 : (a.n_slots == 3 ? 1 : 2), "occ2 trunk");
       if (a.n_slots <= 2) hipLaunchKernelGGL((prune_wave_kernel<NW, 0, CLDS, false, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       else if (a.n_slots == 3) hipLaunchKernelGGL((prune_wave_kernel<NW, 1, CLDS, false, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       else hipLaunchKernelGGL((prune_wave_kernel<NW, 2, CLDS, false, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       return 0;
     }
     if (a.timeline && NW == 4 && CLDS) {  // tracing build (HYPHY_HIP_TIMELINE)
+      note_wave_dispatch(4, a.n_slots <= 3 ? 1 : 2, "occ2 trace");
       if (a.n_slots <= 3) hipLaunchKernelGGL((prune_wave_kernel<4, 1, true, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       else hipLaunchKernelGGL((prune_wave_kernel<4, 2, true, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       return 0;
@@ -2204,14 +2215,17 @@ int launch_prune_T(const PruneArgs &a, hipStream_t stream) {
     // three waves per SIMD (the tuner's second stage): finalised node in LDS instead of 32 registers, no parking slot; 2 without,
     // 3 with the deposit prefetch
     if (NW == 4 && CLDS && a.wave_variant == 2 && a.n_slots <= 2) {
+      note_wave_dispatch(4, 0, "occ3");
       hipLaunchKernelGGL((prune_wave_kernel<4, 0, true, false, true, 3, false>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       return 0;
     }
     if (NW == 4 && CLDS && a.wave_variant == 3 && a.n_slots <= 2) {
+      note_wave_dispatch(4, 0, "occ3+pre");
       hipLaunchKernelGGL((prune_wave_kernel<4, 0, true, false, true, 3, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
       return 0;
     }
     // production: two waves per SIMD, 0 / 1 / 2 parking slots in LDS (the schedule was compiled for a.n_slots - 2 of them)
+    note_wave_dispatch(NW, a.n_slots <= 2 ? 0 : (a.n_slots == 3 ? 1 : 2), "occ2");
     if (a.n_slots <= 2) hipLaunchKernelGGL((prune_wave_kernel<NW, 0, CLDS>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
     else if (a.n_slots == 3) hipLaunchKernelGGL((prune_wave_kernel<NW, 1, CLDS>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
     else hipLaunchKernelGGL((prune_wave_kernel<NW, 2, CLDS>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
@@ -2219,6 +2233,7 @@ int launch_prune_T(const PruneArgs &a, hipStream_t stream) {
   }
   if (a.leaf_tab && a.variant != 1) {  // the trunk of a class-compressed partition under the row-split workgroup kernel (r06)
     if constexpr (NW == 4 && CLDS) {
+      if (a.T == 1) note_team_dispatch(4, 1, a.chain != 0, "trunk");
       if (a.T == 1 && a.chain) {
         hipLaunchKernelGGL((prune_mfma_kernel<4, 1, true, false, 0, true, false, true>), grid, block, lds, stream, a.ops, a);
         return 0;
@@ -2231,6 +2246,7 @@ int launch_prune_T(const PruneArgs &a, hipStream_t stream) {
     return -1;  // (no other form of this mode exists: the caller reports it — a skipped launch would leave the trunk stale)
   }
   if (a.variant == 2 && a.chain && a.T == 1) {  // row-split workgroups on a chain schedule: grid = (tiles, classes, sources)
+    note_team_dispatch(NW, 1, true, "");
     if constexpr (NW == 4 && CLDS) {
       if (a.red_out) {
         hipLaunchKernelGGL((prune_mfma_kernel<4, 1, true, false, 0, true, true>), grid, block, lds, stream, a.ops, a);
@@ -2241,9 +2257,11 @@ int launch_prune_T(const PruneArgs &a, hipStream_t stream) {
     return 0;
   }
   if (a.timeline) {  // tracing build of the kernel (HYPHY_HIP_TIMELINE), T = 1 only
+    note_team_dispatch(NW, 1, false, "trace");
     hipLaunchKernelGGL((prune_mfma_kernel<NW, 1, CLDS, true>), grid, block, lds, stream, a.ops, a);
     return 0;
   }
+  note_team_dispatch(NW, a.T <= 3 ? a.T : 4, false, "");
   if (NW == 4 && CLDS && a.T == 1 && a.ablate) {  // diagnostic ablation builds (results invalid)
 #define ABL_CASE(v)                                                                                     \
   case v:                                                                                               \
@@ -2284,6 +2302,8 @@ int launch_prune_NW(const PruneArgs &a, hipStream_t stream) {
 }
 
 }  // namespace
+
+const PruneDispatch &last_prune_dispatch() { return g_dispatch; }
 
 int launch_prune_mfma(const PruneArgs &a, hipStream_t stream) {
   if (a.n_ops <= 0) return 0;

@@ -201,6 +201,7 @@ void build_schedule_impl(hyphy_hip_partition *p, const int64_t *update_nodes, in
   }
   p->chain = false;
   p->rr_active = false;
+  p->chain_m_used = 0;
   p->jn_host.clear();
   // ---- chain schedules (wave-per-tile kernel, full passes) -------------------------------------------------
   // Bottom subtrees of at most `m` internal nodes become SOURCE programs (walked serially by one wave, exactly like a
@@ -359,6 +360,7 @@ void build_schedule_impl(hyphy_hip_partition *p, const int64_t *update_nodes, in
       p->levels.push_back({0, (int)p->programs.size()});
       p->chain = true;
       p->rr_active = rr;
+      p->chain_m_used = m;
       if (sw::verbose()) {
         fprintf(stderr, "[hyphy_hip] chain schedule: m = %d, %zu sources (root node / distance):", m, srcs.size());
         for (const Src &sr : srcs) fprintf(stderr, " %d/%d", sr.root, sr.prio);

@@ -47,6 +47,7 @@ int launch_prune_current(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_ba
   if (walk) {
     if (launch_trunk_walk(p, s, cat, n_cat_batch, eval != nullptr, &pa)) return -1;  // (its own timeline: evaluations only)
     if (eval) s.last_walk = true;  // (hyphy_hip_prune_kernel_name speaks of evaluations: the tuner's passes leave it alone)
+    if (eval) p->last_form_walk = true;
     return 0;
   }
   if (eval) s.last_walk = false;
@@ -59,6 +60,12 @@ int launch_prune_current(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_ba
     if (launch_prune_mfma(pa, s.stream))  // (the two messages differed before the copies were joined: kept)
       return fail("internal: no pruning kernel for this launch form (variant " + std::to_string(p->variant) +
                   (eval ? ", " + std::to_string(p->NW) + " row blocks)" : ")"));
+  }
+  if (eval) {  // (hyphy_hip_last_prune_form: what the launcher dispatched, and the cut it ran under)
+    p->last_form_walk = false;
+    p->last_dispatch = last_prune_dispatch();
+    p->last_cut = (p->levels.empty() || pa.n_ops <= 0) ? -1 : (p->chain ? p->chain_m_used : 0);
+    p->last_rerooted = p->rr_active;
   }
   return 0;
 }
@@ -140,10 +147,11 @@ int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch) {
   // anything: analyses that create one likelihood function after another on the same tree (FEL: one per site) tune once.
   // (HYPHY_HIP_TUNE_CACHE=0: every partition measures for itself.)
   struct Key {
-    int64_t D, L, I, ntiles, classes, forced, mode;
+    int64_t D, L, I, ntiles, classes, forced, mode, form;
     uint64_t topo;
     bool operator<(const Key &o) const {
-      return std::tie(D, L, I, ntiles, classes, forced, mode, topo) < std::tie(o.D, o.L, o.I, o.ntiles, o.classes, o.forced, o.mode, o.topo);
+      return std::tie(D, L, I, ntiles, classes, forced, mode, form, topo) <
+             std::tie(o.D, o.L, o.I, o.ntiles, o.classes, o.forced, o.mode, o.form, o.topo);
     }
   };
   struct Choice { Cand cand; double ms; };
@@ -154,7 +162,12 @@ int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch) {
   for (int64_t v : p->vw().parents) topo = (topo ^ (uint64_t)v) * 1099511628211ull;
   if (p->mode == 1)  // (the trunk depends on the alignment: leaves that are class tables gather differently from plain ones)
     for (int sl : p->vw().slot) topo = (topo ^ (uint64_t)sl) * 1099511628211ull;
-  const Key key{p->D, p->vw().L, p->vw().I, s.ntiles, n_cat_batch, p->kernel_forced ? p->variant + (p->trunk_walk ? 8 : 0) : -1, p->mode, topo};
+  // (form: the switches that take candidates out of the stages below — HYPHY_HIP_SLOTS and _WAVE_VARIANT the second stage's, _REROOT
+  //  the third's — and the slot budget the wave kernel's candidates are compiled for.  A choice made without them must not be taken over
+  //  by a partition created or evaluated under one of them: the three-waves instantiation has no parking slot and ignores both.)
+  const int64_t form = (sw::wave_form_forced() ? 1 : 0) | (int64_t)(sw::wave_variant(-1) + 1) << 1 | (int64_t)p->n_slots_wave << 8 |
+                       (int64_t)(sw::given(sw::REROOT) ? 2 + (sw::reroot() & 1) : 0) << 12;
+  const Key key{p->D, p->vw().L, p->vw().I, s.ntiles, n_cat_batch, p->kernel_forced ? p->variant + (p->trunk_walk ? 8 : 0) : -1, p->mode, form, topo};
   if (cache_on) {
     std::lock_guard<std::mutex> lock(cache_mutex);
     auto hit = cache.find(key);

@@ -605,6 +605,15 @@ int hyphy_hip_prune_launches(hyphy_hip_partition *p);
  * "class_table_team_kernel" in front of it, and answer "trunk_walk_kernel" once their full passes run the trunk as one
  * row-split walk per tile (r06; first passes, partial updates and pinned states keep the pruning kernels). */
 const char *hyphy_hip_prune_kernel_name(const hyphy_hip_partition *p);
+/* Form of the pruning launch of this partition's last evaluation (the schedule tuner's own passes leave it alone), written down where
+ * the launcher picks the instantiation — a launch that could not be served by the instantiation asked for says which one ran:
+ *   "prune_wave_kernel NW=<row blocks> park=<0|1|2 parking slots> <occ2|occ3|occ3+pre>; <cut>[; re-rooted]"
+ *   "prune_mfma_kernel NW=<row blocks> T=<tiles per workgroup>[ on-chain]; <cut>[; re-rooted]"
+ * with <cut> "levels" (level-peeled fragments, and every partial update) or "chain m=<source size limit>".  The instantiation may be
+ * followed by " trunk" (class-compressed partitions) or " trace" (HYPHY_HIP_TIMELINE); a trunk walked by trunk_walk_kernel answers
+ * "trunk_walk_kernel NW=<row blocks>".  "" before the first evaluation, for 4-state partitions and after an evaluation that had
+ * nothing to prune.  Valid until the calling thread's next call of this function. */
+const char *hyphy_hip_last_prune_form(const hyphy_hip_partition *p);
 /* Name of the matrix-exponential kernel the calling thread's last launch ran, as it appears in a rocprofv3 kernel trace:
  * "expm_nuc_kernel" (4 states, row-major images), "expm_mfma_kernel<1,1>" / "<2,2>" / "<3,1>" (up to 16 / 32 / 48 states),
  * "expm64_kernel<1>" / "<2>" / "<4>" (49-64 states: 1, 2 or 4 workgroups per matrix, by batch size and compute-unit count) or
