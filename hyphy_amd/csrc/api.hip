@@ -416,6 +416,7 @@ template <typename Args>
 void EvalCtx::wire_fused_combine(Args &a, int *red_done) {
   double *const d_logl_out = rq.d_logl_out, *rec = s.d_hout ? s.d_hout : s.out;
   fused_reduce = true;
+  if (&s == &p->shards[0]) p->last_reduce = {"fused", n_wg, false};
   a.red_out = d_logl_out ? d_logl_out : rec, a.red_rec = d_logl_out ? s.out + 1 : rec + 1;
   a.red_status = d_logl_out ? nullptr : s.status;
   a.red_seq = next_seq(s, !d_logl_out), a.red_done = red_done;
@@ -541,10 +542,14 @@ int EvalCtx::stage_reduce() {
     double *o0 = d_logl_out ? d_logl_out : rec, *o1 = d_logl_out ? s.out + 1 : rec + 1;
     const int *st = d_logl_out ? nullptr : s.status;
     const double seq = next_seq(s, !d_logl_out);
+    hyphy_hip_partition::ReduceForm form;
     if (n_ops > 0 && !rq.floor_log)  // the pruning kernel left per-workgroup partial sums
-      launch_wg_reduce(s.wg_sum, s.wg_cnt, s.wg_flag, n_wg, o0, o1, st, s.stream, seq);
-    else  // nothing was recomputed (or category mode): reduce the stored per-pattern values
+      form = {launch_wg_reduce(s.wg_sum, s.wg_cnt, s.wg_flag, n_wg, o0, o1, st, s.stream, seq), n_wg, false};
+    else {  // nothing was recomputed (or category mode): reduce the stored per-pattern values
       launch_site_reduce(site_lik(), site_cnt(), s.freq, s.S_pad, rq.floor_log ? 1 : 0, o0, o1, st, s.stream, seq);
+      form = {"site", s.S_pad, rq.floor_log};
+    }
+    if (&s == &p->shards[0]) p->last_reduce = form;
   }
   if (p->all_timings) HIPCHK(hipEventRecord(s.ev[3], s.stream));
   HIPCHK(hipGetLastError());
@@ -799,6 +804,7 @@ int mix_and_reduce_categories(hyphy_hip_partition *p, const double *weights, boo
     launch_mix_categories(s.site_lik, s.site_cnt, s.weights, (int)p->C, s.S_pad, s.mixed_lik, s.mixed_cnt, s.stream);
     double *rec = s.d_hout ? s.d_hout : s.out;
     launch_site_reduce(s.mixed_lik, s.mixed_cnt, s.freq, s.S_pad, 1, rec, rec + 1, s.status, s.stream, next_seq(s, rec == s.d_hout));
+    if (&s == &p->shards[0]) p->last_reduce = {"site", s.S_pad, true};
   }
   return 0;
 }
@@ -838,6 +844,15 @@ const char *hyphy_hip_last_prune_form(const hyphy_hip_partition *p) {
   else n += snprintf(b + n, sizeof b - n, "; levels");
   if (p->last_rerooted) snprintf(b + n, sizeof b - n, "; re-rooted");
   return (out = b).c_str();
+}
+
+const char *hyphy_hip_last_reduce_form(const hyphy_hip_partition *p) {
+  if (!p || !p->last_reduce.kind[0]) return "";
+  static thread_local std::string out;
+  const auto &f = p->last_reduce;
+  out = std::string(f.kind) + (strcmp(f.kind, "site") ? " n=" : " S_pad=") + std::to_string(f.n) + (f.floor ? " floor" : "");
+  if (p->shards.size() > 1) out += "; host x" + std::to_string(p->shards.size());
+  return out.c_str();
 }
 
 int64_t hyphy_hip_prune_timings(hyphy_hip_partition *p, double *out_ms, int64_t n) {
@@ -1810,7 +1825,8 @@ int hyphy_hip_branch_cache_evaluate(hyphy_hip_partition *p, int64_t cat, int64_t
     ba.wg_flag = s.wg_flag;
     launch_bc_eval(ba, s.stream);
     double *rec = s.d_hout ? s.d_hout : s.out;
-    launch_wg_reduce(s.wg_sum, s.wg_cnt, s.wg_flag, s.ntiles, rec, rec + 1, s.status, s.stream, next_seq(s, rec == s.d_hout));
+    const char *form = launch_wg_reduce(s.wg_sum, s.wg_cnt, s.wg_flag, s.ntiles, rec, rec + 1, s.status, s.stream, next_seq(s, rec == s.d_hout));
+    if (&s == &p->shards[0]) p->last_reduce = {form, s.ntiles, false};
     HIPCHK(hipGetLastError());
   }
   return result_tail(p, (int)cat, kCombineHost, kNoTimings, kSitesGathered, logl_out, site_lik_out, site_scaler_out);

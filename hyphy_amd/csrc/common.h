@@ -358,8 +358,8 @@ void launch_site_export(const double *lik, const int32_t *cnt, const int32_t *in
                         hipStream_t stream);
 void launch_site_reduce(const double *site_lik, const int32_t *site_cnt, const double *freq, int S_pad, int floor_log,
                         double *out_logl, double *out_cnt, const int *status, hipStream_t stream, double seq = 0.);
-void launch_wg_reduce(const double *wg_sum, const long long *wg_cnt, const int *wg_flag, int n, double *out_logl,
-                      double *out_cnt, const int *status, hipStream_t stream, double seq = 0.);
+const char *launch_wg_reduce(const double *wg_sum, const long long *wg_cnt, const int *wg_flag, int n, double *out_logl,
+                             double *out_cnt, const int *status, hipStream_t stream, double seq = 0.);  // the form it picked: "block", "multi_wave<8>", "wave"
 int prune_mfma_grid(const PruneArgs &a);
 bool prune_fuses_reduce(const PruneArgs &a);  // launch_prune_mfma has a fused-combine instantiation for this launch form
 int prune_nuc_grid(const NucArgs &a);

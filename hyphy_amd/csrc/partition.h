@@ -371,6 +371,9 @@ struct hyphy_hip_partition {
   hyhip::PruneDispatch last_dispatch;
   int last_cut = -1;
   bool last_rerooted = false, last_form_walk = false;
+  // the final combine of shard 0's last evaluation (hyphy_hip_last_reduce_form puts it into words): "fused" / "wave" / "multi_wave<8>" /
+  // "block" over n partials, or "site" over n = S_pad stored patterns, with the category floor or without ("": none yet)
+  struct ReduceForm { const char *kind = ""; int n = 0; bool floor = false; } last_reduce;
   double tuned_ms = 0.;                      // duration of the pruning pass under the schedule it chose
   bool rep_decided = false;                  // subtree repeats on / off has been settled by measurement (or by the caller)
   std::string rep_report;                    // ... and what was measured

@@ -2451,18 +2451,22 @@ void launch_site_reduce(const double *site_lik, const int32_t *site_cnt, const d
                      out, out_cnt, status, seq);
 }
 
-void launch_wg_reduce(const double *wg_sum, const long long *wg_cnt, const int *wg_flag, int n, double *out_logl,
-                      double *out_cnt, const int *status, hipStream_t stream, double seq) {
+const char *launch_wg_reduce(const double *wg_sum, const long long *wg_cnt, const int *wg_flag, int n, double *out_logl,
+                             double *out_cnt, const int *status, hipStream_t stream, double seq) {
   const int form = sw::reduce_form();
   const bool block_form = form == 1, multi_off = form == 2;
-  if (block_form)
+  if (block_form) {
     hipLaunchKernelGGL(wg_reduce_kernel, dim3(1), dim3(256), 0, stream, wg_sum, wg_cnt, wg_flag, n, out_logl, out_cnt, status, seq);
-  else if (n >= 2048 && !multi_off)
+    return "block";
+  }
+  if (n >= 2048 && !multi_off) {
     hipLaunchKernelGGL(multi_wave_reduce_kernel<8>, dim3(1), dim3(512), 0, stream, const_cast<double *>(wg_sum), const_cast<long long *>(wg_cnt),
                        const_cast<int *>(wg_flag), n, out_logl, out_cnt, status, seq);
-  else
-    hipLaunchKernelGGL(wave_reduce_kernel, dim3(1), dim3(64), 0, stream, const_cast<double *>(wg_sum), const_cast<long long *>(wg_cnt),
-                       const_cast<int *>(wg_flag), n, out_logl, out_cnt, status, seq);
+    return "multi_wave<8>";
+  }
+  hipLaunchKernelGGL(wave_reduce_kernel, dim3(1), dim3(64), 0, stream, const_cast<double *>(wg_sum), const_cast<long long *>(wg_cnt),
+                     const_cast<int *>(wg_flag), n, out_logl, out_cnt, status, seq);
+  return "wave";
 }
 
 int prune_mfma_grid(const PruneArgs &a) { return a.ntiles / a.T; }

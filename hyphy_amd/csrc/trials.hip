@@ -375,6 +375,7 @@ int trials_common(const char *what, hyphy_hip_partition *p, int64_t n_trials, co
     }
     hipLaunchKernelGGL(trials_reduce_kernel, dim3((unsigned)n_trials), dim3(64), 0, s.stream, part_sum, part_cnt, part_flag, ntiles,
                        part_stride, d_tot);
+    if (&s == &p->shards[0]) p->last_reduce = {"wave", ntiles, false};  // (one wave per trial over its own partials)
     HIPCHK(hipGetLastError());
     int32_t h_status = 0;
     HIPCHK(hipMemcpyAsync(totals.data(), d_tot, (size_t)n_trials * sizeof(double), hipMemcpyDeviceToHost, s.stream));

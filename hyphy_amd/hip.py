@@ -22,7 +22,7 @@ EXPORTS = [
     "hyphy_hip_evaluate_device", "hyphy_hip_fetch_device_scalar", "hyphy_hip_plan_reroot", "hyphy_hip_plan_pattern_order", "hyphy_hip_plan_schedule", "hyphy_hip_evaluate_async", "hyphy_hip_collect", "hyphy_hip_evaluate_mixture", "hyphy_hip_evaluate_mixture_built", "hyphy_hip_comm_unique_id", "hyphy_hip_comm_init_rank", "hyphy_hip_comm_init_all", "hyphy_hip_allreduce_device", "hyphy_hip_evaluate_allreduce", "hyphy_hip_evaluate_built_allreduce", "hyphy_hip_last_allreduce_ms", "hyphy_hip_evaluate_categories", "hyphy_hip_download_partials",
     "hyphy_hip_expm_batch", "hyphy_hip_set_q_templates", "hyphy_hip_build_q", "hyphy_hip_q_buffer",
     "hyphy_hip_evaluate_built", "hyphy_hip_evaluate_built_sites", "hyphy_hip_update_q_templates", "hyphy_hip_evaluate_categories_built", "hyphy_hip_evaluate_categories_built_sites", "hyphy_hip_prune_timings", "hyphy_hip_prune_launches",
-    "hyphy_hip_prune_kernel_name", "hyphy_hip_last_prune_form", "hyphy_hip_branch_cache_build", "hyphy_hip_branch_cache_evaluate",
+    "hyphy_hip_prune_kernel_name", "hyphy_hip_last_prune_form", "hyphy_hip_last_reduce_form", "hyphy_hip_branch_cache_build", "hyphy_hip_branch_cache_evaluate",
     "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_joint_ancestral", "hyphy_hip_sample_ancestral", "hyphy_hip_sample_uniforms", "hyphy_hip_simulate", "hyphy_hip_simulate_uniforms", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
     "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_plan_switches", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
     "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error", "hyphy_hip_last_expm_kernel",
@@ -143,6 +143,8 @@ def load():
     lib.hyphy_hip_prune_kernel_name.argtypes = [vp]
     lib.hyphy_hip_last_prune_form.restype = C.c_char_p
     lib.hyphy_hip_last_prune_form.argtypes = [vp]
+    lib.hyphy_hip_last_reduce_form.restype = C.c_char_p
+    lib.hyphy_hip_last_reduce_form.argtypes = [vp]
     lib.hyphy_hip_set_repeats.restype = C.c_int
     lib.hyphy_hip_set_repeats.argtypes = [vp, C.c_int]
     lib.hyphy_hip_marginal_ancestral.restype = C.c_int
@@ -966,6 +968,10 @@ class HipPartition:
     def prune_form(self) -> str:
         """Form of the pruning launch of the last evaluation: kernel, row blocks, instantiation, cut (include/hyphy_hip.h)."""
         return self._lib.hyphy_hip_last_prune_form(self._h).decode()
+
+    def reduce_form(self) -> str:
+        """Which final combine produced the last evaluation's log-L, and over how many partials (include/hyphy_hip.h)."""
+        return self._lib.hyphy_hip_last_reduce_form(self._h).decode()
 
     def schedule_info(self) -> str:
         return self._lib.hyphy_hip_schedule_info(self._h).decode()

@@ -121,7 +121,12 @@ void hyphy_hip_destroy(hyphy_hip_partition *p);
  *   logl_out        sum_s f_s log L_s - 64 ln2 * scalers — the value ComputeBlock returns
  *                   (likefunc.cpp:11123).  -INFINITY if a pattern has likelihood 0
  *                   (tree_evaluator.cpp:4094-4112); NaN propagates (adapter then calls
- *                   _TerminateAndDump as tree_evaluator.cpp:4142 does).
+ *                   _TerminateAndDump as tree_evaluator.cpp:4142 does): a pattern whose likelihood is NaN or +INFINITY (a NaN in a
+ *                   matrix handed over with q_is_probability = 1, in root_freqs, or in an ambiguity vector) makes log L NaN, and
+ *                   NaN wins over -INFINITY when both occur.
+ *                   A pattern of frequency 0 takes no part in either sum, whatever its likelihood: zero, NaN or finite, it
+ *                   contributes nothing and raises neither flag (every combiner skips f_s == 0; the per-pattern outputs still
+ *                   carry its values).
  *                   A matrix the device cannot exponentiate (NaN, overflow, or a rate matrix with a POSITIVE diagonal entry —
  *                   which the reference restarts its way to the identity for, matrix.cpp:5854-5864) is a hard error (< 0,
  *                   "Failed to compute a valid transition matrix"); an asynchronous evaluation's log-L is then NaN.
@@ -259,6 +264,10 @@ int hyphy_hip_fetch_device_scalar(hyphy_hip_partition *p, const double *d_value,
  * schedule (classes are an extra batch dimension on the device) and mixes them exactly as
  * PopulateConditionalProbabilities' weighted-sum mode + SumUpSiteLikelihoods do
  * (likefunc2.cpp:820-853, 1484-1506).  q_dense is [C][n_q][D*D]; weights [C].
+ * The category floor: a pattern of frequency f whose MIXED likelihood is zero (impossible under every class) contributes exactly
+ * -1e6 * f to logl_out, with no exponent, and no -INFINITY (myLog, likefunc.cpp:644-661); a pattern impossible under some classes
+ * only is an ordinary finite term.  Only this entry point and its _built forms floor: hyphy_hip_evaluate answers -INFINITY, and so
+ * does hyphy_hip_branch_trials for C > 1.  NaN still propagates, and frequency-0 patterns are skipped as in hyphy_hip_evaluate.
  */
 int hyphy_hip_evaluate_categories(hyphy_hip_partition *p, const int64_t *update_nodes, int64_t n_update,
                                   const int64_t *q_nodes, int64_t n_q, const double *q_dense,
@@ -614,6 +623,18 @@ const char *hyphy_hip_prune_kernel_name(const hyphy_hip_partition *p);
  * "trunk_walk_kernel NW=<row blocks>".  "" before the first evaluation, for 4-state partitions and after an evaluation that had
  * nothing to prune.  Valid until the calling thread's next call of this function. */
 const char *hyphy_hip_last_prune_form(const hyphy_hip_partition *p);
+/* Which final combine turned the per-pattern values of this partition's last evaluation (hyphy_hip_evaluate and its kin, the category
+ * entry points, hyphy_hip_branch_cache_evaluate, hyphy_hip_branch_trials) into log L, written down where the launcher picks it:
+ *   "fused n=<partials>"          the last arriver of the pruning launch summed the n per-workgroup partial sums itself
+ *   "wave n=<partials>"           wave_reduce_kernel (fewer than 2048 partials, or HYPHY_HIP_REDUCE=wave); for branch trials: one wave
+ *                                 per trial over that trial's n partials
+ *   "multi_wave<8> n=<partials>"  multi_wave_reduce_kernel<8> (from 2048 partials)
+ *   "block n=<partials>"          wg_reduce_kernel (HYPHY_HIP_REDUCE=block)
+ *   "site S_pad=<padded patterns>[ floor]"  site_reduce_kernel over the stored per-pattern values (an evaluation that recomputed
+ *                                 nothing; " floor": behind the category mix, with the category floor)
+ * "" before the first evaluation.  A multi-shard partition reports shard 0, followed by "; host x<shards>" (the shard records meet in
+ * the host's compensated sum).  Valid until the calling thread's next call of this function. */
+const char *hyphy_hip_last_reduce_form(const hyphy_hip_partition *p);
 /* Name of the matrix-exponential kernel the calling thread's last launch ran, as it appears in a rocprofv3 kernel trace:
  * "expm_nuc_kernel" (4 states, row-major images), "expm_mfma_kernel<1,1>" / "<2,2>" / "<3,1>" (up to 16 / 32 / 48 states),
  * "expm64_kernel<1>" / "<2>" / "<4>" (49-64 states: 1, 2 or 4 workgroups per matrix, by batch size and compute-unit count) or
