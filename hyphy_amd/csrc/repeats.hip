@@ -40,6 +40,7 @@
 #include "devutil.h"
 #include "combine.h"
 #include "partition.h"
+#include "repeats_plan.h"
 
 namespace hyhip {
 
@@ -75,7 +76,6 @@ constexpr int kRepHeadStride = 1088;                 // ints between the words
 constexpr int kRepSyncExit = kRepQueues * kRepHeadStride;
 constexpr int kRepSyncDone = kRepSyncExit + kRepHeadStride;  // per (class, descriptor) finished tiles from here, same spacing
 constexpr int kRepStack = 24;                        // held tickets per wave (tree heights beyond that fall back to waiting)
-constexpr int kRepMaxInputs = 64;                    // inputs of a path whose class indices are staged in LDS (longer paths: cut by the host)
 constexpr int kRepAStages = 3;                       // A-operand chunks in flight ahead of the MFMAs of an edge product
 constexpr int kRepBStages = 2;                       // (row-split walk) B-operand chunks on their way out of LDS ahead of them
 
@@ -713,7 +713,6 @@ struct TrunkWalkArgs {
   int red_n;
   long long *dbg;             // diagnostic (HYPHY_HIP_WALK_TIMELINE): the lower phase's record per workgroup, or nullptr
 };
-constexpr int kWalkDepth = 3;
 
 // (AST: A chunks ahead of a product, DEPTH: waiting products, OCC: workgroups per CU the build allows — one production form: 3 / 3 / 5)
 template <int NW, bool TRACE = false, bool FUSE = false, int AST = kRepAStages, int DEPTH = kWalkDepth, int OCC = 5, int BST = kRepBStages>
@@ -960,7 +959,6 @@ __global__ __launch_bounds__(64 * NW, OCC) void trunk_walk_kernel(const int4 *__
 // class's representative pattern has at the leaf; an ambiguity code: the product with its resolution vector), a finished
 // child's edge product waits on a small per-thread stack in LDS (children are visited heaviest first: a subtree of n leaves needs
 // at most log2 n + 1 slots) — and only the root's rows are stored.  No table reads another: one launch, no synchronisation.
-constexpr int kNucStack = 8;
 struct RepNucArgs {
   const int32_t *map;
   double *tab;        // [rows][4]
@@ -1068,93 +1066,13 @@ void launch_class_tables(const RepArgs &a, int NW, hipStream_t stream, int team 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Host side: classes, compressed set, the trunk view, tables and maps (once per partition); item queues per pass.
+// Host side.  Once per partition: options -> plan (repeats_plan.hip: host only) -> per shard its tables and their upload -> the
+// trunk's starting mode -> report.  Per pass: the item queues.
 // ------------------------------------------------------------------------------------------------------------------
 
 namespace {
 
-// class ids of the pairs (a[s], b[s]) in order of first occurrence
-int pair_classes(const std::vector<int> &a, const std::vector<int> &b, std::vector<int> &out) {
-  std::unordered_map<uint64_t, int> seen;
-  seen.reserve(a.size() / 2 + 16);
-  out.resize(a.size());
-  int n = 0;
-  for (size_t s = 0; s < a.size(); s++) {
-    const uint64_t key = ((uint64_t)(uint32_t)a[s] << 32) | (uint32_t)b[s];
-    auto it = seen.find(key);
-    if (it == seen.end()) it = seen.emplace(key, n++).first;
-    out[s] = it->second;
-  }
-  return n;
-}
-
-// ... of a single column
-int column_classes(const std::vector<int> &a, std::vector<int> &out) {
-  std::unordered_map<int, int> seen;
-  out.resize(a.size());
-  int n = 0;
-  for (size_t s = 0; s < a.size(); s++) {
-    auto it = seen.find(a[s]);
-    if (it == seen.end()) it = seen.emplace(a[s], n++).first;
-    out[s] = it->second;
-  }
-  return n;
-}
-
-// class of every (internal node, pattern) bottom-up — the id of the tuple of the children's classes (a leaf: its code, ambiguity codes
-// included) in order of first occurrence — and the number of classes per node
-void count_classes(const std::vector<std::vector<int>> &children, int L, int I, const std::vector<int16_t> &codes, size_t SP,
-                   std::vector<std::vector<int>> &cls, std::vector<int> &U) {
-  cls.assign(I, std::vector<int>());
-  U.assign(I, 0);
-  std::vector<int> col(SP), tmp;
-  for (int n = 0; n < I; n++) {
-    std::vector<int> run;
-    bool first = true;
-    for (int c : children[n]) {
-      const std::vector<int> *cc;
-      if (c < L) {
-        for (size_t j = 0; j < SP; j++) col[j] = (int)codes[(size_t)c * SP + j];
-        cc = &col;
-      } else {
-        cc = &cls[c - L];
-      }
-      if (first) {
-        run = *cc;
-        first = false;
-      } else {
-        pair_classes(run, *cc, tmp);
-        run.swap(tmp);
-      }
-    }
-    U[n] = column_classes(run, cls[n]);
-  }
-}
-
-// the compressed set: internal nodes (never the root) with at most theta x patterns classes on every shard, all of whose internal
-// children are compressed too
-std::vector<char> compressed_set(const std::vector<std::vector<int>> &children, int L, int I, const std::vector<std::vector<int>> &U,
-                                 const std::vector<int> &S_pad, double theta) {
-  std::vector<char> comp(I, 0);
-  for (int n = 0; n < I - 1; n++) {
-    bool ok = true;
-    for (size_t k = 0; k < U.size(); k++)
-      if ((double)U[k][n] > theta * S_pad[k] || U[k][n] > 32000) ok = false;
-    for (int c : children[n])
-      if (c >= L && !comp[c - L]) ok = false;
-    if ((int)children[n].size() > kRepMaxInputs - 8) ok = false;  // (a star: its children's indices would not fit the wave's LDS list)
-    comp[n] = ok ? 1 : 0;
-  }
-  return comp;
-}
-
-}  // namespace
-
-// Decide the compressed set, build views[1] and every shard's tables.  `codes[k]`: shard k's leaf table [L][S_pad] in device
-// pattern order (padding patterns included: they are patterns like any other).  Leaves p->rep_on false when compression
-// would not pay (or cannot be used) — nothing else changes then.
-namespace {
-void rep_release(hyphy_hip_partition *p) {  // everything rep_setup_impl may have left behind: the partition runs plain
+void rep_release(hyphy_hip_partition *p) {  // everything rep_setup may have left behind: the partition runs plain
   for (Shard &s : p->shards) {
     if (hipSetDevice(s.device) != hipSuccess) continue;
     void **bufs[] = {(void **)&s.rep_tab, (void **)&s.rep_cnt, (void **)&s.rep_map, (void **)&s.rep_desc, (void **)&s.rep_sync,
@@ -1174,715 +1092,110 @@ void rep_release(hyphy_hip_partition *p) {  // everything rep_setup_impl may hav
   p->views[1] = hyphy_hip_partition::View();
   p->rep_on = false;
 }
-int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t>> &codes);
-}  // namespace
 
-// Subtree repeats are an optimisation: whatever goes wrong while they are set up (tables that do not fit the device, a failed
-// copy) leaves a partition that evaluates every node at every pattern — hyphy_hip_create never fails because of them.
-int rep_setup(hyphy_hip_partition *p, const std::vector<std::vector<int16_t>> &codes) {
-  const int rc = rep_setup_impl(p, codes);
-  if (rc != 0 || !p->rep_on) {
-    if (rc != 0) sw::note("subtree repeats not set up (%s): plain evaluation\n", g_last_error.c_str());
-    rep_release(p);
-    (void)hipGetLastError();
-    g_last_error.clear();
+RepOptions rep_options(const hyphy_hip_partition *p) {  // the switches, read at create
+  RepOptions o;
+  o.mode = sw::repeats();
+  o.per_pattern_forced = sw::per_pattern_forced();
+  o.theta = sw::rep_theta(0.35, &o.theta_given);
+  o.rho = sw::rep_rho(NAN);
+  o.min_gain = sw::rep_min_gain();
+  o.inline_chains = sw::rep_inline();
+  o.trunk_kernel = sw::trunk_kernel();
+  o.trunk_walk = sw::trunk_walk_at_create();
+  o.tune = sw::tune();
+  o.variant = p->variant;
+  o.n_slots = p->n_slots;
+  o.n_slots_wave = p->n_slots_wave;
+  return o;
+}
+
+RepPlanInput rep_plan_input(const hyphy_hip_partition *p) {
+  RepPlanInput in;
+  in.L = (int)p->L, in.I = (int)p->I;
+  in.parents = &p->parents, in.children = &p->children, in.leaf_has_ambig = &p->leaf_has_ambig;
+  in.nuc = p->nuc, in.NW = p->NW, in.C = (int)p->C;
+  for (const Shard &s : p->shards) in.S_pad.push_back(s.S_pad), in.ntiles.push_back(s.ntiles), in.T.push_back(s.T);
+  return in;
+}
+
+// One shard's tables onto its device, both forms (4 states: no ticket words, no walk).  The tables must leave the device room for
+// everything else the partition allocates later (deposits, mixtures, site fits): a quarter of what is free, or the caller's bound.
+int rep_upload_shard(hyphy_hip_partition *p, Shard &s, const RepShardTables &t, const std::vector<int4> &walk_prog) {
+  if (hipSetDevice(s.device) != hipSuccess) return fail("hipSetDevice failed");
+  s.rep_tabs = t.tabs;
+  s.rep_rows = t.rows;
+  const size_t tab_bytes = (size_t)p->C * t.rows * (p->nuc ? 4 : p->DP) * sizeof(double), cnt_bytes = (size_t)p->C * t.rows * sizeof(int32_t);
+  const size_t sync_bytes = p->nuc ? 0 : ((size_t)kRepQueues + 1 + (size_t)p->C * t.tabs.size()) * kRepHeadStride * sizeof(int);  // (= rep_sync_words(p) words)
+  {
+    size_t free_b = 0, total_b = 0, limit = (size_t)1 << 30;
+    const size_t need_b = tab_bytes + cnt_bytes + t.maps.size() * sizeof(int32_t) + t.ct.size() * sizeof(int16_t);
+    if (!sw::rep_max_mb(&limit) && hipMemGetInfo(&free_b, &total_b) == hipSuccess) limit = free_b / 4;  // (given: the caller's bound on the tables)
+    if (need_b > limit) return fail("class tables would take more than a quarter of the free device memory (or than HYPHY_HIP_REP_MAX_MB)");
   }
+  struct Block { void **ptr; const char *name; size_t bytes; const void *src; size_t src_bytes; };
+  const Block blocks[] = {
+      {(void **)&s.rep_tab, "s.rep_tab", tab_bytes, nullptr, 0},
+      {(void **)&s.rep_cnt, "s.rep_cnt", cnt_bytes, nullptr, 0},
+      {(void **)&s.rep_map, "s.rep_map", std::max<size_t>(1, t.maps.size()) * sizeof(int32_t), t.maps.data(), t.maps.size() * sizeof(int32_t)},
+      {(void **)&s.rep_desc, "s.rep_desc", t.desc.size() * sizeof(int4), t.desc.data(), t.desc.size() * sizeof(int4)},
+      {(void **)&s.rep_sync, "s.rep_sync", sync_bytes, nullptr, 0},
+      {(void **)&s.rep_codes_tile, "s.rep_codes_tile", t.ct.size() * sizeof(int16_t), t.ct.data(), t.ct.size() * sizeof(int16_t)},
+      {(void **)&s.rep_leaf, "s.rep_leaf", t.lt.size() * sizeof(int2), t.lt.data(), t.lt.size() * sizeof(int2)},
+      {(void **)&s.rep_walk, "s.rep_walk", walk_prog.size() * sizeof(int4), walk_prog.data(), walk_prog.size() * sizeof(int4)}};
+  for (const Block &b : blocks) {
+    if (b.bytes == 0) continue;
+    if (pool_malloc(b.ptr, b.bytes) != hipSuccess) return fail(std::string("hipMalloc failed (") + b.name + ")");
+    s.dev_bytes += b.bytes;
+    s.rep_bytes += b.bytes;
+  }
+  if (sw::poison()) {
+    hipMemset(s.rep_tab, 0xff, tab_bytes);
+    hipMemset(s.rep_cnt, 0xff, cnt_bytes);
+  }
+  if (s.rep_sync) hipMemset(s.rep_sync, 0, sync_bytes);
+  for (const Block &b : blocks)
+    if (b.src_bytes) hipMemcpy(*b.ptr, b.src, b.src_bytes, hipMemcpyHostToDevice);
+  s.rep_leaf_host = t.lt;
+  if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail("repeats: device initialisation failed");
   return 0;
 }
 
-namespace {
-// 4 states (see class_table_nuc_kernel): one descriptor per compressed subtree ROOT, walked whole; theta 0.9 by default (a walk costs
-// 16 multiply-adds per node: everything that repeats at all is worth a table).
-int rep_setup_nuc(hyphy_hip_partition *p, const std::vector<std::vector<int16_t>> &codes, const std::vector<std::vector<std::vector<int>>> &cls,
-                  const std::vector<std::vector<int>> &U, std::vector<char> &comp, bool forced) {
-  const int L = (int)p->L, I = (int)p->I;
-  const size_t nsh = p->shards.size();
-  // stack slots a subtree's walk needs when every node visits its internal children heaviest first
-  std::vector<int> need(I, 1);
-  std::vector<std::vector<int>> order(I);  // internal children (internal indices) in visiting order
-  for (int n = 0; n < I; n++) {
-    for (int c : p->children[n])
-      if (c >= L) order[n].push_back(c - L);
-    std::stable_sort(order[n].begin(), order[n].end(), [&](int x, int y) { return need[x] > need[y]; });
-    for (size_t j = 0; j < order[n].size(); j++) need[n] = std::max(need[n], (int)j + need[order[n][j]]);
-  }
-  for (int n = I - 1; n >= 0; n--)  // (parents first: a subtree too deep for the stack hands the role of root to its children)
-    if (comp[n] && (p->parents[L + n] < 0 || !comp[p->parents[L + n]]) && need[n] > kNucStack) comp[n] = 0;
-  {
-    double full = 0., repd = 0.;
-    for (int n = 0; n < I - 1; n++) {
-      full += p->shards[0].S_pad;
-      const bool root = comp[n] && !comp[p->parents[L + n]];
-      repd += comp[n] ? (root ? (double)U[0][n] : 0.) : (double)p->shards[0].S_pad;  // (nodes inside a walk cost next to nothing here)
-    }
-    if (!forced && repd > 0.5 * full) return 0;
-  }
-  p->rep_nodes.clear();
-  p->rep_desc_of.assign((size_t)L + I, -1);
-  for (int n = 0; n < I; n++) {
-    if (!comp[n] || comp[p->parents[L + n]]) continue;  // roots only
-    hyphy_hip_partition::RepNode rn;
-    rn.node = L + n;
-    rn.level = 0;
-    // post-order over the subtree, heaviest child first
-    std::vector<std::pair<int, size_t>> stack(1, std::make_pair(n, (size_t)0));
-    while (!stack.empty()) {
-      std::pair<int, size_t> &t = stack.back();
-      if (t.second < order[t.first].size()) {
-        const int c = order[t.first][t.second++];
-        stack.push_back(std::make_pair(c, (size_t)0));
-      } else {
-        const int x = t.first;
-        rn.path.push_back(L + x);
-        rn.flags.push_back((int)order[x].size());  // (4 states: finished children this node takes off the stack)
-        rn.kids.push_back(std::vector<int>());
-        rn.kid_desc.push_back(std::vector<int>());
-        for (int c : p->children[x])
-          if (c < L) {
-            rn.kids.back().push_back(c);
-            rn.kid_desc.back().push_back(-1);
-          }
-        stack.pop_back();
-      }
-    }
-    p->rep_desc_of[L + n] = (int)p->rep_nodes.size();
-    p->rep_nodes.push_back(rn);
-  }
-  const int ND = (int)p->rep_nodes.size();
-  if (ND == 0 || ND > 65535) return 0;
-  // the trunk view: ordinary leaves (ambiguity codes stay with the trunk kernel's own resolution-vector path) and compressed roots
-  hyphy_hip_partition::View &v = p->views[1];
-  v = hyphy_hip_partition::View();
-  std::vector<int> vint(I, -1);
-  for (int n = 0; n < I; n++)
-    if (!comp[n]) vint[n] = v.I++;
-  std::vector<int> leaf_nodes, vleaf((size_t)L + I, -1);
-  for (int n = 0; n < I; n++)
-    if (!comp[n])
-      for (int c : p->children[n])
-        if (c < L || comp[c - L]) {
-          vleaf[c] = (int)leaf_nodes.size();
-          leaf_nodes.push_back(c);
-        }
-  v.L = (int)leaf_nodes.size();
-  if (v.L > 65535 || v.L < 1) return 0;
-  v.parents.assign((size_t)v.L + v.I, -1);
-  v.children.assign(v.I, std::vector<int>());
-  v.slot.assign((size_t)v.L + v.I, 0);
-  v.leaf_has_ambig.assign(v.L, 0);
-  for (int n = 0; n < I; n++) {
-    if (comp[n]) continue;
-    v.slot[v.L + vint[n]] = L + n;
-    const int64_t par = p->parents[L + n];
-    v.parents[v.L + vint[n]] = par < 0 ? -1 : vint[par];
-    for (int c : p->children[n]) {
-      if (c < L || comp[c - L]) {
-        v.children[vint[n]].push_back(vleaf[c]);
-        v.parents[vleaf[c]] = vint[n];
-        v.slot[vleaf[c]] = c;
-        if (c < L) v.leaf_has_ambig[vleaf[c]] = p->leaf_has_ambig[c];
-      } else {
-        v.children[vint[n]].push_back(v.L + vint[c - L]);
-      }
-    }
-    std::sort(v.children[vint[n]].begin(), v.children[vint[n]].end());
-  }
-  for (size_t k = 0; k < nsh; k++) {
-    Shard &s = p->shards[k];
-    if (hipSetDevice(s.device) != hipSuccess) return fail("hipSetDevice failed");
-    const size_t SP = (size_t)s.S_pad;
-    s.rep_tabs.assign(ND, RepTable());
-    std::vector<int32_t> maps;
-    int64_t rows = 0;
-    std::vector<int4> desc((size_t)2 * ND);
-    for (int d = 0; d < ND; d++) {
-      const hyphy_hip_partition::RepNode &rn = p->rep_nodes[d];
-      RepTable &t = s.rep_tabs[d];
-      const std::vector<int> &cl = cls[k][rn.node - L];
-      t.U = U[k][rn.node - L];
-      t.rows = (t.U + 15) / 16 * 16;
-      t.row0 = rows;
-      rows += t.rows;
-      std::vector<int> first_pat(t.rows, -1);
-      for (size_t j = 0; j < SP; j++)
-        if (first_pat[cl[j]] < 0) first_pat[cl[j]] = (int)j;
-      for (int u = t.U; u < t.rows; u++) first_pat[u] = first_pat[0];
-      const int64_t map0 = (int64_t)maps.size();
-      int n_in = 0;
-      for (size_t x = 0; x < rn.path.size(); x++)
-        for (int c : rn.kids[x]) {
-          for (int u = 0; u < t.rows; u++) maps.push_back((int32_t)codes[k][(size_t)c * SP + first_pat[u]]);
-          n_in++;
-        }
-      t.map0.push_back(map0);
-      const int node0 = (int)desc.size();
-      desc[2 * d] = make_int4((int)t.row0, t.U, (int)rn.path.size(), node0);
-      desc[2 * d + 1] = make_int4((int)map0, t.rows, 0, n_in);
-      desc.resize(desc.size() + rn.path.size());
-      for (size_t x = 0; x < rn.path.size(); x++) {
-        desc[node0 + x] = make_int4(rn.path[x], (int)rn.kids[x].size(), (int)desc.size(), rn.flags[x]);
-        for (int c : rn.kids[x]) desc.push_back(make_int4(-1, c, 0, -1));
-      }
-    }
-    s.rep_rows = rows;
-    if (maps.size() > 0x7fffffffull || rows > 0x7fffffffll) return 0;
-    std::vector<int16_t> ct((size_t)v.L * SP, 0);  // the trunk's leaf table, row-major [view leaf][pattern]: state codes / class ids
-    std::vector<int2> lt(v.L);
-    for (int vl = 0; vl < v.L; vl++) {
-      const int c = leaf_nodes[vl], d = p->rep_desc_of[c];
-      lt[vl] = d >= 0 ? make_int2((int)s.rep_tabs[d].row0, (int)s.rep_tabs[d].row0) : make_int2(-1, c);
-      for (size_t j = 0; j < SP; j++) ct[(size_t)vl * SP + j] = (int16_t)(d < 0 ? (int)codes[k][(size_t)c * SP + j] : cls[k][c - L][j]);
-    }
-    {
-      size_t free_b = 0, total_b = 0, limit = (size_t)1 << 30;
-      const size_t need_b = (size_t)p->C * rows * 36 + maps.size() * 4 + ct.size() * 2;
-      if (!sw::rep_max_mb(&limit) && hipMemGetInfo(&free_b, &total_b) == hipSuccess) limit = free_b / 4;
-      if (need_b > limit) return fail("class tables would take more than a quarter of the free device memory (or than HYPHY_HIP_REP_MAX_MB)");
-    }
-#define R_(ptr, bytes)                                                                  \
-  if (pool_malloc((void **)&(ptr), (bytes)) != hipSuccess) return fail("hipMalloc failed (" #ptr ")"); \
-  s.dev_bytes += (size_t)(bytes);                                                                      \
-  s.rep_bytes += (size_t)(bytes);
-    R_(s.rep_tab, (size_t)p->C * rows * 4 * sizeof(double));
-    R_(s.rep_cnt, (size_t)p->C * rows * sizeof(int32_t));
-    R_(s.rep_map, std::max<size_t>(1, maps.size()) * sizeof(int32_t));
-    R_(s.rep_desc, desc.size() * sizeof(int4));
-    R_(s.rep_codes_tile, ct.size() * sizeof(int16_t));
-    R_(s.rep_leaf, lt.size() * sizeof(int2));
-#undef R_
-    if (sw::poison()) {
-      hipMemset(s.rep_tab, 0xff, (size_t)p->C * rows * 4 * sizeof(double));
-      hipMemset(s.rep_cnt, 0xff, (size_t)p->C * rows * sizeof(int32_t));
-    }
-    hipMemcpy(s.rep_map, maps.data(), maps.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    hipMemcpy(s.rep_desc, desc.data(), desc.size() * sizeof(int4), hipMemcpyHostToDevice);
-    hipMemcpy(s.rep_codes_tile, ct.data(), ct.size() * sizeof(int16_t), hipMemcpyHostToDevice);
-    hipMemcpy(s.rep_leaf, lt.data(), lt.size() * sizeof(int2), hipMemcpyHostToDevice);
-    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail("repeats: device initialisation failed");
-  }
+// What the trunk's schedules start from (the tuner refines them).  4 states: the partition's own kernel, one leaf per entry
+// (prune_nuc_kernel), and on / off settled here by the plan's arithmetic.  Otherwise the wave-per-tile kernel, no re-rooting.
+void seed_trunk_mode(hyphy_hip_partition *p, const RepOptions &opt) {
   p->rep_resident.assign(p->C, 0);
   p->rep_cached_valid = false;
   hyphy_hip_partition::ModeState &ms = p->saved_mode[1];
-  ms.variant = p->variant;
-  ms.wave_variant = 0;
-  ms.n_slots = p->n_slots;   // (2 + kNucParkSlots)
-  ms.chain_m_forced = 0;
-  ms.rr_use = false;
+  ms = hyphy_hip_partition::ModeState();
+  ms.variant = p->nuc ? opt.variant : 1;
+  ms.n_slots = p->nuc ? opt.n_slots : opt.n_slots_wave;  // (4 states: 2 + kNucParkSlots)
   ms.kernel_forced = true;
-  ms.tuned_for = 0;
-  ms.nuc_leaf_pairs = false;  // (the trunk goes through prune_nuc_kernel: one leaf per entry)
   p->rep_on = true;
-  p->rep_decided = true;       // (4 states: decided here, by the arithmetic above)
-  if (sw::verbose()) {
-    long long rows = 0, lower = 0;
-    for (int d = 0; d < ND; d++) {
-      rows += p->shards[0].rep_tabs[d].rows;
-      lower += (long long)p->shards[0].rep_tabs[d].rows * (long long)p->rep_nodes[d].path.size();
-    }
-    fprintf(stderr, "[hyphy_hip] subtree repeats (4 states): %d compressed subtrees walked per class (%lld classes on shard 0, %lld node visits), trunk of %d "
-                    "internal nodes over %d leaves (every pattern at every node: %lld)\n",
-            ND, rows, lower, v.I, v.L, (long long)(I - 1) * p->shards[0].S_pad);
+  if (p->nuc) {
+    p->rep_decided = true;
+    return;
   }
-  return 0;
-}
-}  // namespace
-
-// The trunk as one post-order walk per tile (trunk_walk_kernel): heaviest internal child first — its chain stays in the running
-// product —, every other internal child a chain of its own behind a push (flag 1 on its first walked node, 2 on the child itself).
-// Two forms: ONE workgroup per tile walks everything; TWO split the subtrees below the root (longest-processing-time-first); each
-// chain ends with a node -1: the root's own leaf children (first chain only) and the hand-over / epilogue.
-struct WalkPlan {
-  struct Node { int node, n_in, in0, flags; };  // node: view-internal index (-1: the chain's end at the root); in0: first entry of `inputs`
-  std::vector<Node> nodes;
-  std::vector<int> inputs;                      // view leaves
-  std::vector<int> one_range, two_range;        // [first, end) node ranges: the one-chain form; the two chains
-  int max_depth = 0;
-  bool two = false;
-};
-static WalkPlan plan_trunk_walk(const hyphy_hip_partition::View &v) {
-  WalkPlan wp;
-  std::vector<int> weight(v.I, 1);
-  for (int i = 0; i < v.I; i++)  // (children before parents)
-    for (int c : v.children[i])
-      if (c >= v.L) weight[i] += weight[c - v.L];
-  std::vector<WalkPlan::Node> &nodes = wp.nodes;
-  std::vector<int> &inputs = wp.inputs;
-  int depth = 0;
-  auto leaf_inputs = [&](int i, int &n_in, int &in0) {
-    n_in = 0, in0 = (int)inputs.size();
-    for (int c : v.children[i])
-      if (c < v.L) inputs.push_back(c), n_in++;
-  };
-  std::function<void(int)> emit = [&](int i) {
-    std::vector<int> kids;
-    for (int c : v.children[i])
-      if (c >= v.L) kids.push_back(c - v.L);
-    std::stable_sort(kids.begin(), kids.end(), [&](int x, int y) { return weight[x] > weight[y]; });
-    for (size_t j = 0; j < kids.size(); j++) {
-      const size_t first = nodes.size();
-      if (j > 0) wp.max_depth = std::max(wp.max_depth, ++depth);
-      emit(kids[j]);
-      if (j > 0) {
-        nodes[first].flags |= 1;
-        nodes.back().flags |= 2;
-        depth--;
-      }
-    }
-    int n_in, in0;
-    leaf_inputs(i, n_in, in0);
-    nodes.push_back(WalkPlan::Node{i, n_in, in0, 0});
-  };
-  auto emit_chain = [&](const std::vector<int> &subs, bool root_leaves, std::vector<int> &range) {
-    range.push_back((int)nodes.size());
-    for (size_t j = 0; j < subs.size(); j++) {
-      const size_t first = nodes.size();
-      if (j > 0) wp.max_depth = std::max(wp.max_depth, ++depth);
-      emit(subs[j]);
-      if (j > 0) {
-        nodes[first].flags |= 1;
-        nodes.back().flags |= 2;
-        depth--;
-      }
-    }
-    int n_in = 0, in0 = (int)inputs.size();
-    if (root_leaves) leaf_inputs(v.I - 1, n_in, in0);
-    nodes.push_back(WalkPlan::Node{-1, n_in, in0, 0});
-    range.push_back((int)nodes.size());
-  };
-  std::vector<int> subs;
-  for (int c : v.children[v.I - 1])
-    if (c >= v.L) subs.push_back(c - v.L);
-  std::stable_sort(subs.begin(), subs.end(), [&](int x, int y) { return weight[x] > weight[y]; });
-  emit_chain(subs, true, wp.one_range);
-  if (subs.size() >= 2) {
-    std::vector<int> c0, c1;
-    int w0 = 0, w1 = 0;
-    for (int sb : subs)
-      if (w0 <= w1) c0.push_back(sb), w0 += weight[sb];
-      else c1.push_back(sb), w1 += weight[sb];
-    if (std::min(w0, w1) >= 2 && 4 * std::min(w0, w1) >= std::max(w0, w1)) {  // (a second chain of a node or two is not worth its workgroup)
-      emit_chain(c0, true, wp.two_range);
-      emit_chain(c1, false, wp.two_range);
-      wp.two = true;
-    }
-  }
-  return wp;
-}
-
-namespace {
-int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t>> &codes) {
-  p->rep_on = false;
-  const int env = sw::repeats();  // -1 not given, 0 never, 2 always and past the size rules, 1 always
-  if (env == 0) return 0;
-  if (p->shards.empty()) return 0;
-  if (env < 0 && sw::per_pattern_forced()) return 0;  // (the diagnostic switches that force a kernel, an instantiation or a cut are about the per-pattern kernels)
-  for (const Shard &s : p->shards)
-    if (s.T != 1) return 0;
-  if (!p->nuc && p->variant != 1 && env != 2) return 0;  // (tiny shards: the workgroup-per-tile kernel keeps the whole tree)
-  // 4 states: only on request (HYPHY_HIP_REPEATS=1 / 2).  Measured, it loses: a class row is 36 bytes gathered past the L2 per pattern
-  // and generalised leaf, where prune_nuc2_kernel computes a whole node from registers for 16 multiply-adds — gtr_32x50k 35.0 us plain
-  // against 16.5 (walks) + 26.0 (trunk of 5 nodes) compressed, gtr_32x1m 123.8 against 14.5 + 238.9
-  if (p->nuc && env < 0) return 0;
-  const int L = (int)p->L, I = (int)p->I, DP = p->DP;
-  if (I < 2) return 0;
-  const bool forced = env == 2;
-  // (before any work: a partition of a few tiles — FEL makes one per site — has nothing to compress, and the class arrays of a
-  //  very large one are host memory this analysis should not take: 4 bytes per internal node and pattern)
-  if (!forced && (p->nuc ? p->shards[0].S_pad < 8192 : p->shards[0].ntiles < 8)) return 0;  // (4 states: a small shard is one launch
-                                                                                              //  with exponentials and combine folded in)
-  {
-    double cells = 0.;
-    for (const Shard &s : p->shards) cells += (double)I * s.S_pad;
-    // (2.5e8 cells = 1 GB of transient host memory and a few seconds of hashing inside hyphy_hip_create, before it is known
-    //  whether compression pays — 128 taxa x 100 000 codons is 1.3e7; beyond the bound the partition runs plain)
-    if (cells > 2.5e8) return 0;
-  }
-  // theta: the share of the patterns below which a node's classes are worth a table.  0.3-0.4 is the flat optimum of the headline
-  // alignment (0.2: 100 us of pruning launches, 0.3: 89, 0.4: 89, 0.5: 101, 0.7: 106): above it the walks of the lower phase get long
-  // and few, below it the trunk keeps nodes that repeat heavily
-  bool theta_given = false;
-  const double theta = sw::rep_theta(0.35, &theta_given);
-  const size_t nsh = p->shards.size();
-  // ---- classes per shard ----
-  std::vector<std::vector<std::vector<int>>> cls(nsh);  // [shard][internal node][pattern]
-  std::vector<std::vector<int>> U(nsh, std::vector<int>(I, 0));
-  for (size_t k = 0; k < nsh; k++) count_classes(p->children, L, I, codes[k], (size_t)p->shards[k].S_pad, cls[k], U[k]);
-  // ---- compressed set: the same on every shard (one schedule serves them all) ----
-  std::vector<int> spads;
-  for (const Shard &s : p->shards) spads.push_back(s.S_pad);
-  std::vector<char> comp = compressed_set(p->children, L, I, U, spads, p->nuc && !theta_given ? 0.9 : theta);
-  for (size_t k = 0; k < nsh; k++)  // (only the classes of compressed nodes are read again: tables, maps, the trunk's leaf table)
-    for (int n = 0; n < I; n++)
-      if (!comp[n]) std::vector<int>().swap(cls[k][n]);
-  if (p->nuc) return rep_setup_nuc(p, codes, cls, U, comp, forced);
-  {  // worth it?  compare the edge products of the two forms on the first shard
-    double full = 0., rep = 0.;
-    for (int n = 0; n < I - 1; n++) {
-      full += p->shards[0].S_pad;
-      rep += comp[n] ? (U[0][n] + 15) / 16 * 16 : p->shards[0].S_pad;
-    }
-    const double need = sw::rep_min_gain();
-    if (!forced && rep > (1.0 - need) * full) return 0;
-  }
-  // ---- descriptors: leaves with ambiguity codes first (level 0), then the paths, inputs before the paths that read them ----
-  // rho: a path goes on into the heaviest compressed child while that child keeps at least rho of the node's classes.  0: paths
-  // run to the bottom of the subtree — no table reads a table, one launch, more products (3.4 x those of one table per node at
-  // 128 x 100 k).  Larger values trade products for hand-offs; a hand-off is a launch boundary (rep_build_items: one launch per
-  // level).  Where the lower phase is bound by its walks' lengths (a shard of a few hundred tiles: 1.5 walks per wave) rho = 0 wins
-  // (headline pruning launches 74.5 us, 79.0 at 0.3, 77.0 at 0.6, 83.2 at 2); where it is bound by throughput (128 x 100 k: 6 250
-  // tiles, eight rounds of walks) the saved products win: 663.6 us at 0, 584.2 at 0.15, 537.7 at 0.3, 549.6 at 0.45, 552.2 at 2.
-  // In between (64 taxa): 1 250 tiles 110.0 us at 0 against 119.1 at 0.3; 2 500 tiles 173.8 against 169.3 — the default changes at
-  // 2 048.  (Before the per-level launches, with the ticket protocol: 785 us at 0.6 against 726 at 0.)  HYPHY_HIP_REP_RHO overrides.
-  // (r06, row-split walks in both phases, pruning launches at 128 x 100 k: 625 us at 0, 537 at 0.15, 501 at 0.3, 489 at 0.5, 485 at 0.6,
-  //  504 at 0.7, 508 at 1 and 2: the default there moved from 0.3 to 0.5)
-  const double rho = sw::rep_rho(p->shards[0].ntiles >= 2048 ? 0.5 : 0.);
-  std::vector<int> heavy(I, -1);     // the compressed child a node's path continues into
-  std::vector<char> continued(I, 0); // the node is inside its parent's path (no table of its own)
-  std::vector<int> path_inputs(I, 0), path_len(I, 0);
-  for (int n = 0; n < I; n++) {
-    if (!comp[n]) continue;
-    int best = -1;
-    for (int c : p->children[n])
-      if (c >= L && (best < 0 || U[0][c - L] > U[0][best])) best = c - L;
-    // (a path's inputs are staged in LDS by index: long caterpillars / wide multifurcations are cut into several paths)
-    const int own_inputs = (int)p->children[n].size();
-    path_inputs[n] = own_inputs;
-    path_len[n] = 1;
-    if (best >= 0 && (double)U[0][best] >= rho * (double)U[0][n] && path_inputs[best] + own_inputs - 1 <= kRepMaxInputs - 8 &&
-        path_len[best] < 32 && own_inputs <= kRepMaxInputs / 2) {
-      heavy[n] = best;
-      continued[best] = 1;
-      path_inputs[n] = path_inputs[best] + own_inputs - 1;
-      path_len[n] = path_len[best] + 1;
-    }
-  }
-  p->rep_nodes.clear();
-  p->rep_desc_of.assign((size_t)L + I, -1);
-  for (int l = 0; l < L; l++)
-    if (p->leaf_has_ambig[l]) {
-      hyphy_hip_partition::RepNode rn;
-      rn.node = l;
-      rn.level = 0;
-      p->rep_desc_of[l] = (int)p->rep_nodes.size();
-      p->rep_nodes.push_back(rn);
-    }
-  // Side chains walked inline (latency mode, rho = 0).  A side path whose nodes read leaves only — a cherry, a short caterpillar —
-  // hanging off another path is not worth a table of its own: its table would be one more hand-off in the dependency chain of the
-  // path that reads it (publish, drain, counter, poll, gather: ~8 us with the item's fixed costs) to save a few products.  Such a
-  // chain is walked INSIDE the item of the path it hangs off: the running product is parked in the wave's LDS tile, the chain
-  // is walked from ones, and its edge product is multiplied back in (one parking slot: inlined chains do not nest).
-  const int inline_forced = sw::rep_inline();
-  const bool inline_chains = inline_forced >= 0 ? inline_forced != 0 : rho == 0.;
-  auto chain_of = [&](int top) {
-    std::vector<int> down;
-    for (int x = top; x >= 0; x = heavy[x]) down.push_back(x);
-    return std::vector<int>(down.rbegin(), down.rend());  // bottom first
-  };
-  std::vector<char> leafy(I, 0);  // a path top whose whole path reads ordinary leaves / leaf tables only
-  for (int n = 0; n < I; n++)
-    if (comp[n] && !continued[n]) {
-      bool ok = true;
-      for (int x : chain_of(n))
-        for (int c : p->children[x])
-          if (c >= L && c - L != heavy[x]) ok = false;
-      leafy[n] = ok ? 1 : 0;
-    }
-  // (first which chains go inline — the path they hang off decides, within what its LDS index list holds —, then the descriptors)
-  std::vector<char> absorbed(I, 0);
-  std::vector<std::vector<int>> inline_at(I);  // per path node: the side tops walked inline in front of it
-  if (inline_chains)
-    for (int n = 0; n < I; n++)
-      if (comp[n] && !continued[n]) {
-        int n_inputs = 0, n_entries = 0;
-        for (int x : chain_of(n)) n_inputs += (int)p->children[x].size() - (heavy[x] >= 0 ? 1 : 0), n_entries++;
-        for (int x : chain_of(n))
-          for (int c : p->children[x]) {
-            if (c < L || c - L == heavy[x] || !comp[c - L] || !leafy[c - L]) continue;
-            const std::vector<int> side = chain_of(c - L);
-            int side_inputs = 0;
-            for (int y : side) side_inputs += (int)p->children[y].size();
-            if (n_inputs + side_inputs > kRepMaxInputs - 8 || n_entries + (int)side.size() > 40) continue;
-            n_inputs += side_inputs - 1;  // (the chain's table would have been one input)
-            n_entries += (int)side.size();
-            absorbed[c - L] = 1;
-            inline_at[x].push_back(c - L);
-          }
-      }
-  for (int n = 0; n < I; n++)
-    if (comp[n] && !continued[n] && !absorbed[n]) {  // a path's top (ascending: every input's top comes first)
-      hyphy_hip_partition::RepNode rn;
-      rn.node = L + n;
-      rn.level = 0;
-      auto add_node = [&](int x, int skip_child, int flags) {
-        rn.path.push_back(L + x);
-        rn.flags.push_back(flags);
-        rn.kids.push_back(std::vector<int>());
-        rn.kid_desc.push_back(std::vector<int>());
-        for (int c : p->children[x]) {
-          if (c == skip_child) continue;  // (comes through the registers / was walked inline just before)
-          if (c >= L && absorbed[c - L]) continue;
-          rn.kids.back().push_back(c);
-          const int d = p->rep_desc_of[c];
-          rn.kid_desc.back().push_back(d);
-          if (d >= 0) rn.level = std::max(rn.level, p->rep_nodes[d].level + 1);
-        }
-      };
-      const std::vector<int> main_path = chain_of(n);
-      for (size_t k = 0; k < main_path.size(); k++) {
-        const int x = main_path[k];
-        for (int c : inline_at[x]) {
-          const std::vector<int> side = chain_of(c);
-          for (size_t j = 0; j < side.size(); j++)
-            add_node(side[j], j > 0 ? L + side[j - 1] : -1, (j == 0 ? 1 : 0) | (j + 1 == side.size() ? 2 : 0));
-        }
-        add_node(x, k > 0 ? L + main_path[k - 1] : -1, 0);
-      }
-      p->rep_desc_of[L + n] = (int)p->rep_nodes.size();
-      p->rep_nodes.push_back(rn);
-    }
-  const int ND = (int)p->rep_nodes.size();
-  if (ND == 0 || ND > 65535) return 0;
-  // ---- the trunk view ----
-  hyphy_hip_partition::View &v = p->views[1];
-  v = hyphy_hip_partition::View();
-  std::vector<int> vint(I, -1);  // view-internal index of a trunk node
-  for (int n = 0; n < I; n++)
-    if (!comp[n]) vint[n] = v.I++;
-  std::vector<int> leaf_nodes;  // node code (partition's tree) of every view leaf
-  std::vector<int> vleaf((size_t)L + I, -1);
-  for (int n = 0; n < I; n++)
-    if (!comp[n])
-      for (int c : p->children[n])
-        if (c < L || comp[c - L]) {
-          vleaf[c] = (int)leaf_nodes.size();
-          leaf_nodes.push_back(c);
-        }
-  v.L = (int)leaf_nodes.size();
-  if (v.L > 65535 || v.L < 1) return 0;
-  v.parents.assign((size_t)v.L + v.I, -1);
-  v.children.assign(v.I, std::vector<int>());
-  v.slot.assign((size_t)v.L + v.I, 0);
-  v.leaf_has_ambig.assign(v.L, 0);  // (ambiguity codes live in class tables: no leaf of the view takes the resolution-vector path)
-  for (int n = 0; n < I; n++) {
-    if (comp[n]) continue;
-    v.slot[v.L + vint[n]] = L + n;
-    const int64_t par = p->parents[L + n];
-    v.parents[v.L + vint[n]] = par < 0 ? -1 : vint[par];
-    for (int c : p->children[n]) {
-      if (c < L || comp[c - L]) {
-        v.children[vint[n]].push_back(vleaf[c]);
-        v.parents[vleaf[c]] = vint[n];
-        v.slot[vleaf[c]] = c;
-      } else {
-        v.children[vint[n]].push_back(v.L + vint[c - L]);
-      }
-    }
-    std::sort(v.children[vint[n]].begin(), v.children[vint[n]].end());
-  }
-  // ---- per shard: table rows, index maps, descriptors, the trunk's leaf table ----
-  for (size_t k = 0; k < nsh; k++) {
-    Shard &s = p->shards[k];
-    if (hipSetDevice(s.device) != hipSuccess) return fail("hipSetDevice failed");
-    const size_t SP = (size_t)s.S_pad;
-    s.rep_tabs.assign(ND, RepTable());
-    std::vector<std::vector<int>> leaf_cls(L);  // classes of the leaves that own a table
-    std::vector<int32_t> maps;
-    int64_t rows = 0;
-    std::vector<std::vector<int>> first_pat(ND);  // representative pattern of every class
-    for (int d = 0; d < ND; d++) {
-      const hyphy_hip_partition::RepNode &rn = p->rep_nodes[d];
-      RepTable &t = s.rep_tabs[d];
-      const std::vector<int> *cl;
-      std::vector<int> col(SP);
-      if (rn.node < L) {
-        for (size_t j = 0; j < SP; j++) col[j] = (int)codes[k][(size_t)rn.node * SP + j];
-        t.U = column_classes(col, leaf_cls[rn.node]);
-        cl = &leaf_cls[rn.node];
-      } else {
-        t.U = U[k][rn.node - L];
-        cl = &cls[k][rn.node - L];
-      }
-      t.rows = (t.U + 15) / 16 * 16;
-      t.row0 = rows;
-      rows += t.rows;
-      first_pat[d].assign(t.rows, -1);
-      for (size_t j = 0; j < SP; j++)
-        if (first_pat[d][(*cl)[j]] < 0) first_pat[d][(*cl)[j]] = (int)j;
-      for (int u = t.U; u < t.rows; u++) first_pat[d][u] = first_pat[d][0];  // padding rows repeat class 0
-      if (rn.node < L) {  // the code of every class
-        t.map0.push_back((int64_t)maps.size());
-        for (int u = 0; u < t.rows; u++) maps.push_back((int32_t)codes[k][(size_t)rn.node * SP + first_pat[d][u]]);
-      } else {
-        for (size_t x = 0; x < rn.path.size(); x++)
-          for (size_t j = 0; j < rn.kids[x].size(); j++) {
-            t.map0.push_back((int64_t)maps.size());
-            const int c = rn.kids[x][j], cd = rn.kid_desc[x][j];
-            for (int u = 0; u < t.rows; u++) {
-              const int pat = first_pat[d][u];  // (a class of the top node fixes the class of everything below it)
-              int32_t idx;
-              if (cd < 0) idx = (int32_t)codes[k][(size_t)c * SP + pat];        // ordinary leaf: its state
-              else if (c < L) idx = (int32_t)leaf_cls[c][pat];                  // leaf with a table: class of its code
-              else idx = (int32_t)cls[k][c - L][pat];                           // compressed child: its class
-              maps.push_back(idx);
-            }
-          }
-      }
-    }
-    s.rep_rows = rows;
-    if (maps.size() > 0x7fffffffull || rows > 0x7fffffffll) return 0;
-    std::vector<int4> desc((size_t)2 * ND);
-    for (int d = 0; d < ND; d++) {
-      const hyphy_hip_partition::RepNode &rn = p->rep_nodes[d];
-      const RepTable &t = s.rep_tabs[d];
-      const int kind = rn.node < L ? 1 : 0;
-      const int node0 = (int)desc.size();
-      desc[2 * d] = make_int4((int)t.row0, t.U, (int)rn.path.size() | (kind << 16), node0);
-      int n_in = 0;
-      for (const std::vector<int> &kk : rn.kids) n_in += (int)kk.size();
-      desc[2 * d + 1] = make_int4(t.map0.empty() ? 0 : (int)t.map0[0], t.rows / 16, rn.level, kind ? rn.node : n_in);
-      desc.resize(desc.size() + rn.path.size());
-      size_t mi = 0;
-      for (size_t x = 0; x < rn.path.size(); x++) {
-        desc[node0 + x] = make_int4(rn.path[x], (int)rn.kids[x].size(), (int)desc.size(), rn.flags[x]);
-        for (size_t j = 0; j < rn.kids[x].size(); j++, mi++) {
-          const int cd = rn.kid_desc[x][j];
-          desc.push_back(make_int4(cd >= 0 ? (int)s.rep_tabs[cd].row0 : -1, rn.kids[x][j], (int)t.map0[mi],
-                                   cd >= 0 ? (cd | ((s.rep_tabs[cd].rows / 16) << 16)) : -1));
-        }
-      }
-    }
-    // the trunk's leaf table, tile-major, and where each view leaf gathers from
-    std::vector<int16_t> ct((size_t)v.L * SP, 0);
-    std::vector<int2> lt(v.L);
-    for (int vl = 0; vl < v.L; vl++) {
-      const int c = leaf_nodes[vl], d = p->rep_desc_of[c];
-      lt[vl] = d >= 0 ? make_int2((int)s.rep_tabs[d].row0, (int)s.rep_tabs[d].row0) : make_int2(-1, c);
-      for (size_t j = 0; j < SP; j++) {
-        int val;
-        if (d < 0) val = (int)codes[k][(size_t)c * SP + j];
-        else if (c < L) val = leaf_cls[c][j];
-        else val = cls[k][c - L][j];
-        ct[((j >> 4) * (size_t)v.L + vl) * 16 + (j & 15)] = (int16_t)val;
-      }
-    }
-    const size_t sync_words = ((size_t)kRepQueues + 1 + (size_t)p->C * ND) * kRepHeadStride;  // (= rep_sync_words(p) words)
-    {  // the tables must leave the device room for everything else the partition allocates later (deposits, mixtures, site fits)
-      size_t free_b = 0, total_b = 0;
-      const size_t need_b = (size_t)p->C * rows * (DP * sizeof(double) + sizeof(int32_t)) + maps.size() * sizeof(int32_t) + ct.size() * sizeof(int16_t);
-      size_t limit = (size_t)1 << 30;
-      if (!sw::rep_max_mb(&limit) && hipMemGetInfo(&free_b, &total_b) == hipSuccess) limit = free_b / 4;  // (given: the caller's bound on the tables)
-      if (need_b > limit) return fail("class tables would take more than a quarter of the free device memory (or than HYPHY_HIP_REP_MAX_MB)");
-    }
-#define R_(ptr, bytes)                                                                  \
-  if (pool_malloc((void **)&(ptr), (bytes)) != hipSuccess) return fail("hipMalloc failed (" #ptr ")"); \
-  s.dev_bytes += (size_t)(bytes);                                                                      \
-  s.rep_bytes += (size_t)(bytes);
-    R_(s.rep_tab, (size_t)p->C * rows * DP * sizeof(double));
-    R_(s.rep_cnt, (size_t)p->C * rows * sizeof(int32_t));
-    R_(s.rep_map, std::max<size_t>(1, maps.size()) * sizeof(int32_t));
-    R_(s.rep_desc, desc.size() * sizeof(int4));
-    R_(s.rep_sync, sync_words * sizeof(int));
-    R_(s.rep_codes_tile, ct.size() * sizeof(int16_t));
-    R_(s.rep_leaf, lt.size() * sizeof(int2));
-#undef R_
-    if (sw::poison()) {
-      hipMemset(s.rep_tab, 0xff, (size_t)p->C * rows * DP * sizeof(double));
-      hipMemset(s.rep_cnt, 0xff, (size_t)p->C * rows * sizeof(int32_t));
-    }
-    hipMemset(s.rep_sync, 0, sync_words * sizeof(int));
-    hipMemcpy(s.rep_map, maps.data(), maps.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    hipMemcpy(s.rep_desc, desc.data(), desc.size() * sizeof(int4), hipMemcpyHostToDevice);
-    hipMemcpy(s.rep_codes_tile, ct.data(), ct.size() * sizeof(int16_t), hipMemcpyHostToDevice);
-    hipMemcpy(s.rep_leaf, lt.data(), lt.size() * sizeof(int2), hipMemcpyHostToDevice);
-    s.rep_leaf_host = lt;
-    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail("repeats: device initialisation failed");
-  }
-  // the trunk as one post-order walk per tile (trunk_walk_kernel): plan_trunk_walk below
-  p->rep_walk_host.clear();
-  if (!p->nuc && p->NW >= 2 && v.L <= 1024) {
-    const WalkPlan wp = plan_trunk_walk(v);
-    const std::vector<WalkPlan::Node> &nodes = wp.nodes;
-    const std::vector<int> &inputs = wp.inputs;
-    const std::vector<int> &one_range = wp.one_range, &two_range = wp.two_range;
-    const int max_depth = wp.max_depth;
-    const bool two = wp.two;
-    if (max_depth <= kWalkDepth && nodes.size() < 4096 && !inputs.empty()) {
-      for (Shard &s : p->shards) {
-        const std::vector<int2> &lt = s.rep_leaf_host;
-        // [0] header, one-chain form (1 + 1 words), two-chain form (1 + 2 words), node words, input words
-        const int form1 = 1, form2 = two ? 3 : 0, node_base = two ? 6 : 3, in_base = node_base + (int)nodes.size();
-        std::vector<int4> prog((size_t)in_base + inputs.size());
-        prog[0] = make_int4(form1, form2, max_depth, (int)prog.size());
-        prog[form1] = make_int4(1, 0, 0, 0);
-        prog[form1 + 1] = make_int4(node_base + one_range[0], one_range[1] - one_range[0], 0, 0);
-        if (two) {
-          prog[form2] = make_int4(2, 0, 0, 0);
-          const int n0 = two_range[1] - two_range[0], n1 = two_range[3] - two_range[2];
-          // (.z: wave priority — the longer chain's instructions first wherever the two share a SIMD: 59.5 against 60.4 us of pruning
-          //  launches at the headline; the same by walk length in the lower phase: no difference, not kept)
-          prog[form2 + 1] = make_int4(node_base + two_range[0], n0, n0 > n1 ? 3 : 0, 0);
-          prog[form2 + 2] = make_int4(node_base + two_range[2], n1, n1 > n0 ? 3 : 0, 0);
-        }
-        for (size_t k = 0; k < nodes.size(); k++)
-          prog[node_base + k] = make_int4(nodes[k].node < 0 ? -1 : v.slot[v.L + nodes[k].node], nodes[k].n_in, in_base + nodes[k].in0, nodes[k].flags);
-        for (size_t k = 0; k < inputs.size(); k++) prog[in_base + k] = make_int4(inputs[k], lt[inputs[k]].x, lt[inputs[k]].y, 0);
-        if (&s == &p->shards[0]) {
-          p->rep_walk_host = prog;
-          if (sw::verbose()) {
-            fprintf(stderr, "[hyphy_hip] trunk walk: %d nodes, waiting products at most %d deep", one_range[1] - one_range[0], max_depth);
-            if (two) fprintf(stderr, "; two chains per tile: %d + %d nodes", two_range[1] - two_range[0], two_range[3] - two_range[2]);
-            fprintf(stderr, "\n");
-          }
-        }
-        if (hipSetDevice(s.device) != hipSuccess) return fail("hipSetDevice failed");
-        const size_t bytes = prog.size() * sizeof(int4);
-        if (pool_malloc((void **)&s.rep_walk, bytes) != hipSuccess) return fail("hipMalloc failed (s.rep_walk)");
-        s.dev_bytes += bytes;
-        s.rep_bytes += bytes;
-        hipMemcpy(s.rep_walk, prog.data(), bytes, hipMemcpyHostToDevice);
-      }
-    }
-  }
-  p->rep_resident.assign(p->C, 0);
-  p->rep_cached_valid = false;
-  // what the trunk's schedules start from (the tuner refines them): the wave-per-tile kernel, no re-rooting
-  hyphy_hip_partition::ModeState &ms = p->saved_mode[1];
-  ms.variant = 1;
-  ms.wave_variant = 0;
-  ms.n_slots = p->n_slots_wave;
-  ms.chain_m_forced = 0;
-  ms.rr_use = false;
-  ms.kernel_forced = true;
-  ms.tuned_for = 0;
-  ms.rr_path.clear();
-  ms.rr_cands.clear();
+  const hyphy_hip_partition::View &tv = p->views[1];
+  const bool fits_lds = (size_t)tv.L * 32 + (size_t)(tv.L + tv.I) * 16 <= 24576;  // (the workgroup kernel's leaf codes and slots)
   // (r06: the trunk under the row-split workgroup kernel, prune_mfma_kernel<.., REP> — the tuner offers it on shards below eight tiles
   //  per CU; HYPHY_HIP_TRUNK_KERNEL=0 / 2 forces it — whole trunk per workgroup / on chain schedules — for tests and A/B runs)
-  {
-    const int kv = sw::trunk_kernel();  // (-1: not given)
-    const hyphy_hip_partition::View &tv = p->views[1];
-    if ((kv == 0 || kv == 2) && p->NW == 4 && !p->nuc && (size_t)tv.L * 32 + (size_t)(tv.L + tv.I) * 16 <= 24576) {
-      ms.variant = kv;
-      ms.n_slots = lds_slots(1);
-    }
+  if ((opt.trunk_kernel == 0 || opt.trunk_kernel == 2) && p->NW == 4 && fits_lds) {
+    ms.variant = opt.trunk_kernel;
+    ms.n_slots = lds_slots(1);
   }
-  ms.trunk_walk = false;
-  {
-    // HYPHY_HIP_TRUNK_WALK=1: the walk without asking the tuner (tests, A/B runs), at every NW it has a plan for.  No tuner at all
-    // (HYPHY_HIP_TUNE=0): the walk at NW = 4 — it is the faster form wherever the static rule turns compression on, and with the
-    // one-workgroup-per-tile kernel behind it for the other passes nothing in this mode depends on an order of arrival: the same
-    // bits on every run (tested).  (The chain schedules of the wave and row-split trunks do join by order of arrival, but form every
-    // node in schedule order — schedule.hip, prune.hip — so their bits do not depend on it either.)  (NW 2 / 3: the walk's speed is unmeasured; without the switch only the tuner offers it.)
-    const int tw = sw::trunk_walk_at_create();
-    const bool tune_off = !sw::tune();
-    const hyphy_hip_partition::View &tv = p->views[1];
-    if ((tw >= 0 ? tw == 1 : tune_off && p->NW == 4) && !p->rep_walk_host.empty() && (size_t)tv.L * 32 + (size_t)(tv.L + tv.I) * 16 <= 24576) {
-      ms.trunk_walk = true;
-      ms.variant = trunk_walk_backing(p);
-      ms.n_slots = ms.variant == 1 ? p->n_slots_wave : lds_slots(1);
-    }
+  // HYPHY_HIP_TRUNK_WALK=1: the walk without asking the tuner (tests, A/B runs), at every NW it has a plan for.  No tuner at all
+  // (HYPHY_HIP_TUNE=0): the walk at NW = 4 — it is the faster form wherever the static rule turns compression on, and with the
+  // one-workgroup-per-tile kernel behind it for the other passes nothing in this mode depends on an order of arrival: the same
+  // bits on every run (tested).  (The chain schedules of the wave and row-split trunks do join by order of arrival, but form every
+  // node in schedule order — schedule.hip, prune.hip — so their bits do not depend on it either.)  (NW 2 / 3: the walk's speed is
+  // unmeasured; without the switch only the tuner offers it.)
+  if ((opt.trunk_walk >= 0 ? opt.trunk_walk == 1 : !opt.tune && p->NW == 4) && !p->rep_walk_host.empty() && fits_lds) {
+    ms.trunk_walk = true;
+    ms.variant = trunk_walk_backing(p);
+    ms.n_slots = ms.variant == 1 ? opt.n_slots_wave : lds_slots(1);
   }
-  if (p->C == 1 && !p->nuc) {  // the trunk's own height-minimising roots (the tuner's third stage times the re-rooted schedules)
+  if (p->C == 1) {  // the trunk's own height-minimising roots (the tuner's third stage times the re-rooted schedules)
     const int mode0 = p->mode;
     std::vector<int> path0;
     std::vector<std::vector<int>> cands0;
@@ -1896,20 +1209,67 @@ int rep_setup_impl(hyphy_hip_partition *p, const std::vector<std::vector<int16_t
     p->rr_path.swap(path0);
     p->rr_cands.swap(cands0);
   }
-  p->rep_on = true;
-  if (sw::verbose()) {
-    long long rows = 0, lower = 0;
-    for (int d = 0; d < ND; d++) {
-      rows += p->shards[0].rep_tabs[d].rows;
-      lower += (long long)p->shards[0].rep_tabs[d].rows * std::max<size_t>(1, p->rep_nodes[d].path.size());
-    }
-    fprintf(stderr, "[hyphy_hip] subtree repeats: theta %.2f, rho %.2f, %d class tables (%lld rows on shard 0), trunk of %d internal nodes over %d leaves; "
-                    "edge products per pass %lld + %lld (every pattern at every node: %lld)\n",
-            theta, rho, ND, rows, v.I, v.L, lower, (long long)(v.I - 1) * p->shards[0].S_pad, (long long)(I - 1) * p->shards[0].S_pad);
+}
+
+void rep_report(const hyphy_hip_partition *p, const RepPlan &plan) {
+  const hyphy_hip_partition::View &v = p->views[1];
+  const long long SP0 = p->shards[0].S_pad, every = (long long)(p->I - 1) * SP0;
+  long long rows = 0, lower = 0;
+  for (size_t d = 0; d < p->rep_nodes.size(); d++) {
+    rows += p->shards[0].rep_tabs[d].rows;
+    lower += (long long)p->shards[0].rep_tabs[d].rows * std::max<size_t>(1, p->rep_nodes[d].path.size());
   }
+  if (p->nuc) {
+    sw::note("subtree repeats (4 states): %d compressed subtrees walked per class (%lld classes on shard 0, %lld node visits), trunk of %d "
+             "internal nodes over %d leaves (every pattern at every node: %lld)\n",
+             (int)p->rep_nodes.size(), rows, lower, v.I, v.L, every);
+    return;
+  }
+  if (plan.has_walk) {
+    const WalkPlan &wp = plan.walk;
+    std::string two;
+    if (wp.two) two = "; two chains per tile: " + std::to_string(wp.two_range[1] - wp.two_range[0]) + " + " + std::to_string(wp.two_range[3] - wp.two_range[2]) + " nodes";
+    sw::note("trunk walk: %d nodes, waiting products at most %d deep%s\n", wp.one_range[1] - wp.one_range[0], wp.max_depth, two.c_str());
+  }
+  sw::note("subtree repeats: theta %.2f, rho %.2f, %d class tables (%lld rows on shard 0), trunk of %d internal nodes over %d leaves; "
+           "edge products per pass %lld + %lld (every pattern at every node: %lld)\n",
+           plan.theta, plan.rho, (int)p->rep_nodes.size(), rows, v.I, v.L, lower, (long long)(v.I - 1) * SP0, every);
+}
+
+}  // namespace
+
+// Decide the compressed set, build views[1] and every shard's tables.  `codes[k]`: shard k's leaf table [L][S_pad] in device pattern
+// order (padding patterns included: they are patterns like any other).  Subtree repeats are an optimisation: when the plan declines
+// (it says why), or whatever goes wrong while they are set up (tables that do not fit the device, a failed copy), the partition
+// evaluates every node at every pattern — hyphy_hip_create never fails because of them.
+int rep_setup(hyphy_hip_partition *p, const std::vector<std::vector<int16_t>> &codes) {
+  auto plain = [&](const std::string &why) {
+    sw::note("subtree repeats not used (%s): plain evaluation\n", why.c_str());
+    rep_release(p);
+    (void)hipGetLastError();
+    g_last_error.clear();
+    return 0;
+  };
+  p->rep_on = false;
+  const RepOptions opt = rep_options(p);
+  const RepPlanInput in = rep_plan_input(p);
+  RepPlan plan = plan_repeat_set(in, opt, codes);
+  if (!plan.declined.empty()) return plain(plan.declined);
+  p->rep_walk_host.clear();
+  for (size_t k = 0; k < p->shards.size(); k++) {  // (one shard at a time: the host copies of a large shard's maps are hundreds of MB)
+    const RepShardTables t = plan_shard_tables(in, plan, k, codes[k]);
+    if (!t.declined.empty()) return plain(t.declined);
+    const std::vector<int4> walk_prog = plan.has_walk ? encode_walk_program(plan.walk, plan.view, t.lt) : std::vector<int4>();
+    if (k == 0) p->rep_walk_host = walk_prog;
+    if (rep_upload_shard(p, p->shards[k], t, walk_prog) != 0) return plain(g_last_error);
+  }
+  p->rep_nodes.swap(plan.rep_nodes);
+  p->rep_desc_of.swap(plan.rep_desc_of);
+  p->views[1] = plan.view;
+  seed_trunk_mode(p, opt);
+  rep_report(p, plan);
   return 0;
 }
-}  // namespace
 
 // The view in use: saves what the tuner decided for the view that is left and restores the other's.
 void switch_mode(hyphy_hip_partition *p, int mode) {
@@ -2551,65 +1911,3 @@ int rep_decide(hyphy_hip_partition *p, int cat, int n_classes) {
 }
 
 }  // namespace hyhip
-
-using namespace hyhip;
-
-extern "C" {
-
-/* Host-only (no device needed): what hyphy_hip_create decides about subtree repeats from the topology and the leaf table alone.
- * classes_out[I]: classes of every internal node over the S patterns as given (no padding, one shard); compressed_out[I]: 1 where
- * the node's subtree is evaluated per class (theta <= 0: the library's default).  Returns the edge products a full pass executes
- * with one table per compressed node (sum of their classes + S per trunk edge), < 0 on bad arguments. */
-/* Host-only: the walk program of a trunk given as a tree over generalised leaves (node codes 0 .. L - 1: leaves, L + i: internal node
- * i, children before parents, the root last; parents[c] = node code of c's parent, the root's entry is ignored).
- * out: [nodes, inputs, stack depth, two chains?, first / end node of the one-chain form, of chain 0, of chain 1], then per node
- * (internal index or -1, leaf children, first input, flags), then the inputs (leaf codes).  Returns the words written, < 0: cap too small. */
-int64_t hyphy_hip_plan_trunk_walk(int64_t L, int64_t I, const int64_t *parents, int64_t *out, int64_t cap) {
-  if (L < 1 || I < 1 || !parents || !out) return -1;
-  hyphy_hip_partition::View v;
-  v.L = (int)L, v.I = (int)I;
-  v.children.assign((size_t)I, std::vector<int>());
-  for (int64_t c = 0; c < L + I - 1; c++) {
-    if (parents[c] < L || parents[c] >= L + I) return -1;
-    v.children[(size_t)(parents[c] - L)].push_back((int)c);
-  }
-  const hyhip::WalkPlan wp = hyhip::plan_trunk_walk(v);
-  const int64_t need = 10 + 4 * (int64_t)wp.nodes.size() + (int64_t)wp.inputs.size();
-  if (need > cap) return -need;
-  int64_t *o = out;
-  *o++ = (int64_t)wp.nodes.size(), *o++ = (int64_t)wp.inputs.size(), *o++ = wp.max_depth, *o++ = wp.two ? 1 : 0;
-  *o++ = wp.one_range[0], *o++ = wp.one_range[1];
-  for (int k = 0; k < 4; k++) *o++ = wp.two ? wp.two_range[(size_t)k] : 0;
-  for (const auto &n : wp.nodes) *o++ = n.node, *o++ = n.n_in, *o++ = n.in0, *o++ = n.flags;
-  for (int x : wp.inputs) *o++ = x;
-  return need;
-}
-
-int64_t hyphy_hip_plan_repeats(int64_t L, int64_t I, const int64_t *flat_parents, int64_t S, const int64_t *leaf_codes, double theta,
-                               int64_t *classes_out, int64_t *compressed_out) {
-  if (L < 2 || I < 1 || S < 1 || !flat_parents || !leaf_codes) return -1;
-  std::vector<std::vector<int>> children((size_t)I);
-  for (int64_t n = 0; n < L + I - 1; n++) {
-    const int64_t par = flat_parents[n];
-    if (par < 0 || par >= I || (n >= L && par <= n - L)) return -1;
-    children[(size_t)par].push_back((int)n);
-  }
-  std::vector<int16_t> codes((size_t)L * S);
-  for (int64_t k = 0; k < L * S; k++) {
-    if (leaf_codes[k] > 32767 || leaf_codes[k] < -32768) return -1;
-    codes[(size_t)k] = (int16_t)leaf_codes[k];
-  }
-  std::vector<std::vector<int>> cls;
-  std::vector<std::vector<int>> U(1);
-  count_classes(children, (int)L, (int)I, codes, (size_t)S, cls, U[0]);
-  const std::vector<char> comp = compressed_set(children, (int)L, (int)I, U, std::vector<int>(1, (int)S), theta > 0. ? theta : 0.35);
-  int64_t work = 0;
-  for (int64_t n = 0; n < I; n++) {
-    if (classes_out) classes_out[n] = U[0][(size_t)n];
-    if (compressed_out) compressed_out[n] = comp[(size_t)n];
-    if (n < I - 1) work += comp[(size_t)n] ? U[0][(size_t)n] : S;
-  }
-  return work;
-}
-
-}  // extern "C"

@@ -24,7 +24,7 @@ EXPORTS = [
     "hyphy_hip_evaluate_built", "hyphy_hip_evaluate_built_sites", "hyphy_hip_update_q_templates", "hyphy_hip_evaluate_categories_built", "hyphy_hip_evaluate_categories_built_sites", "hyphy_hip_prune_timings", "hyphy_hip_prune_launches",
     "hyphy_hip_prune_kernel_name", "hyphy_hip_last_prune_form", "hyphy_hip_last_reduce_form", "hyphy_hip_branch_cache_build", "hyphy_hip_branch_cache_evaluate",
     "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_joint_ancestral", "hyphy_hip_sample_ancestral", "hyphy_hip_sample_uniforms", "hyphy_hip_simulate", "hyphy_hip_simulate_uniforms", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
-    "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_plan_switches", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
+    "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_repeat_layout", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_plan_switches", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
     "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error", "hyphy_hip_last_expm_kernel",
     "hyphy_hip_version",
 ]
@@ -169,6 +169,9 @@ def load():
     lib.hyphy_hip_plan_trunk_walk.argtypes = [C.c_int64, C.c_int64, lp, lp, C.c_int64]
     lib.hyphy_hip_plan_repeats.restype = C.c_int64
     lib.hyphy_hip_plan_repeats.argtypes = [C.c_int64, C.c_int64, lp, C.c_int64, lp, C.c_double, lp, lp]
+    lib.hyphy_hip_plan_repeat_layout.restype = C.c_int64
+    lib.hyphy_hip_plan_repeat_layout.argtypes = [C.c_int64, C.c_int64, lp, C.c_int64, C.c_int64, C.c_int64, lp, lp, C.c_int64, C.c_double, C.c_double,
+                                                 C.c_double, C.c_int64, C.c_int64, lp, C.c_int64, C.c_char_p, C.c_int64]
     lib.hyphy_hip_repeat_stats.restype = C.c_int
     lib.hyphy_hip_repeat_stats.argtypes = [vp, lp]
     lib.hyphy_hip_comm_init_host.restype = C.c_int
@@ -254,6 +257,62 @@ def plan_repeats(flat_parents, L: int, leaf_codes, theta: float = 0.0):
     if work < 0:
         raise HipError("plan_repeats: bad arguments")
     return cl, cp.astype(bool), int(work)
+
+
+def plan_repeat_layout(flat_parents, L: int, shard_codes, D: int, n_classes: int = 1, mode: int = -1, theta: float = 0.0, rho: float = -1.0,
+                       min_gain: float = -1.0, inline_chains: int = -1, variant: int = 1) -> dict:
+    """Host-only: what hyphy_hip_create would upload for the class-compressed form (include/hyphy_hip.h:
+    hyphy_hip_plan_repeat_layout).  ``shard_codes``: one [L][S_pad] array per shard, padded as for the device.  Returns
+    ``{"declined": reason}`` when the plan declines, else a dict with ``compressed``, ``rep_desc_of``, ``descriptors`` (dicts: node,
+    level, path, flags, kids, kid_desc), ``view`` (L, I, parents, slot, leaf_has_ambig, leaf_nodes, children) and ``shards`` (dicts:
+    rows, tables [(U, rows, row0, map0)], and the uploaded words maps, desc [n][4], ct, lt [n][2], walk [n][4])."""
+    lib = load()
+    fp = np.ascontiguousarray(flat_parents, dtype=np.int64)
+    I = len(fp) - int(L)
+    sp = np.array([np.shape(c)[1] for c in shard_codes], dtype=np.int64)
+    lc = np.concatenate([np.ascontiguousarray(c, dtype=np.int64).ravel() for c in shard_codes])
+    reason = C.create_string_buffer(256)
+    args = (int(L), I, _l(fp), int(D), int(n_classes), len(sp), _l(sp), _l(lc), int(mode), float(theta), float(rho), float(min_gain),
+            int(inline_chains), int(variant))
+    n = lib.hyphy_hip_plan_repeat_layout(*args, None, 0, reason, len(reason))
+    if n == 0:
+        return {"declined": reason.value.decode()}
+    if n == -1:
+        raise HipError("plan_repeat_layout: bad arguments")
+    out = np.zeros(-n, dtype=np.int64)
+    if lib.hyphy_hip_plan_repeat_layout(*args, _l(out), len(out), reason, len(reason)) != -n:
+        raise HipError("plan_repeat_layout: the layout changed size between two calls")
+    pos = [0]
+
+    def take(k):
+        pos[0] += k
+        return out[pos[0] - k: pos[0]]
+
+    def lst(width=1):
+        k = int(take(1)[0])
+        a = take(k * width).copy()
+        return a.reshape(k, width) if width > 1 else a
+
+    ND, vL, vI, nsh, _walk = (int(x) for x in take(5))
+    res = {"compressed": lst().astype(bool), "rep_desc_of": lst(), "descriptors": [], "shards": []}
+    for _ in range(ND):
+        node, level = (int(x) for x in take(2))
+        d = {"node": node, "level": level, "path": lst(), "flags": lst(), "kids": [], "kid_desc": []}
+        for _x in range(len(d["path"])):
+            d["kids"].append(lst())
+            d["kid_desc"].append(lst())
+        res["descriptors"].append(d)
+    res["view"] = {"L": vL, "I": vI, "parents": lst(), "slot": lst(), "leaf_has_ambig": lst(), "leaf_nodes": lst()}
+    res["view"]["children"] = [lst() for _ in range(vI)]
+    for _ in range(nsh):
+        sh = {"rows": int(take(1)[0]), "tables": []}
+        for _d in range(ND):
+            U, rows, row0 = (int(x) for x in take(3))
+            sh["tables"].append((U, rows, row0, lst()))
+        sh["maps"], sh["desc"], sh["ct"], sh["lt"], sh["walk"] = lst(), lst(4), lst(), lst(2), lst(4)
+        res["shards"].append(sh)
+    assert pos[0] == len(out)
+    return res
 
 
 def plan_trunk_walk(parents, L: int):

@@ -695,6 +695,19 @@ int hyphy_hip_repeat_stats(const hyphy_hip_partition *p, int64_t out[8]);
  * (< 0: -words needed).  Restates nothing of the reference: it is the order in which src/core/tree_evaluator.cpp:3556-4171 visits the
  * nodes above the class tables, cut for one or two workgroups per tile. */
 int64_t hyphy_hip_plan_trunk_walk(int64_t L, int64_t I, const int64_t *parents, int64_t *out, int64_t cap);
+/* Host-only (no device, reads no environment): everything hyphy_hip_create would put on the device for the class-compressed form of
+ * a partition of D states (4: the stack-walk form) and C rate classes — the plan of csrc/repeats_plan.h with its switches as
+ * arguments.  leaf_codes: shard after shard, [L][S_pad[k]] as padded for the device (a multiple of 16 patterns unless D = 4; codes
+ * < 0: ambiguity codes).  mode: HYPHY_HIP_REPEATS (-1 not given, 1, 2); theta <= 0, rho < 0, min_gain < 0, inline_chains < 0: not
+ * given; variant: the pruning kernel the partition starts with (1: wave per tile).
+ * Returns 0 when the plan declines (`reason` says why), -1 on bad arguments, -words needed when cap is too small, else the words
+ * written.  out: [descriptors ND, view L, view I, shards, walk?]; then lists, each as its length followed by its entries:
+ * compressed[I], rep_desc_of[L + I]; per descriptor node, level, path, flags and per path node kids, kid_desc; the view's parents,
+ * slot, leaf_has_ambig, leaf_nodes and per view-internal node its children; per shard: rows, per table (U, rows, row0, map0 list),
+ * then the words exactly as uploaded: maps, desc (x y z w per entry), ct, lt (x y), the trunk walk's program (x y z w; empty: none). */
+int64_t hyphy_hip_plan_repeat_layout(int64_t L, int64_t I, const int64_t *flat_parents, int64_t D, int64_t C, int64_t n_shards,
+                                     const int64_t *S_pad, const int64_t *leaf_codes, int64_t mode, double theta, double rho, double min_gain,
+                                     int64_t inline_chains, int64_t variant, int64_t *out, int64_t cap, char *reason, int64_t reason_cap);
 
 /* 4 states: schedules as run-time generated straight-line kernels (nucgen.hip; replaces the interpretation of the reference's
  * 4-state loop, src/core/tree_evaluator.cpp:2253-2273, 3556-4171, entry by entry).  A 4-state partition whose full-pass schedule

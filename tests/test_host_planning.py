@@ -340,3 +340,308 @@ def test_trunk_walk_program_of_a_balanced_trunk_nests_its_waiting_products():
     assert [e - f - 1 for f, e in plan["two"]] == [7, 7]
     first, end = plan["one"]
     assert sum(1 for _, _, _, fl in plan["nodes"][first:end] if fl & 1) == sum(1 for _, _, _, fl in plan["nodes"][first:end] if fl & 2) == 7
+
+
+# ---- the class-compressed form below the trunk: hyphy_hip_plan_repeat_layout run by a numpy interpreter --------------------------
+
+def _node(name, *kids):
+    n = tree.Node(name=name, children=list(kids))
+    for c in kids:
+        c.parent = n
+    return n
+
+
+def _leaves(prefix, k):
+    return [tree.Node(name=f"{prefix}{j}") for j in range(k)]
+
+
+def _pad(codes, D):
+    """Patterns padded as hyphy_hip_create pads a shard: state 0, to whole tiles of 16 (4 states: to 512)."""
+    q = 512 if D == 4 else 16
+    out = np.zeros((codes.shape[0], (codes.shape[1] + q - 1) // q * q), dtype=np.int64)
+    out[:, :codes.shape[1]] = codes
+    return out
+
+
+def _layout_case(root, D, sites, seed, cuts=(), ambig_leaves=(), p_change=0.03, **opts):
+    """(flat tree, padded leaf codes per shard, resolution vectors, layout): an alignment evolved down ``root`` with few changes,
+    ambiguity codes sprinkled over ``ambig_leaves`` (names), the patterns cut into shards at ``cuts``, admission forced."""
+    from hyphy_amd import data
+    syn = data.evolve(0, sites, 3 if D > 5 else 1, seed=seed, p_change=p_change, tree=root)
+    flat, codes = syn.flat, np.array(syn.states, dtype=np.int64) % D
+    rng = np.random.default_rng(seed + 1000)
+    for name in ambig_leaves:
+        leaf = flat.leaf_names.index(name)
+        codes[leaf, rng.choice(sites, size=max(3, sites // 10), replace=False)] = -rng.integers(1, 3, size=max(3, sites // 10))
+    shards = [_pad(c, D) for c in np.split(codes, list(cuts), axis=1)]
+    ambig = (rng.random((2, D)) < 0.5).astype(np.float64)
+    ambig[:, 0] = 1.0
+    opts.setdefault("mode", 2)
+    opts.setdefault("theta", 0.9)
+    return flat, shards, ambig, hip.plan_repeat_layout(flat.flat_parents, flat.L, shards, D, **opts)
+
+
+def _leaf_vectors(code, ambig, D):
+    """[n, D]: the unit vector of a state, the resolution vector of an ambiguity code (< 0)."""
+    code = np.asarray(code)
+    out = np.zeros((len(code), D))
+    ok = code >= 0
+    assert np.all(code[ok] < D) and np.all(-code[~ok] - 1 < len(ambig))
+    out[np.nonzero(ok)[0], code[ok]] = 1.0
+    out[~ok] = ambig[-code[~ok] - 1]
+    return out
+
+
+def _run_tables_mfma(lay, sh, P, ambig, D, L):
+    """The lower phase as class_table_kernel walks it: every descriptor in order, per table row the path bottom-up."""
+    desc, maps = sh["desc"], sh["maps"]
+    tab = np.full((sh["rows"], D), np.nan)
+    rows_of = [t[1] for t in sh["tables"]]
+    for d, rn in enumerate(lay["descriptors"]):
+        (row0, U, z, node0), (map0, tiles, level, w) = desc[2 * d], desc[2 * d + 1]
+        n_path, kind, rows = z & 0xffff, z >> 16, tiles * 16
+        assert (U, rows, row0) == sh["tables"][d][:3] and level == rn["level"] and n_path == len(rn["path"])
+        if kind == 1:                                   # a leaf with ambiguity codes: one row per distinct code
+            assert w == rn["node"] < L and n_path == 0
+            code = maps[map0:map0 + rows]
+            assert np.all(code[U:] == code[0])          # padding rows repeat class 0
+            tab[row0:row0 + rows] = _leaf_vectors(code, ambig, D) @ P[w].T
+            continue
+        acc, parked, e = np.ones((rows, D)), None, 0
+        for k in range(n_path):
+            slot, n_in, in0, flags = desc[node0 + k]
+            assert slot == rn["path"][k] and flags == rn["flags"][k] and n_in == len(rn["kids"][k])
+            if flags & 1:
+                assert parked is None
+                acc, parked = np.ones((rows, D)), acc
+            for j in range(n_in):
+                x, y, m0, wd = desc[in0 + j]
+                assert m0 == map0 + e * rows and y == rn["kids"][k][j]
+                idx = maps[m0:m0 + rows]
+                assert np.all(idx[U:] == idx[0])
+                if x >= 0:                               # a table: its descriptor comes earlier, on a lower level
+                    cd = wd & 0xffff
+                    assert cd == rn["kid_desc"][k][j] < d and lay["descriptors"][cd]["level"] < level
+                    assert (wd >> 16) * 16 == rows_of[cd] and x == sh["tables"][cd][2]
+                    assert np.all((0 <= idx) & (idx < rows_of[cd]))
+                    acc = acc * tab[x + idx]
+                else:                                    # an ordinary leaf: the column of its matrix
+                    assert wd == -1 and rn["kid_desc"][k][j] == -1 and y < L and np.all((0 <= idx) & (idx < D))
+                    acc = acc * P[y].T[idx]
+                e += 1
+            acc = acc @ P[slot].T
+            if flags & 2:
+                acc, parked = acc * parked, None
+        assert parked is None and e == w
+        tab[row0:row0 + rows] = acc
+    return tab
+
+
+def _run_tables_nuc(lay, sh, P, ambig, D, L):
+    """... as class_table_nuc_kernel walks it: a post-order over the whole subtree, finished children on a stack."""
+    desc, maps = sh["desc"], sh["maps"]
+    tab = np.full((sh["rows"], D), np.nan)
+    for d, rn in enumerate(lay["descriptors"]):
+        (row0, U, n_path, node0), (map0, rows, _, n_in_all) = desc[2 * d], desc[2 * d + 1]
+        assert (U, rows, row0) == sh["tables"][d][:3] and rn["level"] == 0
+        stack, e, E = [], 0, None
+        for k in range(n_path):
+            slot, n_in, in0, pops = desc[node0 + k]
+            acc = np.ones((rows, D))
+            for j in range(n_in):
+                x, leaf, _, wd = desc[in0 + j]
+                code = maps[map0 + e * rows: map0 + (e + 1) * rows]
+                assert x == -1 and wd == -1 and leaf < L and np.all(code[U:] == code[0])
+                acc = acc * (_leaf_vectors(code, ambig, D) @ P[leaf].T)
+                e += 1
+            for _j in range(pops):
+                acc = acc * stack.pop()
+            E = acc @ P[slot].T
+            if k + 1 < n_path:
+                stack.append(E)
+        assert not stack and e == n_in_all and len(stack) <= 8
+        tab[row0:row0 + rows] = E
+    return tab
+
+
+def _run_trunk(lay, sh, tab, P, ambig, D, SP, nuc):
+    """The root's conditionals per pattern over the view, generalised leaves read through ``ct`` / ``lt``; and the same through the
+    encoded walk program where there is one."""
+    v, ct, lt = lay["view"], sh["ct"], sh["lt"]
+    vL, vI = v["L"], v["I"]
+    j = np.arange(SP)
+
+    def leaf(vl, x, y):
+        c = ct[vl * SP + j] if nuc else ct[((j >> 4) * vL + vl) * 16 + (j & 15)]
+        if x >= 0:
+            d = int(lay["rep_desc_of"][v["leaf_nodes"][vl]])
+            assert x == sh["tables"][d][2] and np.all((0 <= c) & (c < sh["tables"][d][0]))
+            return tab[x + c]
+        assert y == v["leaf_nodes"][vl]
+        return _leaf_vectors(c, ambig, D) @ P[y].T
+
+    cond = [None] * vI
+    for i in range(vI):
+        acc = np.ones((SP, D))
+        assert list(v["children"][i]) == sorted(v["children"][i])
+        for c in v["children"][i]:
+            acc = acc * (leaf(c, *lt[c]) if c < vL else cond[c - vL] @ P[v["slot"][c]].T)
+        cond[i] = acc
+    walk = sh["walk"]
+    if len(walk):
+        form1, form2, depth, words = walk[0]
+        assert words == len(walk) and depth <= 3
+
+        def chain(first, n):
+            acc, stack = np.ones((SP, D)), []
+            for slot, n_in, in0, flags in walk[first:first + n]:
+                if flags & 1:
+                    stack.append(acc)
+                    acc = np.ones((SP, D))
+                for vl, x, y, _ in walk[in0:in0 + n_in]:
+                    assert (x, y) == tuple(lt[vl])
+                    acc = acc * leaf(vl, x, y)
+                if slot < 0:
+                    assert not stack
+                    return acc
+                acc = acc @ P[slot].T
+                if flags & 2:
+                    acc = acc * stack.pop()
+            raise AssertionError("a chain must end at the root")
+
+        assert walk[form1][0] == 1
+        assert np.allclose(chain(*walk[form1 + 1][:2]), cond[vI - 1], rtol=1e-12, atol=0)
+        if form2:
+            assert walk[form2][0] == 2
+            assert np.allclose(chain(*walk[form2 + 1][:2]) * chain(*walk[form2 + 2][:2]), cond[vI - 1], rtol=1e-12, atol=0)
+    return cond[vI - 1]
+
+
+def _check_layout(flat, shards, ambig, lay, D, seed=0):
+    """Runs the layout of every shard and compares the root's conditionals per pattern with the plain recursion; returns the layout."""
+    assert "declined" not in lay, lay
+    L, fp = flat.L, np.asarray(flat.flat_parents)
+    I = len(fp) - L
+    nuc = D == 4
+    rng = np.random.default_rng(seed)
+    P = 0.9 * np.eye(D) + 0.1 * rng.random((L + I - 1, D, D))       # one matrix per branch: short branches, nothing underflows
+    comp, v = lay["compressed"], lay["view"]
+    assert comp.any() and not comp[I - 1]
+    # the view: its slots are exactly the trunk nodes and the generalised leaves (ordinary leaves below the trunk, compressed roots)
+    trunk = [L + n for n in range(I) if not comp[n]]
+    gen = [c for c in range(L + I - 1) if not comp[fp[c]] and (c < L or comp[c - L])]
+    assert sorted(v["slot"]) == sorted(trunk + gen) and len(set(v["slot"])) == len(v["slot"])
+    assert list(v["slot"][:v["L"]]) == list(v["leaf_nodes"]) and v["I"] == len(trunk)
+    children = [[] for _ in range(I)]
+    for c, p in enumerate(fp[:-1]):
+        children[p].append(c)
+    for k, (codes, sh) in enumerate(zip(shards, lay["shards"])):
+        SP = codes.shape[1]
+        cond = [None] * I
+        for n in range(I):
+            acc = np.ones((SP, D))
+            for c in children[n]:
+                acc = acc * ((_leaf_vectors(codes[c], ambig, D) if c < L else cond[c - L]) @ P[c].T)
+            cond[n] = acc
+        tab = (_run_tables_nuc if nuc else _run_tables_mfma)(lay, sh, P, ambig, D, L)
+        assert not np.isnan(tab).any()
+        got = _run_trunk(lay, sh, tab, P, ambig, D, SP, nuc)
+        assert np.allclose(got, cond[I - 1], rtol=1e-12, atol=0), (k, np.max(np.abs(got / cond[I - 1] - 1)))
+    return lay
+
+
+def _paths(lay):
+    return [d for d in lay["descriptors"] if len(d["path"])]
+
+
+@pytest.mark.parametrize("D,taxa,sites", [(5, 12, 64), (61, 24, 200), (20, 40, 400)])
+def test_repeat_layout_inlines_side_chains_at_rho_0(D, taxa, sites):
+    """rho = 0: paths run to the bottom, side chains of leaves are walked inline (flags 1 and 2)."""
+    root = tree.random_tree(taxa, np.random.default_rng(taxa))
+    lay = _check_layout(*_layout_case(root, D, sites, seed=taxa, rho=0.0), D)
+    flags = np.concatenate([d["flags"] for d in _paths(lay)])
+    assert (flags & 1).any() and (flags & 2).any()
+    assert (len(lay["shards"][0]["walk"]) > 0) == (D > 16)             # (the trunk walk: two row blocks and more)
+
+
+@pytest.mark.parametrize("D,taxa,sites", [(5, 16, 96), (61, 32, 256)])
+def test_repeat_layout_tables_read_tables_at_rho_half(D, taxa, sites):
+    root = tree.random_tree(taxa, np.random.default_rng(taxa + 1))
+    lay = _check_layout(*_layout_case(root, D, sites, seed=taxa, rho=0.5), D)
+    assert max(d["level"] for d in lay["descriptors"]) >= 1
+    assert not any(f for d in _paths(lay) for f in d["flags"])          # (nothing is inlined unless rho is 0)
+
+
+@pytest.mark.parametrize("D", [5, 61])
+def test_repeat_layout_leaves_with_ambiguity_codes_get_tables_of_their_own(D):
+    a = _leaves("a", 2)
+    c = _leaves("c", 3)
+    t = _leaves("t", 3)
+    root = _node("root", _node("n3", _node("n2", _node("n1", a[0], a[1]), c[0]), c[1]), _node("n4", t[0], t[1]), t[2], c[2])
+    flat, shards, ambig, lay = _layout_case(root, D, 128, seed=7, ambig_leaves=("a0", "t2"), rho=0.0)
+    _check_layout(flat, shards, ambig, lay, D)
+    fp, names = flat.flat_parents, flat.leaf_names
+    la, lt = names.index("a0"), names.index("t2")
+    assert lay["compressed"][fp[la]] and not lay["compressed"][fp[lt]]      # one below a compressed node, one below the trunk
+    for leaf in (la, lt):
+        d = lay["descriptors"][lay["rep_desc_of"][leaf]]
+        assert d["node"] == leaf and len(d["path"]) == 0 and d["level"] == 0
+    assert lt in lay["view"]["leaf_nodes"] and not lay["view"]["leaf_has_ambig"].any()
+
+
+def test_repeat_layout_compresses_a_multifurcation_but_not_a_star_beyond_the_input_list():
+    wide = _node("wide", *_leaves("w", 57))                                 # more children than kRepMaxInputs - 8 = 56
+    four = _node("four", *_leaves("f", 4))
+    root = _node("root", _node("up", wide, _node("pair", *_leaves("p", 2))), four, *_leaves("r", 2))
+    flat, shards, ambig, lay = _layout_case(root, 5, 64, seed=3, p_change=0.002, rho=0.0)
+    _check_layout(flat, shards, ambig, lay, 5)
+    fp, names = flat.flat_parents, flat.leaf_names
+    n_wide, n_four = fp[names.index("w0")], fp[names.index("f0")]
+    classes, _, _ = hip.plan_repeats(fp, flat.L, shards[0], 0.9)
+    assert classes[n_wide] <= 0.9 * shards[0].shape[1] and not lay["compressed"][n_wide]
+    assert lay["compressed"][n_four] and sum(1 for p in fp[:flat.L] if p == n_four) == 4
+
+
+def test_repeat_layout_cuts_a_caterpillar_longer_than_32_nodes():
+    root = tree.caterpillar_tree(40)
+    flat, shards, ambig, lay = _layout_case(root, 5, 128, seed=5, p_change=0.005, rho=0.0)
+    _check_layout(flat, shards, ambig, lay, 5)
+    assert lay["compressed"].sum() > 32
+    assert len(_paths(lay)) >= 2 and max(len(d["path"]) for d in _paths(lay)) == 32
+    assert max(d["level"] for d in lay["descriptors"]) >= 1                 # (the upper path reads the lower one's table)
+
+
+def test_repeat_layout_of_two_shards_with_different_class_counts():
+    root = tree.random_tree(20, np.random.default_rng(21))
+    flat, shards, ambig, lay = _layout_case(root, 61, 240, seed=9, cuts=(176,), rho=0.0)
+    _check_layout(flat, shards, ambig, lay, 61)
+    assert [s.shape[1] for s in shards] == [176, 64] and len(lay["shards"]) == 2
+    U = [[t[0] for t in sh["tables"]] for sh in lay["shards"]]
+    assert U[0] != U[1] and lay["shards"][0]["rows"] != lay["shards"][1]["rows"]
+
+
+def test_repeat_layout_4_states_hands_the_root_role_down_where_the_stack_is_too_small():
+    """4 states: one walk per compressed subtree root on a stack of 8.  A node over five nodes over five cherries needs 4 + (4 + 1) = 9
+    slots: it stays with the trunk and its children become the roots.  Ambiguity codes stay with the kernels' resolution vectors."""
+    mids = [_node(f"m{i}", *[_node(f"c{i}_{j}", *_leaves(f"l{i}_{j}_", 2)) for j in range(5)]) for i in range(5)]
+    deep = _node("deep", *mids)
+    root = _node("root", deep, _node("pair", *_leaves("p", 2)), *_leaves("r", 2))
+    flat, shards, ambig, lay = _layout_case(root, 4, 300, seed=11, ambig_leaves=("r0", "l0_0_0"))
+    _check_layout(flat, shards, ambig, lay, 4)
+    fp, names = flat.flat_parents, flat.leaf_names
+    n_c = fp[names.index("l0_0_0")]
+    n_m = fp[flat.L + n_c]
+    n_deep = fp[flat.L + n_m]
+    assert not lay["compressed"][n_deep] and lay["compressed"][n_m] and lay["compressed"][n_c]
+    assert lay["rep_desc_of"][flat.L + n_m] >= 0 and lay["rep_desc_of"][flat.L + n_c] < 0
+    d = lay["descriptors"][lay["rep_desc_of"][flat.L + n_m]]
+    assert len(d["path"]) == 6 and list(d["flags"]) == [0, 0, 0, 0, 0, 5]
+    assert lay["view"]["leaf_has_ambig"].sum() == 1 and len(lay["shards"][0]["walk"]) == 0
+
+
+def test_repeat_layout_names_why_it_declines():
+    root = tree.random_tree(12, np.random.default_rng(2))
+    for D, opts, word in ((4, dict(mode=-1), "4 states"), (61, dict(mode=0), "switched off"), (61, dict(mode=1, variant=0), "workgroup-per-tile"),
+                          (61, dict(mode=1), "too few patterns"), (61, dict(mode=2, theta=1e-9), "no node repeats")):
+        res = _layout_case(root, D, 64, seed=1, **opts)[3]
+        assert list(res) == ["declined"] and word in res["declined"], (D, opts, res)
