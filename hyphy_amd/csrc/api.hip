@@ -1402,7 +1402,8 @@ static int evaluate_mixture_common(hyphy_hip_partition *p, EvalRequest rq, const
 extern "C" {
 
 /* Branch-site mixtures on every branch (the reference's "explicit form" models: BUSTED / BS-REL whole-alignment
- * evaluation): P_b = sum_m weights exp(Q_bm), formed on the device. */
+ * evaluation): P_b = sum_m weights exp(Q_bm), formed on the device; 1..16 components per branch, a count of its own on each.
+ * A component that cannot be exponentiated fails the call whatever its weight, 0 included (include/hyphy_hip.h). */
 int hyphy_hip_evaluate_mixture(hyphy_hip_partition *p, int64_t cat, const int64_t *update_nodes, int64_t n_update,
                                const int64_t *q_nodes, int64_t n_q, const int64_t *n_components, const double *q_dense,
                                const double *weights, const double *root_freqs, double *logl_out, double *site_lik_out,

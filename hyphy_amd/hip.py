@@ -433,6 +433,27 @@ def simulate_uniforms(seed: int, n_rep: int, n_nodes: int, n_sites: int) -> np.n
     return out
 
 
+def pack_mixture(n_q: int, components, weights, tail_ndim: int):
+    """Host-only: what the mixture entry points pass on.  ``components``: one array [n_q, M, ...] (the same M on every branch), or a
+    sequence of n_q per-branch arrays [M_k, ...] (``tail_ndim`` trailing axes: 2 for rate matrices, 1 for coefficient rows);
+    ``weights`` [n_q, M], or a sequence of [M_k].  Returns (components [sum M_k, ...], weights [sum M_k], counts [n_q]), branch-major:
+    the components of the first branch, then those of the second, ..."""
+    if isinstance(components, np.ndarray) and components.ndim == tail_ndim + 2:
+        q = np.ascontiguousarray(components, dtype=np.float64)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        assert w.shape == q.shape[:2] and q.shape[0] == n_q
+        return q.reshape((q.shape[0] * q.shape[1],) + q.shape[2:]), w.reshape(-1), np.full(n_q, q.shape[1], dtype=np.int64)
+    per = [np.asarray(c, dtype=np.float64) for c in components]
+    wts = [np.asarray(x, dtype=np.float64).reshape(-1) for x in weights]
+    assert len(per) == n_q and len(wts) == n_q, (len(per), len(wts), n_q)
+    for c, x in zip(per, wts):
+        assert c.ndim == tail_ndim + 1 and c.shape[0] == len(x) and c.shape[1:] == per[0].shape[1:], (c.shape, x.shape)
+    cnt = np.array([len(x) for x in wts], dtype=np.int64)
+    if not n_q:
+        return np.zeros((0,) * (tail_ndim + 1)), np.zeros(0), cnt
+    return np.ascontiguousarray(np.concatenate(per, axis=0)), np.ascontiguousarray(np.concatenate(wts)), cnt
+
+
 def last_expm_kernel() -> str:
     """The matrix-exponential kernel this thread's last launch ran ("expm64_kernel<2>", "expm_mfma_kernel<4,2>", "expm_nuc_kernel",
     ...); "" before the first launch and when the exponentials were folded into a pruning launch."""
@@ -517,14 +538,13 @@ class HipPartition:
         return out.value
 
     def evaluate_mixture(self, update_nodes, q_nodes, q_components, weights, root_freqs, cat: int = -1, per_site: bool = False):
-        """Branch-site mixture on every listed branch: ``q_components`` [n_q, M, D, D] rate matrices, ``weights`` [n_q, M];
+        """Branch-site mixture on every listed branch: ``q_components`` [n_q, M, D, D] rate matrices, ``weights`` [n_q, M], or a
+        sequence of per-branch arrays [M_k, D, D] and [M_k] (1 to 16 components, any count per branch: ``pack_mixture``);
         the device forms ``P_k = sum_m w_km exp(Q_km)`` (explicit-form models: BUSTED / BS-REL)."""
         un = np.ascontiguousarray(update_nodes, dtype=np.int64)
         qn = np.ascontiguousarray(q_nodes, dtype=np.int64)
-        q = np.ascontiguousarray(q_components, dtype=np.float64)
-        w = np.ascontiguousarray(weights, dtype=np.float64)
-        assert q.ndim == 4 and w.shape == q.shape[:2] and q.shape[0] == len(qn)
-        cnt = np.full(len(qn), q.shape[1], dtype=np.int64)
+        q, w, cnt = pack_mixture(len(qn), q_components, weights, 2)
+        assert q.ndim == 3 and q.shape[1:] == (self.D, self.D)
         rf = np.ascontiguousarray(root_freqs, dtype=np.float64)
         out = C.c_double(0.0)
         sl = np.zeros(self.S) if per_site else None
@@ -535,35 +555,39 @@ class HipPartition:
 
     def evaluate_mixture_built(self, update_nodes, q_nodes, coeffs, weights, root_freqs, cat: int = -1, per_site: bool = False):
         """The same with the component rate matrices formed on the device from the uploaded templates: ``coeffs`` [n_q, M, K]
-        (one coefficient row per branch and component: ``hyphy_hip_build_q`` + ``hyphy_hip_evaluate_mixture_built``)."""
+        or a sequence of per-branch [M_k, K] (one coefficient row per branch and component, ``sum M_k`` rows in all:
+        ``hyphy_hip_build_q`` + ``hyphy_hip_evaluate_mixture_built``)."""
         un = np.ascontiguousarray(update_nodes, dtype=np.int64)
         qn = np.ascontiguousarray(q_nodes, dtype=np.int64)
-        c = np.ascontiguousarray(coeffs, dtype=np.float64)
-        w = np.ascontiguousarray(weights, dtype=np.float64)
-        assert c.ndim == 3 and w.shape == c.shape[:2] and c.shape[0] == len(qn)
-        cnt = np.full(len(qn), c.shape[1], dtype=np.int64)
+        c, w, cnt = pack_mixture(len(qn), coeffs, weights, 1)
+        assert c.ndim == 2
         rf = np.ascontiguousarray(root_freqs, dtype=np.float64)
         out = C.c_double(0.0)
         sl = np.zeros(self.S) if per_site else None
         sc = np.zeros(self.S, dtype=np.int64) if per_site else None
-        _check(self._lib.hyphy_hip_build_q(self._h, c.shape[0] * c.shape[1], _d(c)))
+        _check(self._lib.hyphy_hip_build_q(self._h, c.shape[0], _d(c)))
         _check(self._lib.hyphy_hip_evaluate_mixture_built(self._h, cat, _l(un), len(un), _l(qn), len(qn), _l(cnt), _d(w), _d(rf),
                                                           C.byref(out), _d(sl), _l(sc)))
         return (out.value, sl, sc) if per_site else out.value
 
-    def prepare_mixture_built_step(self, update_nodes, q_nodes, weights, root_freqs, coeffs: np.ndarray, cat: int = -1):
+    def prepare_mixture_built_step(self, update_nodes, q_nodes, weights, root_freqs, coeffs: np.ndarray, cat: int = -1, counts=None):
         """Zero-argument callable: ``build_q`` of one coefficient row per (branch, component) + ``evaluate_mixture_built`` -> log-L.
-        ``coeffs`` [n_q, M, K] and ``weights`` [n_q, M] are read at call time."""
+        ``coeffs`` [n_q, M, K] and ``weights`` [n_q, M] are read at call time.  ``counts`` [n_q]: a component count per branch;
+        ``coeffs`` is then [sum counts, K] and ``weights`` [sum counts], branch-major (``pack_mixture``)."""
         un = np.ascontiguousarray(update_nodes, dtype=np.int64)
         qn = np.ascontiguousarray(q_nodes, dtype=np.int64)
         rf = np.ascontiguousarray(root_freqs, dtype=np.float64)
-        assert coeffs.flags.c_contiguous and coeffs.dtype == np.float64 and coeffs.ndim == 3 and coeffs.shape[0] == len(qn)
-        assert weights.flags.c_contiguous and weights.dtype == np.float64 and weights.shape == coeffs.shape[:2]
-        cnt = np.full(len(qn), coeffs.shape[1], dtype=np.int64)
+        assert coeffs.flags.c_contiguous and coeffs.dtype == np.float64 and weights.flags.c_contiguous and weights.dtype == np.float64
+        if counts is None:
+            assert coeffs.ndim == 3 and coeffs.shape[0] == len(qn) and weights.shape == coeffs.shape[:2]
+            cnt = np.full(len(qn), coeffs.shape[1], dtype=np.int64)
+        else:
+            cnt = np.ascontiguousarray(counts, dtype=np.int64)
+            assert cnt.shape == (len(qn),) and coeffs.ndim == 2 and coeffs.shape[0] == int(cnt.sum()) and weights.shape == (coeffs.shape[0],)
         keep = (un, qn, rf, coeffs, weights, cnt)
         lib, h = self._lib, self._h
         pun, pqn, prf, pco, pw, pcnt = _l(un), _l(qn), _d(rf), _d(coeffs), _d(weights), _l(cnt)
-        nun, nqn, nrows = len(un), len(qn), coeffs.shape[0] * coeffs.shape[1]
+        nun, nqn, nrows = len(un), len(qn), int(cnt.sum())
         out = C.c_double(0.0)
         pout = C.byref(out)
 

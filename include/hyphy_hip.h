@@ -159,7 +159,14 @@ int hyphy_hip_evaluate(hyphy_hip_partition *p, int64_t cat, const int64_t *updat
  * of every branch (variablecontainer.cpp:208-233), exponentiates each and recombines them through the formula
  * (tree.cpp:3047-3090).  Here branch q_nodes[k] comes with n_components[k] numeric rate matrices (consecutive in
  * q_dense) and their mixture weights; the device exponentiates all of them in one launch and forms
- * P_k = sum_m weights[.] exp(Q[.]) directly in the layouts the pruning kernels read.
+ * P_k = sum_m weights[.] exp(Q[.]) directly in the layouts the pruning kernels read.  n_components[k] is 1..16 and may differ
+ * from branch to branch; the components are consecutive, branch-major.
+ * A component the device cannot exponentiate (NaN, overflow, a positive diagonal entry: see hyphy_hip_evaluate) fails the whole
+ * call with "Failed to compute a valid transition matrix" (< 0) WHATEVER ITS WEIGHT, weight 0 included: every listed component is
+ * exponentiated and raises the status word on its own, and the NaN it leaves would reach the images through 0 * NaN anyway.  The
+ * listed branches are then without usable matrices (never their previous ones): a full pass with good matrices on the same
+ * partition gives the value a fresh partition gives (tests/test_gpu_mixture.py::test_a_bad_component_never_gives_a_finite_value).
+ * A caller that wants a component out of the mixture leaves it out of the list.
  */
 int hyphy_hip_evaluate_mixture(hyphy_hip_partition *p, int64_t cat, const int64_t *update_nodes, int64_t n_update,
                                const int64_t *q_nodes, int64_t n_q, const int64_t *n_components /* [n_q] */,
