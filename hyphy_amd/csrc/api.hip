@@ -20,23 +20,9 @@ namespace {
 void free_shard(Shard &s) {
   hipSetDevice(s.device);
   if (s.stream) hipStreamSynchronize(s.stream);
-  void *dev[] = {s.codes, s.freq,  s.ambig,  s.partials, s.counts, s.site_lik, s.site_cnt, s.mixed_lik, s.mixed_cnt,
-                 s.Pfrag, s.PTg,   s.Prow,   s.qbuf,     s.slots,  s.ops,      s.pi,       s.out,       s.status,
-                 s.weights, s.templates, s.templates_pad, s.coeffs, s.wg_sum, s.wg_cnt, s.wg_flag, s.prog, s.frag_ctr, s.hand_cnt, s.pi_ones, s.codes_tile,
-                 s.bc_ops, s.bc_prog, s.bc_slot, s.bc_q, s.pin, s.jn, s.deposits, s.mix_q, s.mix_p, s.mix_w, s.mix_off, s.ar_buf, s.fit_Timg, s.fit_bcoef, s.fit_smult, s.fit_smix, s.fit_out, s.fit_scratch,
-                 s.fit_pi, s.fit_bgroup, s.fit_scratch_cnt, s.fit_ops, s.rep_tab, s.rep_cnt, s.rep_map, s.rep_desc, s.rep_sync,
-                 s.rep_codes_tile, s.rep_leaf, s.rep_walk, s.d_inv, s.expm_need, s.marg_U, s.marg_work, s.marg_PT, s.marg_pi, s.marg_Ucnt,
-                 s.marg_wcnt, s.marg_prog};
-  for (void *d : dev)
-    if (d) pool_free(d);  // (the stream was synchronised above)
-  void *host[] = {s.h_ops, s.h_out, s.h_slots, s.h_small, s.h_coeffs, s.h_prog, s.h_jn, s.h_tstage, s.h_site, s.h_export};
-  for (void *h : host)
-    if (h) pool_host_free(h);
-  for (RepPassSlot &ps : s.rep_slot) {  // (item queues of the lower phase, repeats.hip)
-    if (ps.items) pool_free(ps.items);
-    if (ps.h_items) pool_host_free(ps.h_items);
+  s.own.release_all();  // (the stream was synchronised above)
+  for (RepPassSlot &ps : s.rep_slot)
     if (ps.ev) hipEventDestroy(ps.ev);
-  }
   for (auto &e : s.ev)
     if (e) hipEventDestroy(e);
   for (auto &e : s.ev_ar)
@@ -92,26 +78,18 @@ int ensure_deposits(hyphy_hip_partition *p, Shard &s) {
   const size_t node_stride = (size_t)s.ntiles * 16 * p->DP;
   const size_t class_stride = (size_t)p->vw().I * node_stride;
   const size_t need = (size_t)p->C * class_stride;
-  if (s.deposits && s.deposits_cap >= need) {
-    s.deposits_class_stride = class_stride;
-    return 0;
-  }
-  if (s.deposits) {
-    HIPCHK(hipStreamSynchronize(s.stream));
-    pool_free_sync(s.deposits);
-    s.dev_bytes -= s.deposits_cap * sizeof(double);
-    s.deposits = nullptr;
-    s.deposits_cap = 0;
-  }
-  HIPCHK(pool_malloc((void **)&s.deposits, need * sizeof(double)));
-  s.deposits_cap = need;
   s.deposits_class_stride = class_stride;
-  s.dev_bytes += need * sizeof(double);
+  if (s.deposits_cap >= need) return 0;
+  HIPCHK(s.own.regrow({device_block(s.deposits, need * sizeof(double))}, s.deposits_cap, need, need, FreeMode::Sync));
   if (sw::poison()) {
     HIPCHK(hipMemset(s.deposits, 0xff, need * sizeof(double)));
     HIPCHK(hipDeviceSynchronize());
   }
   return 0;
+}
+void release_deposits(Shard &s) {  // (a smaller view takes over: ensure_deposits sizes them again)
+  s.own.drop(s.deposits, FreeMode::Sync);
+  s.deposits_cap = 0;
 }
 
 // Everything in a PruneArgs that does not depend on the schedule being launched.
@@ -296,18 +274,11 @@ int EvalCtx::stage_expm_mixture() {
   //  component) here — and an evaluation of the other kind that happens to need the same number of rows is refused)
   if (mix_built && s.coeff_kind == 1) return fail("mixture evaluation: the staged rows were consumed as one row per (class, branch): call hyphy_hip_build_q first");
   if (mix_built) s.coeff_kind = 2;
-  if (s.mix_cap < n_tot || s.mix_nq_cap < (size_t)n_q) {
-    HIPCHK(hipStreamSynchronize(s.stream));
-    for (void *d : {(void *)s.mix_q, (void *)s.mix_p, (void *)s.mix_w, (void *)s.mix_off})
-      if (d) pool_free_sync(d);
-    s.mix_q = s.mix_p = s.mix_w = nullptr;
-    s.mix_off = nullptr;
-    s.mix_cap = std::max(n_tot, (size_t)(2 * B));
-    s.mix_nq_cap = (size_t)B;
-    HIPCHK(pool_malloc((void **)&s.mix_q, s.mix_cap * DD * sizeof(double)));
-    HIPCHK(pool_malloc((void **)&s.mix_p, s.mix_cap * DD * sizeof(double)));
-    HIPCHK(pool_malloc((void **)&s.mix_w, s.mix_cap * sizeof(double)));
-    HIPCHK(pool_malloc((void **)&s.mix_off, (s.mix_nq_cap + 1) * sizeof(int)));
+  {  // (n_q <= B: eval_common has checked)
+    const size_t cap = std::max(n_tot, (size_t)(2 * B));
+    HIPCHK(s.own.regrow({device_block(s.mix_q, cap * DD * sizeof(double)), device_block(s.mix_p, cap * DD * sizeof(double)),
+                         device_block(s.mix_w, cap * sizeof(double)), device_block(s.mix_off, ((size_t)B + 1) * sizeof(int))},
+                        s.mix_cap, n_tot, cap, FreeMode::Sync));
   }
   std::vector<int> off((size_t)n_q + 1, 0);
   for (int64_t k = 0; k < n_q; k++) off[k + 1] = off[k] + (int)rq.mix->count[k];
@@ -471,7 +442,6 @@ int EvalCtx::dump_timeline(const Timeline &tl) {
   std::vector<long long> h(tl.n);
   HIPCHK(hipStreamSynchronize(s.stream));
   HIPCHK(hipMemcpy(h.data(), tl.buf, tl.n * sizeof(long long), hipMemcpyDeviceToHost));
-  pool_free_sync(tl.buf);
   FILE *f = fopen(tl.path, "w");
   if (!f) return 0;
   if (tl.per_wave) {
@@ -502,8 +472,9 @@ int EvalCtx::stage_prune_mfma() {
   const size_t tl_waves = (size_t)s.ntiles * std::max(1, n_cat_batch) * std::max<size_t>(1, p->programs.size());
   Timeline tl{sw::timeline(), p->variant == 1, tl_waves,
               p->variant == 1 ? tl_waves * 24 : (size_t)kTraceWG * p->NW * std::max(1, n_ops) * 4, nullptr};
+  Blocks tl_blk;  // (back to the pool behind the dump)
   if (tl.path && n_ops > 0 && s.T == 1) {
-    HIPCHK(pool_malloc((void **)&tl.buf, tl.n * sizeof(long long)));
+    HIPCHK(tl_blk.get(&tl.buf, tl.n));
     HIPCHK(hipMemsetAsync(tl.buf, 0, tl.n * sizeof(long long), s.stream));
     pa.timeline = tl.buf;
   }
@@ -713,27 +684,22 @@ int begin_site_export(hyphy_hip_partition *p, bool want_lik, bool want_cnt) {
   if (!s.h_export && !s.export_failed) {
     // (the pattern-order map first — a partition whose patterns are sorted must never export without it, and a failed
     //  allocation must not leave a half-initialised export behind: on any failure this partition keeps the copies of gather_sites)
-    int32_t *d_inv = nullptr;
-    double *h_export = nullptr, *d_export = nullptr;
-    bool ok = true;
-    if (!p->perm.empty()) {
+    bool ok = s.own.get_group({device_block(s.d_inv, p->perm.empty() ? 0 : (size_t)s.S * sizeof(int32_t)),
+                               pinned_block(s.h_export, (size_t)s.S * 2 * sizeof(double))}) == hipSuccess;
+    if (ok && !p->perm.empty()) {
       std::vector<int32_t> inv((size_t)s.S, 0);
       for (int64_t j = 0; j < s.S; j++) inv[(size_t)p->perm[(size_t)j]] = (int32_t)j;
-      ok = pool_malloc((void **)&d_inv, inv.size() * sizeof(int32_t)) == hipSuccess &&
-           hipMemcpy(d_inv, inv.data(), inv.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+      ok = hipMemcpy(s.d_inv, inv.data(), inv.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
     }
-    ok = ok && pool_host_malloc((void **)&h_export, (size_t)s.S * 2 * sizeof(double)) == hipSuccess &&
-         hipHostGetDevicePointer((void **)&d_export, h_export, 0) == hipSuccess && d_export;
+    ok = ok && hipHostGetDevicePointer((void **)&s.d_export, s.h_export, 0) == hipSuccess && s.d_export;
     if (!ok) {
       (void)hipGetLastError();
-      if (d_inv) pool_free_sync(d_inv);
-      if (h_export) pool_host_free(h_export);
+      s.own.drop(s.d_inv, FreeMode::Sync);
+      s.own.drop(s.h_export, FreeMode::Sync);
+      s.d_export = nullptr;
       s.export_failed = true;
       return 0;
     }
-    s.d_inv = d_inv;
-    s.h_export = h_export;
-    s.d_export = d_export;
   }
   if (!s.d_export || (!p->perm.empty() && !s.d_inv)) return 0;
   p->export_sites = (want_lik ? 1 : 0) | (want_cnt ? 2 : 0);
@@ -746,7 +712,7 @@ int gather_sites(hyphy_hip_partition *p, int cat, double *site_lik_out, int64_t 
     const int32_t *cn = mixed ? s.mixed_cnt : s.site_cnt + (size_t)cat * s.S_pad;
     // both arrays through ONE pinned staging block and one wait (r04; was: two pageable temporaries, a wait behind each copy —
     // a host that mixes rate classes itself asks for these once per class and evaluation)
-    if (!s.h_site) HIPCHK(pool_host_malloc((void **)&s.h_site, (size_t)s.S_pad * (sizeof(double) + sizeof(int32_t))));
+    if (!s.h_site) HIPCHK(s.own.get(pinned_block(s.h_site, (size_t)s.S_pad * (sizeof(double) + sizeof(int32_t)))));
     double *hl = s.h_site;
     int32_t *hc = reinterpret_cast<int32_t *>(s.h_site + s.S_pad);
     if (site_lik_out) HIPCHK(hipMemcpyAsync(hl, lik, s.S * sizeof(double), hipMemcpyDeviceToHost, s.stream));
@@ -807,6 +773,255 @@ int mix_and_reduce_categories(hyphy_hip_partition *p, const double *weights, boo
     if (&s == &p->shards[0]) p->last_reduce = {"site", s.S_pad, true};
   }
   return 0;
+}
+
+// ---- hyphy_hip_create, step by step --------------------------------------------------------------------------------------------
+struct CreateInput {
+  int64_t D, S, L, I, C;
+  const int64_t *flat_parents, *leaf_codes;
+  const double *ambig;
+  int64_t n_ambig;
+  const int64_t *pattern_freq;
+};
+
+// Step 1: the arguments and the tree.  0: *out is the partition (no shard yet) and *nshards says how many it gets; else hyphy_hip_create's result.
+int checked_partition(const CreateInput &in, int device_first, int device_count, hyphy_hip_partition **out, int *nshards_out) {
+  const int64_t D = in.D, S = in.S, L = in.L, I = in.I, C = in.C;
+  if (D < 2 || D > 64) {
+    g_last_error = "unsupported state count (this version: 2 <= D <= 64)";
+    return 1;
+  }
+  if (S < 1 || L < 2 || I < 1 || C < 1 || !in.flat_parents || !in.leaf_codes || !in.pattern_freq)
+    return fail("invalid partition dimensions / null input");
+  if (L > 65535) {
+    g_last_error = "more than 65535 leaves: packed schedule entries unsupported in this version";
+    return 1;
+  }
+  if (in.n_ambig > 32767) {
+    g_last_error = "too many distinct ambiguity vectors for the packed leaf table";
+    return 1;
+  }
+  int ndev = hyphy_hip_device_count();
+  if (ndev <= 0) return fail("no HIP device available (this library has no CPU fallback)");
+  const int force = sw::force_shards();
+  if (device_count < 1) device_count = 1;
+  if (!force && (device_first < 0 || device_first + device_count > ndev)) return fail("device range out of bounds");
+  if (force > 0 && device_first >= ndev) return fail("device out of bounds");
+  int nshards = force > 0 ? force : device_count;
+  if ((int64_t)nshards > S) nshards = (int)S;
+  *nshards_out = nshards;
+
+  hyphy_hip_partition *p = new hyphy_hip_partition();
+  p->D = D; p->S = S; p->L = L; p->I = I; p->C = C; p->B = L + I - 1;
+  p->nuc = (D == 4);
+  p->NW = (int)((D + 15) / 16);
+  p->DP = 16 * p->NW;
+  p->parents.assign(in.flat_parents, in.flat_parents + L + I);
+  p->children.assign(I, std::vector<int>());
+  int roots = 0;
+  for (int64_t n = 0; n < L + I; n++) {
+    int64_t par = in.flat_parents[n];
+    if (par < 0) { roots++; continue; }
+    if (par >= I || (n >= L && par <= n - L)) { delete p; return fail("flat_parents is not a post-order tree"); }
+    p->children[par].push_back((int)n);
+  }
+  if (roots != 1 || in.flat_parents[L + I - 1] != -1) { delete p; return fail("root must be the last internal node"); }
+  for (int64_t k = 0; k < L * S; k++)
+    if (in.leaf_codes[k] >= D || in.leaf_codes[k] < -in.n_ambig) { delete p; return fail("leaf code out of range"); }
+  p->initialized.assign(C, 0);
+  p->bc_node.assign(C, -1);
+  p->bc_use_pi.assign(C, 0);
+  p->resident.assign(C, 0);
+  p->last_full.assign(C, 0);
+  p->cache_policy = sw::cache_always() ? 0 : 1;
+  p->leaf_has_ambig.assign(L, 0);
+  for (int64_t l = 0; l < L; l++)
+    for (int64_t k = 0; k < S; k++)
+      if (in.leaf_codes[l * S + k] < 0) {
+        p->leaf_has_ambig[l] = 1;
+        break;
+      }
+  *out = p;
+  return 0;
+}
+
+// Step 2: a shard's geometry and the kernel its size asks for.  Host arithmetic only: of the device it needs the CU count.
+void shard_geometry(hyphy_hip_partition *p, Shard &s, int cus) {
+  const int64_t L = p->L, I = p->I;
+  const int DP = p->DP;
+  const int tiles_override = sw::tiles();
+  const int64_t tiles = (s.S + 15) / 16;
+  int T = 1;
+  if (!p->nuc) {
+    // T = 1 everywhere the wave-per-tile kernel applies (any shard of >= 1.75 tiles per CU: measured 2.3x
+    // faster than the T = 2 workgroup kernel at 128 taxa x 100k codons, 2 718 vs 6 190 us); T > 1 only beyond
+    // the grid limit of 65 535 tiles
+    T = tiles <= 65535 ? 1 : (tiles <= 2 * 65535 ? 2 : 4);
+    if (tiles_override >= 1 && tiles_override <= 4) T = tiles_override;
+  }
+  s.T = T;
+  s.cus = cus;
+  if (p->nuc) p->n_slots = 2 + kNucParkSlots;  // (prune_nuc_kernel parks pending nodes in LDS)
+  if (p->nuc) p->nuc_leaf_pairs = prune_nuc_takes_leaf_pairs((int)L);
+  if (!p->nuc) {
+    // Kernel choice (measured, tools/sweep_small_shards.sh): the wave-per-tile kernel (no cross-wave
+    // exchange, child -> parent through registers) wins once every SIMD holds ~2 waves of it — 160 vs 183 us
+    // at 624 tiles; below that its 64-MFMA-per-edge chains are pure latency (167 us at 312 tiles as at
+    // 624) and the workgroup-per-tile kernel, which splits a tile's rows over four waves, is faster
+    // (123 us at 312 tiles, 63 us at 78).
+    // (r02: with chain schedules the wave-per-tile kernel also wins at a rank's share of the headline workload —
+    //  89 vs 118 us at 312 tiles, 52 vs 61 us at 78; below ~a quarter tile per CU the row-split workgroup kernel
+    //  keeps its shorter critical path.  The schedule tuner re-checks the choice on the first steady-state pass.)
+    p->variant = tiles >= (int64_t)cus / 4 ? 1 : 0;
+    p->kernel_forced = false;
+    if (const int k = sw::kernel(); k >= 0) {  // (diagnostic override)
+      p->variant = k;  // 0: workgroup per tile, 1: wave per tile, 2: workgroup per tile on chain schedules
+      p->kernel_forced = true;
+    }
+    if (T != 1) {
+      p->variant = 0;
+      p->kernel_forced = true;
+    }
+    // two "exchange" ids (register hand-over) + wave-private LDS parking slots: two where two tiles + the leaf codes fit an
+    // eighth of the CU's 160 KiB (eight waves per CU stay resident: 61 states up to 128 taxa), else one
+    {
+      const size_t tile_bytes = (size_t)p->NW * 4 * 64 * sizeof(double), codes_bytes = (size_t)p->L * 16 * sizeof(int16_t);
+      p->n_slots_wave = 2 * tile_bytes + codes_bytes <= 20480 ? 4 : 3;
+    }
+    if (const int n = sw::slots()) p->n_slots_wave = n;
+    p->n_slots = p->variant == 1 ? p->n_slots_wave : lds_slots(T);
+  }
+  if (p->nuc) {
+    s.S_pad = (int)((s.S + 511) / 512 * 512);  // (prune_nuc2_kernel: 256 threads x 2 patterns per workgroup)
+    s.ntiles = 0;
+    s.partial_stride = (size_t)I * 4 * s.S_pad;
+  } else {
+    s.ntiles = (int)((tiles + T - 1) / T * T);
+    s.S_pad = s.ntiles * 16;
+    s.partial_stride = (size_t)I * s.ntiles * 16 * DP;
+  }
+  s.wg_cap = p->nuc ? (s.S_pad + 255) / 256 : s.ntiles;
+  s.h_small_cap = (size_t)std::max<int64_t>(std::max<int64_t>(DP, p->C), 64);
+}
+
+// Step 3: the stream, the events and every block a shard holds from creation on, as one table.  -1: fail() has said which is missing.
+int allocate_shard(hyphy_hip_partition *p, Shard &s, int64_t n_ambig) {
+  const int64_t D = p->D, L = p->L, I = p->I, C = p->C, B = p->B;
+  const int DP = p->DP;
+  const size_t mfma = p->nuc ? 0 : 1, nuc = p->nuc ? 1 : 0;  // (a row of no bytes is no block: the field stays null)
+  // (+2 node slots per class behind the last class: outside vector of the cached branch and a scratch slot, see
+  //  hyphy_hip_branch_cache_build)
+  const size_t node_stride = p->nuc ? (size_t)4 * s.S_pad : (size_t)s.ntiles * 16 * DP;
+  const size_t wg_rows = (size_t)C * s.wg_cap + 4;  // x C: rate-class batching writes one row per class; + 4: the fused final combine reads them with 16-byte loads
+  pool_stream_get(&s.own_stream);
+  s.stream = s.own_stream;
+  for (auto &e : s.ev) hipEventCreate(&e);
+  s.ring.assign(2 * kTimingRing, nullptr);
+  const BlockReq table[] = {
+      device_block(s.codes, (size_t)L * s.S_pad * sizeof(int16_t), "s.codes"),
+      device_block(s.codes_tile, mfma * L * s.S_pad * sizeof(int16_t), "s.codes_tile"),
+      device_block(s.expm_need, mfma * B, "s.expm_need"),
+      device_block(s.bc_ops, mfma * ops_capacity(p) * sizeof(int4), "s.bc_ops"),
+      device_block(s.bc_prog, mfma * sizeof(int4), "s.bc_prog"),
+      device_block(s.bc_slot, mfma * C * sizeof(int32_t), "s.bc_slot"),
+      device_block(s.bc_q, mfma * D * D * sizeof(double), "s.bc_q"),
+      device_block(s.freq, (size_t)s.S_pad * sizeof(double), "s.freq"),
+      device_block(s.pin, (size_t)s.S_pad * sizeof(int16_t), "s.pin"),
+      device_block(s.ambig, (size_t)std::max<int64_t>(1, n_ambig) * DP * sizeof(double), "s.ambig"),
+      device_block(s.partials, ((size_t)C * s.partial_stride + 2 * C * node_stride) * sizeof(double), "s.partials"),
+      device_block(s.counts, ((size_t)C * I + 2 * C) * s.S_pad * sizeof(int32_t), "s.counts"),
+      device_block(s.site_lik, (size_t)C * s.S_pad * sizeof(double), "s.site_lik"),
+      device_block(s.site_cnt, (size_t)C * s.S_pad * sizeof(int32_t), "s.site_cnt"),
+      device_block(s.mixed_lik, (size_t)s.S_pad * sizeof(double), "s.mixed_lik"),
+      device_block(s.mixed_cnt, (size_t)s.S_pad * sizeof(int32_t), "s.mixed_cnt"),
+      device_block(s.Prow, nuc * 2 * C * B * 16 * sizeof(double), "s.Prow"),  // row-major, then transposed (prune_nuc2_kernel)
+      // (+ transposed path matrices of the branch cache, + twins of re-rooted schedules)
+      device_block(s.Pfrag, mfma * ((size_t)C * B + (size_t)C * (I + 2) + kMaxTwin) * DP * DP * sizeof(double), "s.Pfrag"),
+      device_block(s.pi_ones, mfma * DP * sizeof(double), "s.pi_ones"),
+      device_block(s.PTg, mfma * C * B * DP * DP * sizeof(double), "s.PTg"),
+      device_block(s.qbuf, (size_t)C * B * D * D * sizeof(double), "s.qbuf"),
+      device_block(s.slots, (size_t)C * B * sizeof(int32_t), "s.slots"),
+      device_block(s.ops, ops_capacity(p) * sizeof(int4), "s.ops"),
+      device_block(s.prog, (size_t)(I + 2) * sizeof(int4), "s.prog"),
+      device_block(s.jn, (size_t)(I + 2) * sizeof(int4), "s.jn"),
+      device_block(s.frag_ctr, mfma * C * (I + 2) * s.ntiles * sizeof(int), "s.frag_ctr"),
+      device_block(s.hand_cnt, mfma * C * I * s.ntiles * 32 * sizeof(int32_t), "s.hand_cnt"),
+      device_block(s.pi, (size_t)DP * sizeof(double), "s.pi"),
+      device_block(s.out, 4 * sizeof(double), "s.out"),        // device-side result record [log-L, scaler sum, status copy, pad]
+      device_block(s.status, sizeof(int32_t), "s.status"),     // set by the expm kernel when a matrix fails
+      device_block(s.weights, (size_t)C * sizeof(double), "s.weights"),
+      device_block(s.wg_sum, wg_rows * sizeof(double), "s.wg_sum"),
+      device_block(s.wg_cnt, wg_rows * sizeof(long long), "s.wg_cnt"),
+      device_block(s.wg_flag, wg_rows * sizeof(int), "s.wg_flag"),
+      pinned_block(s.h_ops, ops_capacity(p) * sizeof(int4)),
+      pinned_block(s.h_prog, (size_t)(I + 2) * sizeof(int4)),
+      pinned_block(s.h_jn, (size_t)(I + 2) * sizeof(int4)),
+      pinned_block(s.h_out, 4 * sizeof(double)),
+      pinned_block(s.h_slots, (size_t)C * B * sizeof(int32_t)),
+      pinned_block(s.h_small, s.h_small_cap * sizeof(double))};
+  const BlockReq *missing = nullptr;
+  if (s.own.get_group(table, sizeof table / sizeof table[0], &missing) != hipSuccess)
+    return fail(missing->pinned ? std::string("hipHostMalloc failed") : std::string("hipMalloc failed (") + missing->name + ")");
+  // HYPHY_HIP_POISON=1 (tests): fill every fresh allocation with 0xff bytes (NaN / -1), so that anything read before
+  // it is written shows up even in a process whose recycled device memory happens to hold zeros
+  if (sw::poison())
+    for (const BlockReq &b : table)
+      if (*b.field && !b.pinned && !sw::nopoison(b.name)) {
+        hipMemset(*b.field, 0xff, b.bytes);
+        hipDeviceSynchronize();
+      }
+  return 0;
+}
+
+// Step 4: what the blocks hold before the first evaluation.  `codes_out`: the leaf table in device pattern order ([L][S_pad]; padding
+// patterns use state 0, weight 0), which the class computation of subtree repeats reads.
+void upload_shard(hyphy_hip_partition *p, Shard &s, const CreateInput &in, std::vector<int16_t> &codes) {
+  const int64_t D = p->D, S = p->S, L = p->L, I = p->I, C = p->C, B = p->B;
+  const int DP = p->DP;
+  auto src_pattern = [&](int64_t j) -> int64_t { return p->perm.empty() ? j : p->perm[j]; };
+  if (!p->nuc) {  // which matrix images a branch's consumers read (ExpmArgs::need): leaves are gathered from by state — the column-gather
+                  // image —, internal branches are A operands of edge products; a leaf with ambiguity codes is both
+    std::vector<unsigned char> need((size_t)B, 3);
+    for (int64_t c = 0; c < L && c < B; c++) need[(size_t)c] = p->leaf_has_ambig[(size_t)c] ? 3 : 2;
+    for (int64_t c = L; c < L + I - 1 && c < B; c++) need[(size_t)c] = 1;
+    hipMemcpy(s.expm_need, need.data(), (size_t)B, hipMemcpyHostToDevice);
+  }
+  hipMemset(s.pin, 0, (size_t)s.S_pad * sizeof(int16_t));
+  if (!p->nuc) {
+    std::vector<double> ones(DP, 0.);
+    for (int64_t k = 0; k < D; k++) ones[k] = 1.;
+    hipMemcpy(s.pi_ones, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice);
+    hipMemset(s.frag_ctr, 0, (size_t)C * (I + 2) * s.ntiles * sizeof(int));
+  }
+  hipMemset(s.wg_flag + (size_t)C * s.wg_cap, 0, 4 * sizeof(int));  // (the last word: arrival counter of the 4-state kernel's fused combine)
+  hipMemsetAsync(s.status, 0, sizeof(int32_t), s.stream);
+  if (hipHostGetDevicePointer((void **)&s.d_hout, s.h_out, 0) != hipSuccess) s.d_hout = nullptr;
+  for (int k = 0; k < 4; k++) s.h_out[k] = 0.;
+  hipMemsetAsync(s.partials, 0, (size_t)C * s.partial_stride * sizeof(double), s.stream);
+  hipMemsetAsync(s.counts, 0, (size_t)C * I * s.S_pad * sizeof(int32_t), s.stream);
+  hipMemsetAsync(s.site_lik, 0, (size_t)C * s.S_pad * sizeof(double), s.stream);
+  hipMemsetAsync(s.site_cnt, 0, (size_t)C * s.S_pad * sizeof(int32_t), s.stream);
+  // leaf table: int64 pattern-indexed -> packed int16 [L][S_pad]
+  codes.assign((size_t)L * s.S_pad, 0);
+  for (int64_t l = 0; l < L; l++)
+    for (int64_t k = 0; k < s.S; k++) codes[(size_t)l * s.S_pad + k] = (int16_t)in.leaf_codes[l * S + src_pattern(s.s0 + k)];
+  std::vector<double> fr(s.S_pad, 0.0);
+  for (int64_t k = 0; k < s.S; k++) fr[k] = (double)in.pattern_freq[src_pattern(s.s0 + k)];
+  std::vector<double> amb((size_t)std::max<int64_t>(1, in.n_ambig) * DP, 0.0);
+  const int astride = p->nuc ? 4 : DP;
+  for (int64_t a = 0; a < in.n_ambig; a++)
+    for (int64_t k = 0; k < D; k++) amb[a * astride + k] = in.ambig[a * D + k];
+  hipMemcpy(s.codes, codes.data(), codes.size() * sizeof(int16_t), hipMemcpyHostToDevice);
+  if (!p->nuc) {  // tile-major copy [tile][L][16] for the wave-per-tile kernels: a tile's codes are one 32 L-byte run
+    std::vector<int16_t> ct((size_t)L * s.S_pad, 0);
+    for (int64_t l = 0; l < L; l++)
+      for (int64_t k = 0; k < s.S_pad; k++) ct[((size_t)(k >> 4) * L + l) * 16 + (k & 15)] = codes[(size_t)l * s.S_pad + k];
+    hipMemcpy(s.codes_tile, ct.data(), ct.size() * sizeof(int16_t), hipMemcpyHostToDevice);
+  }
+  hipMemcpy(s.freq, fr.data(), fr.size() * sizeof(double), hipMemcpyHostToDevice);
+  hipMemcpy(s.ambig, amb.data(), amb.size() * sizeof(double), hipMemcpyHostToDevice);
+  // (the host copy is only kept for the class computation of subtree repeats)
+  if (sw::repeats() == 0) std::vector<int16_t>().swap(codes);
 }
 
 }  // namespace
@@ -889,7 +1104,7 @@ int hyphy_hip_device_count(void) {
 void hyphy_hip_destroy(hyphy_hip_partition *p) {
   if (!p) return;
   for (Shard &s : p->shards) free_shard(s);
-  if (p->h_qstage) { hipDeviceSynchronize(); pool_host_free(p->h_qstage); }
+  p->own.drop(p->h_qstage, FreeMode::Sync);
   if (p->xch) hyphy_hip_xch_close(p->xch);
   delete p;
 }
@@ -899,76 +1114,23 @@ int hyphy_hip_create(hyphy_hip_partition **out, int64_t D, int64_t S, int64_t L,
                      const int64_t *pattern_freq, int device_first, int device_count) {
   if (!out) return fail("out == NULL");
   *out = nullptr;
-  if (D < 2 || D > 64) {
-    g_last_error = "unsupported state count (this version: 2 <= D <= 64)";
-    return 1;
-  }
-  if (S < 1 || L < 2 || I < 1 || C < 1 || !flat_parents || !leaf_codes || !pattern_freq)
-    return fail("invalid partition dimensions / null input");
-  if (L > 65535) {
-    g_last_error = "more than 65535 leaves: packed schedule entries unsupported in this version";
-    return 1;
-  }
-  if (n_ambig > 32767) {
-    g_last_error = "too many distinct ambiguity vectors for the packed leaf table";
-    return 1;
-  }
-  int ndev = hyphy_hip_device_count();
-  if (ndev <= 0) return fail("no HIP device available (this library has no CPU fallback)");
-  const int force = sw::force_shards();
-  if (device_count < 1) device_count = 1;
-  if (!force && (device_first < 0 || device_first + device_count > ndev)) return fail("device range out of bounds");
-  if (force > 0 && device_first >= ndev) return fail("device out of bounds");
-  int nshards = force > 0 ? force : device_count;
-  if ((int64_t)nshards > S) nshards = (int)S;
-
-  hyphy_hip_partition *p = new hyphy_hip_partition();
-  p->D = D; p->S = S; p->L = L; p->I = I; p->C = C; p->B = L + I - 1;
-  p->nuc = (D == 4);
-  p->NW = (int)((D + 15) / 16);
-  p->DP = 16 * p->NW;
-  p->parents.assign(flat_parents, flat_parents + L + I);
-  p->children.assign(I, std::vector<int>());
-  int roots = 0;
-  for (int64_t n = 0; n < L + I; n++) {
-    int64_t par = flat_parents[n];
-    if (par < 0) { roots++; continue; }
-    if (par >= I || (n >= L && par <= n - L)) { delete p; return fail("flat_parents is not a post-order tree"); }
-    p->children[par].push_back((int)n);
-  }
-  if (roots != 1 || flat_parents[L + I - 1] != -1) { delete p; return fail("root must be the last internal node"); }
-  for (int64_t k = 0; k < L * S; k++)
-    if (leaf_codes[k] >= D || leaf_codes[k] < -n_ambig) { delete p; return fail("leaf code out of range"); }
-  p->initialized.assign(C, 0);
-  p->bc_node.assign(C, -1);
-  p->bc_use_pi.assign(C, 0);
-  p->resident.assign(C, 0);
-  p->last_full.assign(C, 0);
-  p->cache_policy = sw::cache_always() ? 0 : 1;
-  p->leaf_has_ambig.assign(L, 0);
-  for (int64_t l = 0; l < L; l++)
-    for (int64_t k = 0; k < S; k++)
-      if (leaf_codes[l * S + k] < 0) {
-        p->leaf_has_ambig[l] = 1;
-        break;
-      }
-
-  const int DP = p->DP;
-  const int64_t B = p->B;
-  const int tiles_override = sw::tiles();
+  const CreateInput in = {D, S, L, I, C, flat_parents, leaf_codes, ambig, n_ambig, pattern_freq};
+  hyphy_hip_partition *p = nullptr;
+  int nshards = 0;
+  if (const int r = checked_partition(in, device_first, device_count, &p, &nshards)) return r;
   if (!p->nuc && sw::sort_patterns()) sort_patterns(p, leaf_codes, L, S);
   init_plain_view(p);
   if (!p->nuc && C == 1) reroot_path(p);
-  auto src_pattern = [&](int64_t j) -> int64_t { return p->perm.empty() ? j : p->perm[j]; };
 
+  const int force = sw::force_shards();
   int64_t base = S / nshards, rem = S % nshards, s0 = 0;
+  p->shards.resize((size_t)nshards);  // (in place before anything is allocated: a shard owns its blocks and does not copy)
   for (int k = 0; k < nshards; k++) {
-    Shard s;
+    Shard &s = p->shards[(size_t)k];
     s.device = force > 0 ? device_first : device_first + k;
     s.s0 = s0;
     s.S = base + (k < rem ? 1 : 0);
     s0 += s.S;
-    p->shards.push_back(s);
   }
   std::vector<std::vector<int16_t>> shard_codes;  // per shard: the leaf table in device pattern order (class computation below)
   for (Shard &s : p->shards) {
@@ -979,177 +1141,13 @@ int hyphy_hip_create(hyphy_hip_partition **out, int64_t D, int64_t S, int64_t L,
       hyphy_hip_destroy(p);
       return fail(std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
     }
-    const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    const int64_t tiles = (s.S + 15) / 16;
-    int T = 1;
-    if (!p->nuc) {
-      // T = 1 everywhere the wave-per-tile kernel applies (any shard of >= 1.75 tiles per CU: measured 2.3x
-      // faster than the T = 2 workgroup kernel at 128 taxa x 100k codons, 2 718 vs 6 190 us); T > 1 only beyond
-      // the grid limit of 65 535 tiles
-      T = tiles <= 65535 ? 1 : (tiles <= 2 * 65535 ? 2 : 4);
-      if (tiles_override >= 1 && tiles_override <= 4) T = tiles_override;
-    }
-    s.T = T;
-    s.cus = cus;
-    if (p->nuc) p->n_slots = 2 + kNucParkSlots;  // (prune_nuc_kernel parks pending nodes in LDS)
-    if (p->nuc) p->nuc_leaf_pairs = prune_nuc_takes_leaf_pairs((int)L);
-    if (!p->nuc) {
-      // Kernel choice (measured, tools/sweep_small_shards.sh): the wave-per-tile kernel (no cross-wave
-      // exchange, child -> parent through registers) wins once every SIMD holds ~2 waves of it — 160 vs 183 us
-      // at 624 tiles; below that its 64-MFMA-per-edge chains are pure latency (167 us at 312 tiles as at
-      // 624) and the workgroup-per-tile kernel, which splits a tile's rows over four waves, is faster
-      // (123 us at 312 tiles, 63 us at 78).
-      // (r02: with chain schedules the wave-per-tile kernel also wins at a rank's share of the headline workload —
-      //  89 vs 118 us at 312 tiles, 52 vs 61 us at 78; below ~a quarter tile per CU the row-split workgroup kernel
-      //  keeps its shorter critical path.  The schedule tuner re-checks the choice on the first steady-state pass.)
-      p->variant = tiles >= (int64_t)cus / 4 ? 1 : 0;
-      p->kernel_forced = false;
-      if (const int k = sw::kernel(); k >= 0) {  // (diagnostic override)
-        p->variant = k;  // 0: workgroup per tile, 1: wave per tile, 2: workgroup per tile on chain schedules
-        p->kernel_forced = true;
-      }
-      if (T != 1) {
-        p->variant = 0;
-        p->kernel_forced = true;
-      }
-      // two "exchange" ids (register hand-over) + wave-private LDS parking slots: two where two tiles + the leaf codes fit an
-      // eighth of the CU's 160 KiB (eight waves per CU stay resident: 61 states up to 128 taxa), else one
-      {
-        const size_t tile_bytes = (size_t)p->NW * 4 * 64 * sizeof(double), codes_bytes = (size_t)p->L * 16 * sizeof(int16_t);
-        p->n_slots_wave = 2 * tile_bytes + codes_bytes <= 20480 ? 4 : 3;
-      }
-      if (const int n = sw::slots()) p->n_slots_wave = n;
-      p->n_slots = p->variant == 1 ? p->n_slots_wave : lds_slots(T);
-    }
-    if (p->nuc) {
-      s.S_pad = (int)((s.S + 511) / 512 * 512);  // (prune_nuc2_kernel: 256 threads x 2 patterns per workgroup)
-      s.ntiles = 0;
-      s.partial_stride = (size_t)I * 4 * s.S_pad;
-    } else {
-      s.ntiles = (int)((tiles + T - 1) / T * T);
-      s.S_pad = s.ntiles * 16;
-      s.partial_stride = (size_t)I * s.ntiles * 16 * DP;
-    }
-    // HYPHY_HIP_POISON=1 (tests): fill every fresh allocation with 0xff bytes (NaN / -1), so that anything read before
-    // it is written shows up even in a process whose recycled device memory happens to hold zeros
-    const bool poison = sw::poison();
-#define A_(ptr, n)                                                                                           \
-  {                                                                                                          \
-    if (pool_malloc((void **)&(ptr), (n)) != hipSuccess) {                                                     \
-      hyphy_hip_destroy(p);                                                                                  \
-      return fail("hipMalloc failed (" #ptr ")");                                                            \
-    }                                                                                                        \
-    s.dev_bytes += (size_t)(n);                                                                              \
-    if (poison && !sw::nopoison(#ptr)) {                                                                    \
-      hipMemset((ptr), 0xff, (n));                                                                           \
-      hipDeviceSynchronize();                                                                                \
-    }                                                                                                        \
-  }
-    pool_stream_get(&s.own_stream);
-    s.stream = s.own_stream;
-    for (auto &e : s.ev) hipEventCreate(&e);
-    s.ring.assign(2 * kTimingRing, nullptr);
-    A_(s.codes, (size_t)L * s.S_pad * sizeof(int16_t));
-    if (!p->nuc) {
-      A_(s.codes_tile, (size_t)L * s.S_pad * sizeof(int16_t));
-      {  // which matrix images a branch's consumers read (ExpmArgs::need): leaves are gathered from by state — the column-gather
-         // image —, internal branches are A operands of edge products; a leaf with ambiguity codes is both
-        std::vector<unsigned char> need((size_t)B, 3);
-        for (int64_t c = 0; c < L && c < B; c++) need[(size_t)c] = p->leaf_has_ambig[(size_t)c] ? 3 : 2;
-        for (int64_t c = L; c < L + I - 1 && c < B; c++) need[(size_t)c] = 1;
-        A_(s.expm_need, (size_t)B);
-        hipMemcpy(s.expm_need, need.data(), (size_t)B, hipMemcpyHostToDevice);
-      }
-      A_(s.bc_ops, ops_capacity(p) * sizeof(int4));
-      A_(s.bc_prog, sizeof(int4));
-      A_(s.bc_slot, (size_t)C * sizeof(int32_t));
-      A_(s.bc_q, (size_t)D * D * sizeof(double));
-    }
-    A_(s.freq, (size_t)s.S_pad * sizeof(double));
-    A_(s.pin, (size_t)s.S_pad * sizeof(int16_t));
-    hipMemset(s.pin, 0, (size_t)s.S_pad * sizeof(int16_t));
-    A_(s.ambig, (size_t)std::max<int64_t>(1, n_ambig) * DP * sizeof(double));
-    // (+2 node slots per class behind the last class: outside vector of the cached branch and a scratch slot, see
-    //  hyphy_hip_branch_cache_build)
-    const size_t node_stride = p->nuc ? (size_t)4 * s.S_pad : (size_t)s.ntiles * 16 * DP;
-    A_(s.partials, ((size_t)C * s.partial_stride + 2 * C * node_stride) * sizeof(double));
-    A_(s.counts, ((size_t)C * I + 2 * C) * s.S_pad * sizeof(int32_t));
-    A_(s.site_lik, (size_t)C * s.S_pad * sizeof(double));
-    A_(s.site_cnt, (size_t)C * s.S_pad * sizeof(int32_t));
-    A_(s.mixed_lik, (size_t)s.S_pad * sizeof(double));
-    A_(s.mixed_cnt, (size_t)s.S_pad * sizeof(int32_t));
-    if (p->nuc) {
-      A_(s.Prow, (size_t)2 * C * B * 16 * sizeof(double));  // row-major, then transposed (prune_nuc2_kernel)
-    } else {
-      A_(s.Pfrag, ((size_t)C * B + (size_t)C * (I + 2) + kMaxTwin) * DP * DP * sizeof(double));  // (+ transposed path matrices of the branch cache, + twins of re-rooted schedules)
-      A_(s.pi_ones, (size_t)DP * sizeof(double));
-      {
-        std::vector<double> ones(DP, 0.);
-        for (int64_t k = 0; k < D; k++) ones[k] = 1.;
-        hipMemcpy(s.pi_ones, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice);
-      }
-      A_(s.PTg, (size_t)C * B * DP * DP * sizeof(double));
-    }
-    A_(s.qbuf, (size_t)C * B * D * D * sizeof(double));
-    A_(s.slots, (size_t)C * B * sizeof(int32_t));
-    A_(s.ops, ops_capacity(p) * sizeof(int4));
-    A_(s.prog, (size_t)(I + 2) * sizeof(int4));
-    A_(s.jn, (size_t)(I + 2) * sizeof(int4));
-    if (!p->nuc) {
-      A_(s.frag_ctr, (size_t)C * (I + 2) * s.ntiles * sizeof(int));
-      hipMemset(s.frag_ctr, 0, (size_t)C * (I + 2) * s.ntiles * sizeof(int));
-      A_(s.hand_cnt, (size_t)C * I * s.ntiles * 32 * sizeof(int32_t));
-    }
-    A_(s.pi, (size_t)DP * sizeof(double));
-    A_(s.out, 4 * sizeof(double));  // device-side result record [log-L, scaler sum, status copy, pad]
-    A_(s.status, sizeof(int32_t));  // set by the expm kernel when a matrix fails
-    A_(s.weights, (size_t)C * sizeof(double));
-    s.wg_cap = p->nuc ? (s.S_pad + 255) / 256 : s.ntiles;
-    A_(s.wg_sum, ((size_t)C * s.wg_cap + 4) * sizeof(double));  // x C: rate-class batching writes one row per class; + 4: the fused
-    A_(s.wg_cnt, ((size_t)C * s.wg_cap + 4) * sizeof(long long));  // final combine reads them with 16-byte loads
-    A_(s.wg_flag, ((size_t)C * s.wg_cap + 4) * sizeof(int));
-    hipMemset(s.wg_flag + (size_t)C * s.wg_cap, 0, 4 * sizeof(int));  // (the last word: arrival counter of the 4-state kernel's fused combine)
-#undef A_
-    s.h_small_cap = (size_t)std::max<int64_t>(std::max<int64_t>(DP, C), 64);
-    if (pool_host_malloc((void **)&s.h_ops, ops_capacity(p) * sizeof(int4)) != hipSuccess ||
-        pool_host_malloc((void **)&s.h_prog, (size_t)(I + 2) * sizeof(int4)) != hipSuccess ||
-        pool_host_malloc((void **)&s.h_jn, (size_t)(I + 2) * sizeof(int4)) != hipSuccess ||
-        pool_host_malloc((void **)&s.h_out, 4 * sizeof(double)) != hipSuccess ||
-        pool_host_malloc((void **)&s.h_slots, (size_t)C * B * sizeof(int32_t)) != hipSuccess ||
-        pool_host_malloc((void **)&s.h_small, s.h_small_cap * sizeof(double)) != hipSuccess) {
+    shard_geometry(p, s, prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256);
+    if (allocate_shard(p, s, n_ambig)) {
       hyphy_hip_destroy(p);
-      return fail("hipHostMalloc failed");
+      return -1;
     }
-    hipMemsetAsync(s.status, 0, sizeof(int32_t), s.stream);
-    if (hipHostGetDevicePointer((void **)&s.d_hout, s.h_out, 0) != hipSuccess) s.d_hout = nullptr;
-    for (int k = 0; k < 4; k++) s.h_out[k] = 0.;
-    hipMemsetAsync(s.partials, 0, (size_t)C * s.partial_stride * sizeof(double), s.stream);
-    hipMemsetAsync(s.counts, 0, (size_t)C * I * s.S_pad * sizeof(int32_t), s.stream);
-    hipMemsetAsync(s.site_lik, 0, (size_t)C * s.S_pad * sizeof(double), s.stream);
-    hipMemsetAsync(s.site_cnt, 0, (size_t)C * s.S_pad * sizeof(int32_t), s.stream);
-    // leaf table: int64 pattern-indexed -> packed int16 [L][S_pad]; padding patterns use state 0, weight 0
-    shard_codes.push_back(std::vector<int16_t>((size_t)L * s.S_pad, 0));
-    std::vector<int16_t> &codes = shard_codes.back();
-    for (int64_t l = 0; l < L; l++)
-      for (int64_t k = 0; k < s.S; k++) codes[(size_t)l * s.S_pad + k] = (int16_t)leaf_codes[l * S + src_pattern(s.s0 + k)];
-    std::vector<double> fr(s.S_pad, 0.0);
-    for (int64_t k = 0; k < s.S; k++) fr[k] = (double)pattern_freq[src_pattern(s.s0 + k)];
-    std::vector<double> amb((size_t)std::max<int64_t>(1, n_ambig) * DP, 0.0);
-    const int astride = p->nuc ? 4 : DP;
-    for (int64_t a = 0; a < n_ambig; a++)
-      for (int64_t k = 0; k < D; k++) amb[a * astride + k] = ambig[a * D + k];
-    hipMemcpy(s.codes, codes.data(), codes.size() * sizeof(int16_t), hipMemcpyHostToDevice);
-    if (!p->nuc) {  // tile-major copy [tile][L][16] for the wave-per-tile kernels: a tile's codes are one 32 L-byte run
-      std::vector<int16_t> ct((size_t)L * s.S_pad, 0);
-      for (int64_t l = 0; l < L; l++)
-        for (int64_t k = 0; k < s.S_pad; k++) ct[((size_t)(k >> 4) * L + l) * 16 + (k & 15)] = codes[(size_t)l * s.S_pad + k];
-      hipMemcpy(s.codes_tile, ct.data(), ct.size() * sizeof(int16_t), hipMemcpyHostToDevice);
-    }
-    hipMemcpy(s.freq, fr.data(), fr.size() * sizeof(double), hipMemcpyHostToDevice);
-    hipMemcpy(s.ambig, amb.data(), amb.size() * sizeof(double), hipMemcpyHostToDevice);
-    {  // (the host copy is only kept for the class computation of subtree repeats)
-      if (sw::repeats() == 0) std::vector<int16_t>().swap(shard_codes.back());
-    }
+    shard_codes.emplace_back();
+    upload_shard(p, s, in, shard_codes.back());
     if (hipStreamSynchronize(s.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
       hyphy_hip_destroy(p);
       return fail("device initialisation failed");
@@ -1445,12 +1443,8 @@ int hyphy_hip_evaluate_async(hyphy_hip_partition *p, int64_t cat, const int64_t 
     if (!q_dense) return fail("null matrix list");
     if (p->h_qstage_cap < n) {
       if (hyphy_hip_synchronize(p)) return -1;
-      if (p->h_qstage) { hipDeviceSynchronize(); pool_host_free(p->h_qstage); }
-      p->h_qstage = nullptr;
-      p->h_qstage_cap = 0;
       const size_t cap = std::max(n, (size_t)p->B * p->D * p->D);
-      HIPCHK(pool_host_malloc((void **)&p->h_qstage, cap * sizeof(double)));
-      p->h_qstage_cap = cap;
+      HIPCHK(p->own.regrow({pinned_block(p->h_qstage, cap * sizeof(double))}, p->h_qstage_cap, n, cap, FreeMode::Sync));
     }
     // (the previous asynchronous evaluation was collected or synchronised above: the staging buffer is free)
     memcpy(p->h_qstage, q_dense, n * sizeof(double));
@@ -1590,8 +1584,9 @@ int hyphy_hip_download_partials(hyphy_hip_partition *p, int64_t cat, double *ino
             for (int j = 0; j < 4; j++)
               inode_cache[(n * S + caller_pattern(p, s.s0 + k)) * 4 + j] = tmp[((size_t)n * 4 + j) * s.S_pad + k];
       } else {
+        Blocks blk;
         double *dtmp = nullptr;
-        HIPCHK(pool_malloc((void **)&dtmp, (size_t)I * s.S * D * sizeof(double)));
+        HIPCHK(blk.get(&dtmp, (size_t)I * s.S * D));
         launch_unpack_partials_mfma(s.partials + (size_t)cat * s.partial_stride, (int)I, s.ntiles, p->NW, (int)D,
                                     (int)s.S, dtmp, s.stream);
         hipError_t e;
@@ -1609,7 +1604,6 @@ int hyphy_hip_download_partials(hyphy_hip_partition *p, int64_t cat, double *ino
               memcpy(inode_cache + ((size_t)n * S + p->perm[s.s0 + k]) * D, tmp.data() + (size_t)k * D, (size_t)D * sizeof(double));
           }
         }
-        pool_free_sync(dtmp);
         if (e != hipSuccess) return fail(std::string("download_partials: ") + hipGetErrorString(e));
       }
     }
@@ -1844,9 +1838,10 @@ int hyphy_hip_expm_batch(int64_t D, int64_t n, const double *q_dense, double *p_
   double *dq = nullptr, *dp = nullptr;
   int32_t *st = nullptr;
   const size_t bytes = (size_t)n * D * D * sizeof(double);
-  HIPCHK(pool_malloc((void **)&dq, bytes));
-  HIPCHK(pool_malloc((void **)&dp, bytes));
-  HIPCHK(pool_malloc((void **)&st, sizeof(int32_t)));
+  Blocks blk;
+  HIPCHK(blk.get(&dq, (size_t)n * D * D));
+  HIPCHK(blk.get(&dp, (size_t)n * D * D));
+  HIPCHK(blk.get(&st, 1));
   HIPCHK(hipMemset(st, 0, sizeof(int32_t)));
   HIPCHK(hipMemcpy(dq, q_dense, bytes, hipMemcpyHostToDevice));
   ExpmArgs ea;
@@ -1856,7 +1851,6 @@ int hyphy_hip_expm_batch(int64_t D, int64_t n, const double *q_dense, double *p_
   int32_t hst = 0;
   hipError_t e1 = hipMemcpy(p_out, dp, bytes, hipMemcpyDeviceToHost);
   hipError_t e2 = hipMemcpy(&hst, st, sizeof(int32_t), hipMemcpyDeviceToHost);
-  pool_free_sync(dq); pool_free_sync(dp); pool_free_sync(st);
   if (e1 != hipSuccess || e2 != hipSuccess) return fail("expm_batch: device copy failed");
   if (hst) return fail("Failed to compute a valid transition matrix; this is usually caused by ill-conditioned rate "
                        "matrices (e.g. very large rate values)");
@@ -1876,18 +1870,23 @@ static std::vector<double> padded_templates(const double *templates, int64_t K, 
 int hyphy_hip_set_q_templates(hyphy_hip_partition *p, int64_t K, const double *templates) {
   if (!p || K < 1 || !templates) return fail("invalid templates");
   const int64_t D = p->D;
+  p->K = 0;  // (until every shard holds the new set)
   for (Shard &s : p->shards) {
     HIPCHK(hipSetDevice(s.device));
     HIPCHK(hipStreamSynchronize(s.stream));
-    if (s.templates) pool_free_sync(s.templates);
-    if (s.coeffs) pool_free_sync(s.coeffs);
-    s.templates = s.coeffs = nullptr;
-    HIPCHK(pool_malloc((void **)&s.templates, (size_t)K * D * D * sizeof(double)));
     // rows: one per (class, branch), or — mixtures built on the device — one per (branch, component), up to kMixRows components
     const size_t coeff_rows_cap = (size_t)std::max<int64_t>(p->C, kMixRows) * p->B;
-    HIPCHK(pool_malloc((void **)&s.coeffs, coeff_rows_cap * K * sizeof(double)));
-    if (s.h_coeffs) { hipDeviceSynchronize(); pool_host_free(s.h_coeffs); }
-    HIPCHK(pool_host_malloc((void **)&s.h_coeffs, (size_t)4 * coeff_rows_cap * K * sizeof(double)));
+    // pinned rings: four slots of coefficients (hyphy_hip_build_q), two of template images (hyphy_hip_update_q_templates: the copy of
+    // one update may still be queued when the next arrives)
+    s.tstage_slot = (size_t)K * D * D + (p->DP == 64 ? (size_t)K * 64 * 64 : 0);
+    const BlockReq blocks[] = {device_block(s.templates, (size_t)K * D * D * sizeof(double)),
+                               device_block(s.coeffs, coeff_rows_cap * K * sizeof(double)),
+                               pinned_block(s.h_coeffs, (size_t)4 * coeff_rows_cap * K * sizeof(double)),
+                               device_block(s.templates_pad, p->DP == 64 ? (size_t)K * 64 * 64 * sizeof(double) : 0),
+                               pinned_block(s.h_tstage, 2 * s.tstage_slot * sizeof(double))};
+    s.own.drop(blocks, 5, FreeMode::Sync);
+    s.d_hcoeffs = nullptr;
+    HIPCHK(s.own.get_group(blocks, 5));
     if (hipHostGetDevicePointer((void **)&s.d_hcoeffs, s.h_coeffs, 0) != hipSuccess) s.d_hcoeffs = nullptr;
     s.coeffs_cur = nullptr;
     s.coeff_rows = 0;
@@ -1899,18 +1898,10 @@ int hyphy_hip_set_q_templates(hyphy_hip_partition *p, int64_t K, const double *t
       if (!s.coeff_ev[k]) HIPCHK(hipEventCreateWithFlags(&s.coeff_ev[k], hipEventDisableTiming));
     }
     HIPCHK(hipMemcpy(s.templates, templates, (size_t)K * D * D * sizeof(double), hipMemcpyHostToDevice));
-    if (s.templates_pad) pool_free_sync(s.templates_pad);
-    s.templates_pad = nullptr;
-    if (p->DP == 64) {
-      HIPCHK(pool_malloc((void **)&s.templates_pad, (size_t)K * 64 * 64 * sizeof(double)));
+    if (s.templates_pad) {
       const std::vector<double> pad = padded_templates(templates, K, D);
       HIPCHK(hipMemcpy(s.templates_pad, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    // pinned ring for hyphy_hip_update_q_templates (two slots: the copy of one update may still be queued when the next arrives)
-    if (s.h_tstage) { hipDeviceSynchronize(); pool_host_free(s.h_tstage); }
-    s.h_tstage = nullptr;
-    s.tstage_slot = (size_t)K * D * D + (p->DP == 64 ? (size_t)K * 64 * 64 : 0);
-    HIPCHK(pool_host_malloc((void **)&s.h_tstage, 2 * s.tstage_slot * sizeof(double)));
     for (int k = 0; k < 2; k++) {
       s.tstage_busy[k] = false;
       if (!s.tstage_ev[k]) HIPCHK(hipEventCreateWithFlags(&s.tstage_ev[k], hipEventDisableTiming));
@@ -2165,11 +2156,10 @@ static int site_fits_common(hyphy_hip_partition *p, int64_t n_sets, int64_t n_gr
     HIPCHK(hipSetDevice(s.device));
     HIPCHK(hipStreamSynchronize(s.stream));
     if (!s.fit_Timg) {
-      HIPCHK(pool_malloc((void **)&s.fit_Timg, (size_t)4 * DP * DP * sizeof(double)));
-      HIPCHK(pool_malloc((void **)&s.fit_bcoef, (size_t)B * 4 * sizeof(double)));
-      HIPCHK(pool_malloc((void **)&s.fit_bgroup, (size_t)B * sizeof(int)));
-      HIPCHK(pool_malloc((void **)&s.fit_pi, (size_t)DP * sizeof(double)));
-      HIPCHK(pool_malloc((void **)&s.fit_ops, ops_capacity(p) * sizeof(int4)));
+      HIPCHK(s.own.get_group({device_block(s.fit_Timg, (size_t)4 * DP * DP * sizeof(double)), device_block(s.fit_bcoef, (size_t)B * 4 * sizeof(double)),
+                              device_block(s.fit_bgroup, (size_t)B * sizeof(int)), device_block(s.fit_pi, (size_t)DP * sizeof(double)),
+                              device_block(s.fit_ops, ops_capacity(p) * sizeof(int4))}));
+      s.fit_static_current = false;
     }
     if (!s.fit_static_current) {
       if (p->fit_ops_host.size() > ops_capacity(p)) return fail("internal: site-fit schedule overflow");
@@ -2178,33 +2168,21 @@ static int site_fits_common(hyphy_hip_partition *p, int64_t n_sets, int64_t n_gr
       s.fit_static_current = true;
     }
     const size_t need = (size_t)n_sets * std::max<size_t>(GK, 1);  // (doubles per pattern)
-    if (s.fit_sets_cap < need) {
-      if (s.fit_smult) pool_free_sync(s.fit_smult);
-      if (s.fit_out) pool_free_sync(s.fit_out);
-      s.fit_smult = s.fit_out = nullptr;
-      s.fit_sets_cap = 0;
-      if (s.fit_smix) pool_free_sync(s.fit_smix);
-      s.fit_smix = nullptr;
-      HIPCHK(pool_malloc((void **)&s.fit_smult, need * s.S_pad * sizeof(double)));
-      HIPCHK(pool_malloc((void **)&s.fit_out, need * s.S_pad * sizeof(double)));
-      HIPCHK(pool_malloc((void **)&s.fit_smix, need * s.S_pad * sizeof(double)));
-      s.fit_sets_cap = need;
-    }
+    const size_t set_bytes = need * s.S_pad * sizeof(double);
+    HIPCHK(s.own.regrow({device_block(s.fit_smult, set_bytes), device_block(s.fit_out, set_bytes), device_block(s.fit_smix, set_bytes)},
+                        s.fit_sets_cap, need, need, FreeMode::Sync));
     if (p->fit_spills && s.fit_scratch_sets < (size_t)n_sets) {
-      if (s.fit_scratch) pool_free_sync(s.fit_scratch);
-      if (s.fit_scratch_cnt) pool_free_sync(s.fit_scratch_cnt);
-      s.fit_scratch = nullptr;
-      s.fit_scratch_cnt = nullptr;
+      const BlockReq scratch[] = {device_block(s.fit_scratch, (size_t)n_sets * I * s.ntiles * TILE * sizeof(double)),
+                                  device_block(s.fit_scratch_cnt, (size_t)n_sets * I * s.S_pad * sizeof(int32_t))};
+      s.own.drop(scratch, 2, FreeMode::Sync);
       s.fit_scratch_sets = 0;
-      const size_t bytes = (size_t)n_sets * I * s.ntiles * TILE * sizeof(double);
       size_t free_b = 0, total_b = 0;
       hipMemGetInfo(&free_b, &total_b);
-      if (bytes > free_b / 2) {
+      if (scratch[0].bytes > free_b / 2) {
         g_last_error = "site fits: scratch for spilled nodes does not fit; use fewer parameter sets per call";
         return 1;
       }
-      HIPCHK(pool_malloc((void **)&s.fit_scratch, bytes));
-      HIPCHK(pool_malloc((void **)&s.fit_scratch_cnt, (size_t)n_sets * I * s.S_pad * sizeof(int32_t)));
+      HIPCHK(s.own.get_group(scratch, 2));
       s.fit_scratch_sets = (size_t)n_sets;
     }
     // site multipliers of this shard's pattern range, padded with zeros (padding sites: exp(0) = I, weightless)

@@ -244,22 +244,17 @@ int hyphy_hip_marginal_ancestral(hyphy_hip_partition *p, int64_t which, const do
     if (!s.marg_U) {  // scratch of the pass, kept until the partition is destroyed; published only when every block is there
       const size_t work = p->nuc ? (size_t)2 * maxk * 4 * s.S_pad : (size_t)s.ntiles * 2 * maxk * 16 * DP;
       const size_t wcnt = p->nuc ? (size_t)2 * maxk * s.S_pad : (size_t)s.ntiles * 2 * maxk * 16;
-      const size_t bytes[7] = {(size_t)I * node_stride * sizeof(double), (size_t)I * s.S_pad * sizeof(int32_t), work * sizeof(double),
-                               wcnt * sizeof(int32_t), prog.size() * sizeof(int4), pi_pad.size() * sizeof(double),
-                               p->nuc ? 0 : (size_t)B * DP * DP * sizeof(double)};
-      void *blk[7] = {};
-      hipError_t ae = hipSuccess;
-      for (int k = 0; k < 7 && ae == hipSuccess; k++)
-        if (bytes[k]) ae = pool_malloc(&blk[k], bytes[k]);
-      if (ae == hipSuccess) ae = hipMemcpy(blk[4], prog.data(), bytes[4], hipMemcpyHostToDevice);
-      if (ae != hipSuccess) {
-        for (void *b : blk)
-          if (b) pool_free(b);
-        return fail(std::string("marginal_ancestral: scratch: ") + hipGetErrorString(ae));
-      }
-      s.marg_U = (double *)blk[0], s.marg_Ucnt = (int32_t *)blk[1], s.marg_work = (double *)blk[2], s.marg_wcnt = (int32_t *)blk[3];
-      s.marg_prog = (int4 *)blk[4], s.marg_pi = (double *)blk[5], s.marg_PT = (double *)blk[6];
-      for (size_t b : bytes) s.dev_bytes += b;
+      const BlockReq scratch[] = {device_block(s.marg_U, (size_t)I * node_stride * sizeof(double)),
+                                  device_block(s.marg_Ucnt, (size_t)I * s.S_pad * sizeof(int32_t)),
+                                  device_block(s.marg_work, work * sizeof(double)),
+                                  device_block(s.marg_wcnt, wcnt * sizeof(int32_t)),
+                                  device_block(s.marg_prog, prog.size() * sizeof(int4)),
+                                  device_block(s.marg_pi, pi_pad.size() * sizeof(double)),
+                                  device_block(s.marg_PT, p->nuc ? 0 : (size_t)B * DP * DP * sizeof(double))};
+      hipError_t ae = s.own.get_group(scratch, 7);
+      if (ae == hipSuccess && (ae = hipMemcpy(s.marg_prog, prog.data(), prog.size() * sizeof(int4), hipMemcpyHostToDevice)) != hipSuccess)
+        s.own.drop(scratch, 7, FreeMode::NoSync);
+      if (ae != hipSuccess) return fail(std::string("marginal_ancestral: scratch: ") + hipGetErrorString(ae));
     }
     HIPCHK(hipMemcpy(s.marg_pi, pi_pad.data(), pi_pad.size() * sizeof(double), hipMemcpyHostToDevice));
     Blocks blk;  // the call's own blocks: back to the pool on every way out of this shard

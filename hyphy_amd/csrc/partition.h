@@ -3,6 +3,9 @@
 //   schedule.hip  the schedule compiler (post-order programs, chain / level-peeled cuts, re-rooting, pattern order)
 //   tuner.hip     the run-time schedule tuner and the launch of the current schedule
 //   comm.hip      RCCL (loaded on first use) and the all-reduce entry points
+// Memory: blocks.h.  Every device / pinned block a shard keeps belongs to Shard::own (a BlockOwner): the typed pointers of Shard are set
+// and nulled through it alone, free_shard releases them in one call, and hyphy_hip_schedule_info reports the device bytes it holds.
+// Blocks of one call belong to a Blocks on that call's stack.  Only blocks.h and pool.hip call the pool's allocation functions.
 // The environment is read in switches.h alone (sw::...): one table row and one accessor per HYPHY_HIP_* switch.
 // Host-side bookkeeping only — all arithmetic of the hot path happens in expm.hip / prune.hip / sitefit.hip.
 // An evaluation: an entry point fills an EvalRequest by name, eval_common validates it and settles the schedule, enqueue_eval
@@ -21,6 +24,7 @@
 #include <vector>
 
 #include "../../include/hyphy_hip.h"
+#include "blocks.h"
 #include "common.h"
 #include "switches.h"
 
@@ -29,17 +33,7 @@ namespace hyhip {
 extern thread_local std::string g_last_error;
 int fail(const std::string &msg);
 
-// Recycling allocator (pool.hip): analyses that create one likelihood function after another on the same tree (FEL: one per
-// site) allocate the same ~45 device / pinned-host blocks and a stream over and over; hipMalloc / hipHostMalloc / hipFree /
-// stream creation cost that life cycle more than its 50 evaluations.  Freed blocks go to a free list keyed by (device, size)
-// and are handed out again on an exact size match.  pool_free does NOT synchronise (hipFree does, implicitly): callers that
-// free while work may be in flight use pool_free_sync.  HYPHY_HIP_POOL_MB (default 1024; 0: off) caps the cached bytes per
-// kind; blocks above 64 MiB are never cached.
-hipError_t pool_malloc(void **p, size_t bytes);
-void pool_free(void *p);
-void pool_free_sync(void *p);
-hipError_t pool_host_malloc(void **p, size_t bytes);
-void pool_host_free(void *p);
+// Streams of destroyed partitions are recycled like their blocks (pool.hip; the blocks: blocks.h)
 hipError_t pool_stream_get(hipStream_t *s);   // a non-blocking stream of the current device
 void pool_stream_put(hipStream_t s);          // (idle: the caller has synchronised it)
 
@@ -123,6 +117,7 @@ struct RepPassSlot {
 };
 
 struct Shard {
+  BlockOwner own;                    // every device / pinned block behind the pointers below (blocks.h): allocated, regrown and freed through it alone
   int device = 0;
   hipStream_t stream = nullptr;      // stream in use
   hipStream_t own_stream = nullptr;  // stream created (and destroyed) by the library
@@ -154,13 +149,11 @@ struct Shard {
   void *comm = nullptr;       // ncclComm_t of this shard (hyphy_hip_comm_init_rank / single-process group)
   double *mix_q = nullptr, *mix_p = nullptr, *mix_w = nullptr;  // branch-site mixtures: component rate matrices, their exponentials, weights
   int *mix_off = nullptr;
-  size_t mix_cap = 0, mix_nq_cap = 0;
+  size_t mix_cap = 0;         // components they hold (mix_off: one entry per branch and one more)
   int4 *jn = nullptr;         // chain schedules: per internal node (parent, arrivals needed | child sum << 8, trunk entries offset, count)
   int4 *h_jn = nullptr;
   double *deposits = nullptr; // chain schedules: [C][view's I][ntiles][TILE] edge products of non-last arrivers (allocated on first use: ensure_deposits)
   size_t deposits_cap = 0, deposits_class_stride = 0;  // doubles
-  size_t dev_bytes = 0;       // device memory this shard holds
-  size_t rep_bytes = 0;       // ... of which class tables and their maps (repeats.hip)
   int *frag_ctr = nullptr;    // [classes][programs][tiles] arrivals of child fragments (wave-per-tile kernel)
   int32_t *hand_cnt = nullptr;  // [classes][I][tiles][32] 2^64-exponents of fragment roots (own 128-byte line each)
   double *pi = nullptr;       // [DP]
@@ -356,6 +349,7 @@ struct hyphy_hip_partition {
   bool chain = false;                        // the current schedule is a chain schedule (common.h PruneArgs::chain)
   bool kernel_forced = false;                // HYPHY_HIP_KERNEL / T > 1: the tuner must not switch kernels
   int n_slots_wave = 3;                      // LDS slot budget of the wave-per-tile kernel's schedules
+  hyhip::BlockOwner own;                     // the partition's own block (the shards' blocks: Shard::own)
   double *h_qstage = nullptr;                // pinned copy of the caller's matrices for hyphy_hip_evaluate_async
   size_t h_qstage_cap = 0;
   bool async_pending = false;                // an asynchronous evaluation has not been collected yet
@@ -405,24 +399,6 @@ inline int64_t caller_pattern(const hyphy_hip_partition *p, int64_t j) { return 
 inline int twin_slot0(const hyphy_hip_partition *p) { return (int)(p->B + (p->I + 2)); }
 
 // ---- shared by the passes over the resident conditionals (marginal.hip, trials.hip, joint.hip, sample.hip) ----------------
-// device blocks of one call: from the pool, back to it (behind a synchronisation) when the call returns, on every path
-struct Blocks {
-  std::vector<void *> held;
-  ~Blocks() { release(); }
-  void release() {
-    for (void *b : held) pool_free_sync(b);
-    held.clear();
-  }
-  template <typename T>
-  hipError_t get(T **out, size_t n) {
-    void *b = nullptr;
-    const hipError_t e = pool_malloc(&b, std::max<size_t>(1, n) * sizeof(T));
-    if (e == hipSuccess) held.push_back(b);
-    *out = (T *)b;
-    return e;
-  }
-};
-
 // what they refuse (`pre`: the entry point's name and ": "; `used`: the classes the call reads, nullptr: all)
 inline int check_unpinned(const hyphy_hip_partition *p, const std::string &pre) {
   return p->pin_node >= 0 ? fail(pre + "a node's states are pinned (clear the pin first)") : 0;
@@ -509,6 +485,7 @@ int tune_schedule(hyphy_hip_partition *p, int cat, int n_cat_batch);
 void refresh_twins(hyphy_hip_partition *p, Shard &s);
 PruneArgs base_prune_args(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch);
 int ensure_deposits(hyphy_hip_partition *p, Shard &s);
+void release_deposits(Shard &s);
 int eval_common(hyphy_hip_partition *p, const EvalRequest &request);
 int finish_pending_async(hyphy_hip_partition *p);
 int ensure_resident(hyphy_hip_partition *p, int64_t cat);  // persisted conditionals of class cat current (re-runs a persisting pass)

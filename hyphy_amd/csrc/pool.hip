@@ -1,4 +1,4 @@
-// Recycling allocator of libhyphy_hip.so (partition.h): device blocks, pinned host blocks and streams of destroyed partitions
+// Recycling allocator of libhyphy_hip.so (declared in blocks.h; streams: partition.h): device blocks, pinned host blocks and streams of destroyed partitions
 // are kept for the next partition of the same shape.  Host-side bookkeeping only.
 #include <map>
 #include <mutex>
@@ -154,6 +154,12 @@ void pool_host_free(void *p) {
     }
   }
   hipHostFree(p);
+}
+
+void pool_host_free_sync(void *p) {
+  if (!p) return;
+  hipDeviceSynchronize();  // (a kernel may still read the block through its device-side address)
+  pool_host_free(p);
 }
 
 hipError_t pool_stream_get(hipStream_t *s) {

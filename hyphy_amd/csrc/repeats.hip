@@ -1072,18 +1072,31 @@ void launch_class_tables(const RepArgs &a, int NW, hipStream_t stream, int team 
 
 namespace {
 
+// The blocks of a shard's class tables, named once: rep_upload_shard allocates and fills them, rep_release drops them (sizes unused).
+struct RepBlock {
+  BlockReq req;
+  const void *src;   // host array the block is filled from (nullptr: tables the device writes)
+  size_t src_bytes;
+};
+std::vector<RepBlock> rep_blocks(const hyphy_hip_partition *p, Shard &s, const RepShardTables &t, const std::vector<int4> &walk_prog) {
+  const size_t tab_bytes = (size_t)p->C * t.rows * (p->nuc ? 4 : p->DP) * sizeof(double), cnt_bytes = (size_t)p->C * t.rows * sizeof(int32_t);
+  const size_t sync_bytes = p->nuc ? 0 : ((size_t)kRepQueues + 1 + (size_t)p->C * t.tabs.size()) * kRepHeadStride * sizeof(int);  // (= rep_sync_words(p) words)
+  const size_t map_bytes = t.maps.size() * sizeof(int32_t), desc_bytes = t.desc.size() * sizeof(int4), ct_bytes = t.ct.size() * sizeof(int16_t),
+               lt_bytes = t.lt.size() * sizeof(int2), walk_bytes = walk_prog.size() * sizeof(int4);
+  return {{device_block(s.rep_tab, tab_bytes, "s.rep_tab"), nullptr, 0},
+          {device_block(s.rep_cnt, cnt_bytes, "s.rep_cnt"), nullptr, 0},
+          {device_block(s.rep_map, std::max(sizeof(int32_t), map_bytes), "s.rep_map"), t.maps.data(), map_bytes},
+          {device_block(s.rep_desc, desc_bytes, "s.rep_desc"), t.desc.data(), desc_bytes},
+          {device_block(s.rep_sync, sync_bytes, "s.rep_sync"), nullptr, 0},
+          {device_block(s.rep_codes_tile, ct_bytes, "s.rep_codes_tile"), t.ct.data(), ct_bytes},
+          {device_block(s.rep_leaf, lt_bytes, "s.rep_leaf"), t.lt.data(), lt_bytes},
+          {device_block(s.rep_walk, walk_bytes, "s.rep_walk"), walk_prog.data(), walk_bytes}};
+}
+
 void rep_release(hyphy_hip_partition *p) {  // everything rep_setup may have left behind: the partition runs plain
   for (Shard &s : p->shards) {
     if (hipSetDevice(s.device) != hipSuccess) continue;
-    void **bufs[] = {(void **)&s.rep_tab, (void **)&s.rep_cnt, (void **)&s.rep_map, (void **)&s.rep_desc, (void **)&s.rep_sync,
-                     (void **)&s.rep_codes_tile, (void **)&s.rep_leaf, (void **)&s.rep_walk};
-    for (void **b : bufs)
-      if (*b) {
-        pool_free_sync(*b);
-        *b = nullptr;
-      }
-    s.dev_bytes -= std::min(s.dev_bytes, s.rep_bytes);
-    s.rep_bytes = 0;
+    for (const RepBlock &b : rep_blocks(p, s, RepShardTables(), std::vector<int4>())) s.own.drop(&b.req, 1, FreeMode::Sync);
     s.rep_tabs.clear();
     s.rep_rows = 0;
   }
@@ -1125,37 +1138,25 @@ int rep_upload_shard(hyphy_hip_partition *p, Shard &s, const RepShardTables &t, 
   if (hipSetDevice(s.device) != hipSuccess) return fail("hipSetDevice failed");
   s.rep_tabs = t.tabs;
   s.rep_rows = t.rows;
-  const size_t tab_bytes = (size_t)p->C * t.rows * (p->nuc ? 4 : p->DP) * sizeof(double), cnt_bytes = (size_t)p->C * t.rows * sizeof(int32_t);
-  const size_t sync_bytes = p->nuc ? 0 : ((size_t)kRepQueues + 1 + (size_t)p->C * t.tabs.size()) * kRepHeadStride * sizeof(int);  // (= rep_sync_words(p) words)
+  const std::vector<RepBlock> blocks = rep_blocks(p, s, t, walk_prog);
+  const size_t tab_bytes = blocks[0].req.bytes, cnt_bytes = blocks[1].req.bytes;
   {
     size_t free_b = 0, total_b = 0, limit = (size_t)1 << 30;
     const size_t need_b = tab_bytes + cnt_bytes + t.maps.size() * sizeof(int32_t) + t.ct.size() * sizeof(int16_t);
     if (!sw::rep_max_mb(&limit) && hipMemGetInfo(&free_b, &total_b) == hipSuccess) limit = free_b / 4;  // (given: the caller's bound on the tables)
     if (need_b > limit) return fail("class tables would take more than a quarter of the free device memory (or than HYPHY_HIP_REP_MAX_MB)");
   }
-  struct Block { void **ptr; const char *name; size_t bytes; const void *src; size_t src_bytes; };
-  const Block blocks[] = {
-      {(void **)&s.rep_tab, "s.rep_tab", tab_bytes, nullptr, 0},
-      {(void **)&s.rep_cnt, "s.rep_cnt", cnt_bytes, nullptr, 0},
-      {(void **)&s.rep_map, "s.rep_map", std::max<size_t>(1, t.maps.size()) * sizeof(int32_t), t.maps.data(), t.maps.size() * sizeof(int32_t)},
-      {(void **)&s.rep_desc, "s.rep_desc", t.desc.size() * sizeof(int4), t.desc.data(), t.desc.size() * sizeof(int4)},
-      {(void **)&s.rep_sync, "s.rep_sync", sync_bytes, nullptr, 0},
-      {(void **)&s.rep_codes_tile, "s.rep_codes_tile", t.ct.size() * sizeof(int16_t), t.ct.data(), t.ct.size() * sizeof(int16_t)},
-      {(void **)&s.rep_leaf, "s.rep_leaf", t.lt.size() * sizeof(int2), t.lt.data(), t.lt.size() * sizeof(int2)},
-      {(void **)&s.rep_walk, "s.rep_walk", walk_prog.size() * sizeof(int4), walk_prog.data(), walk_prog.size() * sizeof(int4)}};
-  for (const Block &b : blocks) {
-    if (b.bytes == 0) continue;
-    if (pool_malloc(b.ptr, b.bytes) != hipSuccess) return fail(std::string("hipMalloc failed (") + b.name + ")");
-    s.dev_bytes += b.bytes;
-    s.rep_bytes += b.bytes;
-  }
+  std::vector<BlockReq> req;
+  for (const RepBlock &b : blocks) req.push_back(b.req);
+  const BlockReq *missing = nullptr;
+  if (s.own.get_group(req.data(), req.size(), &missing) != hipSuccess) return fail(std::string("hipMalloc failed (") + missing->name + ")");
   if (sw::poison()) {
     hipMemset(s.rep_tab, 0xff, tab_bytes);
     hipMemset(s.rep_cnt, 0xff, cnt_bytes);
   }
-  if (s.rep_sync) hipMemset(s.rep_sync, 0, sync_bytes);
-  for (const Block &b : blocks)
-    if (b.src_bytes) hipMemcpy(*b.ptr, b.src, b.src_bytes, hipMemcpyHostToDevice);
+  if (s.rep_sync) hipMemset(s.rep_sync, 0, blocks[4].req.bytes);
+  for (const RepBlock &b : blocks)
+    if (b.src_bytes) hipMemcpy(*b.req.field, b.src, b.src_bytes, hipMemcpyHostToDevice);
   s.rep_leaf_host = t.lt;
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail("repeats: device initialisation failed");
   return 0;
@@ -1563,16 +1564,8 @@ int rep_prepare_pass(hyphy_hip_partition *p, const int64_t *update_nodes, int64_
       ps.ev_recorded = false;
     }
     auto ensure = [&](size_t words, size_t cap_wanted) -> int {
-      if (words <= ps.cap) return 0;
-      if (ps.items) pool_free_sync(ps.items);
-      if (ps.h_items) pool_host_free(ps.h_items);
-      ps.items = nullptr;
-      ps.h_items = nullptr;
-      ps.cap = 0;
       const size_t cap = std::max(words, cap_wanted);
-      HIPCHK(pool_malloc((void **)&ps.items, cap * sizeof(int4)));
-      HIPCHK(pool_host_malloc((void **)&ps.h_items, cap * sizeof(int4)));
-      ps.cap = cap;
+      HIPCHK(s.own.regrow({device_block(ps.items, cap * sizeof(int4)), pinned_block(ps.h_items, cap * sizeof(int4))}, ps.cap, words, cap, FreeMode::Sync));
       return 0;
     };
     if (p->nuc) {  // 4 states: the list of subtrees to walk (no items, no queues: one thread per class, no table reads another)
@@ -1683,13 +1676,13 @@ static int rep_launch_impl(hyphy_hip_partition *p, Shard &s, int cat0) {
     const bool team_tr = s.rep_team && a.n_static > 0;
     const size_t n_rec = team_tr ? (size_t)a.n_static : (size_t)a.n_waves;
     const size_t n = n_rec * 16;
-    HIPCHK(pool_malloc((void **)&a.dbg, n * sizeof(long long)));
+    Blocks blk;
+    HIPCHK(blk.get(&a.dbg, n));
     HIPCHK(hipMemsetAsync(a.dbg, 0, n * sizeof(long long), s.stream));
     launch_class_tables(a, p->NW, s.stream, s.rep_team);
     std::vector<long long> h(n);
     HIPCHK(hipStreamSynchronize(s.stream));
     HIPCHK(hipMemcpy(h.data(), a.dbg, n * sizeof(long long), hipMemcpyDeviceToHost));
-    pool_free_sync(a.dbg);
     if (FILE *f = fopen(tl, "w")) {
       if (team_tr) fprintf(f, "# team (one workgroup of NW waves per item, class_table_team_kernel) wall_start wall_end(100MHz) walked_nodes hw_id|xcc<<32 cycles: index-maps gathers exchange product publish\n");
       else fprintf(f, "# wave wall_start wall_end(100MHz) items failed_polls cycles: tickets waiting gathers product publish\n");
@@ -1774,13 +1767,13 @@ int launch_trunk_walk(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_batch
   const char *tl = timeline ? sw::walk_timeline() : nullptr;
   if (tl && p->NW == 4) {  // diagnostic: synchronous, one record per workgroup (the lower phase's format: tools/rep_team_timeline.py)
     const size_t n = (size_t)grid.x * grid.y * grid.z * 16;
-    HIPCHK(pool_malloc((void **)&a.dbg, n * sizeof(long long)));
+    Blocks blk;
+    HIPCHK(blk.get(&a.dbg, n));
     HIPCHK(hipMemsetAsync(a.dbg, 0, n * sizeof(long long), s.stream));
     hipLaunchKernelGGL((trunk_walk_kernel<4, true>), grid, block, lds, s.stream, (const int4 *)s.rep_walk, a);
     std::vector<long long> h(n);
     HIPCHK(hipStreamSynchronize(s.stream));
     HIPCHK(hipMemcpy(h.data(), a.dbg, n * sizeof(long long), hipMemcpyDeviceToHost));
-    pool_free_sync(a.dbg);
     if (FILE *f = fopen(tl, "w")) {
       fprintf(f, "# team (one workgroup of NW waves per tile and chain, trunk_walk_kernel) wall_start wall_end(100MHz) walked_nodes hw_id|xcc<<32 cycles: leaf-table gathers exchange product epilogue\n");
       for (size_t w = 0; w < n / 16; w++) {
@@ -1901,10 +1894,7 @@ int rep_decide(hyphy_hip_partition *p, int cat, int n_classes) {
       if (sh.deposits) {
         HIPCHK(hipSetDevice(sh.device));
         HIPCHK(hipStreamSynchronize(sh.stream));
-        pool_free_sync(sh.deposits);
-        sh.dev_bytes -= sh.deposits_cap * sizeof(double);
-        sh.deposits = nullptr;
-        sh.deposits_cap = 0;
+        release_deposits(sh);
       }
   }
   return 0;

@@ -683,7 +683,8 @@ const char *hyphy_hip_schedule_info(const hyphy_hip_partition *p) {
   out = p->tune_report + buf;
   if (!p->rep_report.empty()) out += " {" + p->rep_report + "}";
   if (!p->shards.empty()) {
-    snprintf(buf, sizeof buf, " [device memory, first shard: %.1f MB]", p->shards[0].dev_bytes / 1e6);
+    const size_t held = p->shards[0].own.device_bytes();  // every device block the shard holds now, lazily allocated ones included
+    snprintf(buf, sizeof buf, " [device memory, first shard: %.1f MB = %zu bytes]", held / 1e6, held);
     out += buf;
   }
   return out.c_str();
