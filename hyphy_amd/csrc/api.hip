@@ -59,6 +59,8 @@ double next_seq(Shard &s, bool host_record) {
 
 }  // namespace
 
+double result_seq(Shard &s, bool host_record) { return next_seq(s, host_record); }
+
 // Twin images of re-rooted schedules (ExpmArgs::n_twin): slot of twin j relative to the class base, and the refresh by the
 // branch cache's transpose kernel for the cases the exponential kernel did not cover (a writer other than the fused path,
 // new root frequencies without a new matrix).
@@ -1065,6 +1067,7 @@ const char *hyphy_hip_last_reduce_form(const hyphy_hip_partition *p) {
   if (!p || !p->last_reduce.kind[0]) return "";
   static thread_local std::string out;
   const auto &f = p->last_reduce;
+  if (!strcmp(f.kind, "hmm")) return (out = p->hmm_form).c_str();  // (shard 0 ran it alone: no host sum behind it)
   out = std::string(f.kind) + (strcmp(f.kind, "site") ? " n=" : " S_pad=") + std::to_string(f.n) + (f.floor ? " floor" : "");
   if (p->shards.size() > 1) out += "; host x" + std::to_string(p->shards.size());
   return out.c_str();
@@ -1361,6 +1364,17 @@ int publish_and_collect(hyphy_hip_partition *p, const double *d_value, double *v
   return 0;
 }
 
+// A shard that takes no part in the last kernel of a synchronous call (hmm.hip: shard 0 finishes alone) still posts its record, for
+// the expm status collect_status reads.
+int post_status_record(Shard &s) {
+  HIPCHK(hipSetDevice(s.device));
+  double *rec = s.d_hout ? s.d_hout : s.out;
+  hipLaunchKernelGGL(publish_scalar_kernel, dim3(1), dim3(1), 0, s.stream, (const double *)s.out, rec, (const int *)s.status,
+                     next_seq(s, rec == s.d_hout));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 }  // namespace hyhip
 
 extern "C" {
@@ -1563,6 +1577,44 @@ int hyphy_hip_evaluate_categories_built(hyphy_hip_partition *p, const int64_t *u
                                         const int64_t *q_nodes, int64_t n_q, const double *weights,
                                         const double *root_freqs, double *logl_out) {
   return hyphy_hip_evaluate_categories_built_sites(p, update_nodes, n_update, q_nodes, n_q, weights, root_freqs, logl_out, nullptr, nullptr);
+}
+
+// The two category entry points above with the hidden-Markov combine (hmm.hip) in place of the weighted mix: the class passes are
+// queued as there, mix_and_reduce_categories is skipped altogether, and hmm_combine's last kernel posts the result record: one wait.
+int hyphy_hip_evaluate_categories_hmm(hyphy_hip_partition *p, const int64_t *update_nodes, int64_t n_update, const int64_t *q_nodes,
+                                      int64_t n_q, const double *q_dense, int q_is_probability, const double *transition,
+                                      const double *initial, const double *root_freqs, double *logl_out) {
+  if (p && !logl_out) return fail("evaluate_categories_hmm: logl_out == NULL");
+  if (const int rc = hmm_check(p, transition, initial, "evaluate_categories_hmm", false)) return rc;
+  EvalRequest rq = request_of(0, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::HostDense, rq.q = q_dense, rq.q_is_probability = q_is_probability;
+  rq.reduce = false, rq.floor_log = true;
+  if (!p->nuc) {
+    rq.batch = true;
+    if (eval_common(p, rq)) return -1;
+  } else {
+    for (int64_t c = 0; c < p->C; c++) {
+      if (!p->initialized[c]) p->cached_valid = 0;
+      rq.cat = c;
+      rq.q = q_dense ? q_dense + (size_t)c * n_q * p->D * p->D : nullptr;
+      if (eval_common(p, rq)) return -1;
+    }
+  }
+  return hmm_combine(p, transition, initial, logl_out, nullptr);
+}
+
+int hyphy_hip_evaluate_categories_built_hmm(hyphy_hip_partition *p, const int64_t *update_nodes, int64_t n_update, const int64_t *q_nodes,
+                                            int64_t n_q, const double *transition, const double *initial, const double *root_freqs,
+                                            double *logl_out) {
+  if (p && !logl_out) return fail("evaluate_categories_built_hmm: logl_out == NULL");
+  if (const int rc = hmm_check(p, transition, initial, "evaluate_categories_built_hmm", false)) return rc;
+  if (!p->K) return fail("evaluate_categories_built_hmm: templates not set");
+  if (p->nuc) return fail("evaluate_categories_built_hmm: MFMA partitions only (4-state: hyphy_hip_evaluate_categories_hmm)");
+  EvalRequest rq = request_of(0, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::OwnStaged;
+  rq.reduce = false, rq.floor_log = true, rq.batch = true;
+  if (eval_common(p, rq)) return -1;
+  return hmm_combine(p, transition, initial, logl_out, nullptr);
 }
 
 int hyphy_hip_download_partials(hyphy_hip_partition *p, int64_t cat, double *inode_cache, int64_t *scaler_counts) {

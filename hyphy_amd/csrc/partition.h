@@ -3,6 +3,7 @@
 //   schedule.hip  the schedule compiler (post-order programs, chain / level-peeled cuts, re-rooting, pattern order)
 //   tuner.hip     the run-time schedule tuner and the launch of the current schedule
 //   comm.hip      RCCL (loaded on first use) and the all-reduce entry points
+//   hmm.hip       hidden-Markov rate classes: the forward sum and the Viterbi path over the resident per-class values
 // Memory: blocks.h.  Every device / pinned block a shard keeps belongs to Shard::own (a BlockOwner): the typed pointers of Shard are set
 // and nulled through it alone, free_shard releases them in one call, and hyphy_hip_schedule_info reports the device bytes it holds.
 // Blocks of one call belong to a Blocks on that call's stack.  Only blocks.h and pool.hip call the pool's allocation functions.
@@ -246,6 +247,7 @@ struct Shard {
   double *marg_U = nullptr, *marg_work = nullptr, *marg_PT = nullptr, *marg_pi = nullptr;
   int32_t *marg_Ucnt = nullptr, *marg_wcnt = nullptr;
   int4 *marg_prog = nullptr;
+  int32_t *hmm_sites = nullptr;      // (shard 0) hidden-Markov site list: internal pattern of each site in alignment order (hmm.hip)
 };
 
 }  // namespace hyhip
@@ -390,6 +392,8 @@ struct hyphy_hip_partition {
   std::vector<int4> marg_prog;                // marginal reconstruction: pre-order program over the tree (marginal.hip), compiled once
   int marg_maxk = 0;                         // ... most children of a node
   double allreduce_ms = 0.;                  // duration of the last in-stream all-reduce (timing detail on; else 0)
+  int64_t hmm_n_sites = 0;                   // sites of the hidden-Markov site list on shard 0 (hyphy_hip_hmm_set_sites; 0: none)
+  std::string hmm_form;                      // what hyphy_hip_last_reduce_form answers while last_reduce.kind is "hmm"
 };
 
 namespace hyhip {
@@ -491,6 +495,8 @@ int finish_pending_async(hyphy_hip_partition *p);
 int ensure_resident(hyphy_hip_partition *p, int64_t cat);  // persisted conditionals of class cat current (re-runs a persisting pass)
 int collect_status(hyphy_hip_partition *p);
 int publish_and_collect(hyphy_hip_partition *p, const double *d_value, double *value_out);  // (single-shard partitions)
+int post_status_record(Shard &s);  // a shard's [.., expm status, sequence word] record behind what its stream holds, without a value of its own
+double result_seq(Shard &s, bool host_record);  // sequence number the kernel that posts the shard's result record publishes (0: wait for the stream)
 void record_timings(hyphy_hip_partition *p);
 double combine(const std::vector<double> &parts);
 // repeats.hip
@@ -512,6 +518,9 @@ size_t rep_sync_words(const hyphy_hip_partition *p);
 int rep_sync_stride();
 // marginal.hip
 std::vector<int4> plan_marginal_program(int64_t L, int64_t I, const int64_t *parents, int *maxk_out);
+// hmm.hip
+int hmm_check(const hyphy_hip_partition *p, const double *transition, const double *initial, const char *who, bool need_evaluated);
+int hmm_combine(hyphy_hip_partition *p, const double *transition, const double *initial, double *logl_out, int8_t *path_out);
 // comm.hip
 int combine_shards(hyphy_hip_partition *p, double *logl_out, bool allow_rccl = true);
 

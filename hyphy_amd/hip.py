@@ -26,6 +26,7 @@ EXPORTS = [
     "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_joint_ancestral", "hyphy_hip_sample_ancestral", "hyphy_hip_sample_uniforms", "hyphy_hip_simulate", "hyphy_hip_simulate_uniforms", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
     "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_repeat_layout", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_plan_switches", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
     "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error", "hyphy_hip_last_expm_kernel",
+    "hyphy_hip_hmm_set_sites", "hyphy_hip_hmm_logl", "hyphy_hip_hmm_viterbi", "hyphy_hip_evaluate_categories_hmm", "hyphy_hip_evaluate_categories_built_hmm", "hyphy_hip_plan_hmm", "hyphy_hip_hmm_host",
     "hyphy_hip_version",
 ]
 
@@ -193,6 +194,21 @@ def load():
     lib.hyphy_hip_last_error.restype = C.c_char_p
     lib.hyphy_hip_last_expm_kernel.restype = C.c_char_p
     lib.hyphy_hip_last_expm_kernel.argtypes = []
+    bp = C.POINTER(C.c_int8)
+    lib.hyphy_hip_hmm_set_sites.restype = C.c_int
+    lib.hyphy_hip_hmm_set_sites.argtypes = [vp, C.c_int64, lp]
+    lib.hyphy_hip_hmm_logl.restype = C.c_int
+    lib.hyphy_hip_hmm_logl.argtypes = [vp, dp, dp, dp]
+    lib.hyphy_hip_hmm_viterbi.restype = C.c_int
+    lib.hyphy_hip_hmm_viterbi.argtypes = [vp, dp, dp, bp]
+    lib.hyphy_hip_evaluate_categories_hmm.restype = C.c_int
+    lib.hyphy_hip_evaluate_categories_hmm.argtypes = [vp, lp, C.c_int64, lp, C.c_int64, dp, C.c_int, dp, dp, dp, dp]
+    lib.hyphy_hip_evaluate_categories_built_hmm.restype = C.c_int
+    lib.hyphy_hip_evaluate_categories_built_hmm.argtypes = [vp, lp, C.c_int64, lp, C.c_int64, dp, dp, dp, dp]
+    lib.hyphy_hip_plan_hmm.restype = C.c_int64
+    lib.hyphy_hip_plan_hmm.argtypes = [C.c_int64, C.c_int64, lp, C.c_int64]
+    lib.hyphy_hip_hmm_host.restype = C.c_int
+    lib.hyphy_hip_hmm_host.argtypes = [C.c_int64, C.c_int64, C.c_int64, lp, dp, lp, dp, dp, dp, bp]
     lib.hyphy_hip_version.restype = C.c_char_p
     _lib = lib
     return lib
@@ -369,6 +385,45 @@ def plan_nucgen(flat_parents, L: int, leaf_has_ambig=None, compile_it: bool = Tr
     return buf.value.decode(), bool(ok[0])
 
 
+def plan_hmm(n_sites: int, C: int) -> dict:
+    """Host-only: the launches of a hidden-Markov forward sum over ``n_sites`` sites and ``C`` classes: ``G`` (sites per segment =
+    blocks per combine), ``levels`` and ``items`` (work items of each level: (block, row) pairs, 1 for the last)."""
+    out = np.zeros(32, dtype=np.int64)
+    n = int(load().hyphy_hip_plan_hmm(int(n_sites), int(C), _l(out), len(out)))
+    if n < 0:
+        raise HipError("plan_hmm: bad arguments (1 <= n_sites < 2^31, 2 <= C <= 8)")
+    return dict(G=int(out[0]), levels=int(out[1]), items=[int(x) for x in out[2:n]])
+
+
+def _hmm_params(T, pi, C):
+    t = np.ascontiguousarray(T, dtype=np.float64)
+    f = np.ascontiguousarray(pi, dtype=np.float64)
+    if t.shape != (C, C) or f.shape != (C,):
+        raise HipError(f"hmm: transition must be [{C}, {C}] and initial [{C}]")
+    return t, f
+
+
+def hmm_host(lik, cnt, T, pi, pattern_of_site=None, logl: bool = True, path: bool = False):
+    """Host-only: the hidden-Markov forward sum / Viterbi path of ``HipPartition.hmm_logl`` / ``hmm_viterbi`` from per-class
+    per-pattern values ``lik`` [C, S] and 2^64 exponents ``cnt`` [C, S], run serially over the device's plan.  Returns log L, the
+    path (int8 [n_sites]), or both as a tuple."""
+    lk = np.ascontiguousarray(lik, dtype=np.float64)
+    cn = np.ascontiguousarray(cnt, dtype=np.int64)
+    Cc, S = lk.shape
+    if cn.shape != lk.shape:
+        raise HipError("hmm_host: lik and cnt must both be [C, S]")
+    t, f = _hmm_params(T, pi, Cc)
+    ps = None if pattern_of_site is None else np.ascontiguousarray(pattern_of_site, dtype=np.int64)
+    n = S if ps is None else len(ps)
+    out = C.c_double(0.0)
+    pth = np.zeros(n, dtype=np.int8) if path else None
+    _check(load().hyphy_hip_hmm_host(Cc, S, n, _l(ps), _d(lk), _l(cn), _d(t), _d(f), C.byref(out) if logl else None,
+                                     pth.ctypes.data_as(C.POINTER(C.c_int8)) if path else None))
+    if logl and path:
+        return out.value, pth
+    return pth if path else out.value
+
+
 def plan_switches() -> list:
     """Host-only: the library's environment switches (csrc/switches.h, docs/switches.md), one dict per row with ``name`` (without
     the HYPHY_HIP_ prefix), ``kind``, ``when`` (process | create | call), ``audience`` (integrator | diagnostic), ``default`` and
@@ -472,6 +527,7 @@ class HipPartition:
         codes = np.ascontiguousarray(leaf_codes, dtype=np.int64)
         self.S = int(codes.shape[1])
         self.C = int(C_cat)
+        self._hmm_n = 0                    # sites of the list set through hmm_set_sites (0: none)
         self.B = self.L + self.I - 1
         amb = np.ascontiguousarray(ambig, dtype=np.float64) if ambig is not None and len(ambig) else None
         freq = np.ascontiguousarray(pattern_freq, dtype=np.int64)
@@ -795,6 +851,56 @@ class HipPartition:
                                                        int(q_is_probability), _d(w), _d(rf), C.byref(out), _d(sl),
                                                        _l(sc)))
         return (out.value, sl, sc) if per_site else out.value
+
+    def hmm_set_sites(self, pattern_of_site=None):
+        """The site list of the hidden-Markov entry points: the pattern (caller's order) of each site in alignment order;
+        ``None``: site j is pattern j.  Stays on the device until replaced."""
+        ps = None if pattern_of_site is None else np.ascontiguousarray(pattern_of_site, dtype=np.int64)
+        n = self.S if ps is None else len(ps)
+        _check(self._lib.hyphy_hip_hmm_set_sites(self._h, n, _l(ps)))
+        self._hmm_n = n
+
+    def hmm_logl(self, T, pi) -> float:
+        """log L of the hidden-Markov chain over the site list from the RESIDENT per-class values (no tree work)."""
+        t, f = _hmm_params(T, pi, self.C)
+        out = C.c_double(0.0)
+        _check(self._lib.hyphy_hip_hmm_logl(self._h, _d(t), _d(f), C.byref(out)))
+        return out.value
+
+    def hmm_viterbi(self, T, pi) -> np.ndarray:
+        """The Viterbi path over the site list (int8 [n_sites]; all -1: no path of positive probability, or a NaN)."""
+        t, f = _hmm_params(T, pi, self.C)
+        if self._hmm_n <= 0:  # (the library writes n_sites bytes: the size must be known here)
+            raise HipError("hmm_viterbi: no site list set through this object's hmm_set_sites")
+        pth = np.zeros(self._hmm_n, dtype=np.int8)
+        _check(self._lib.hyphy_hip_hmm_viterbi(self._h, _d(t), _d(f), pth.ctypes.data_as(C.POINTER(C.c_int8))))
+        return pth
+
+    def evaluate_categories_hmm(self, update_nodes, q_nodes, q_dense, T, pi, root_freqs, q_is_probability: bool = False) -> float:
+        """``evaluate_categories`` with the hidden-Markov combine in place of the weighted mix: one wait."""
+        un = np.ascontiguousarray(update_nodes, dtype=np.int64)
+        qn = np.ascontiguousarray(q_nodes, dtype=np.int64)
+        q = np.ascontiguousarray(q_dense, dtype=np.float64) if len(qn) else None
+        t, f = _hmm_params(T, pi, self.C)
+        rf = np.ascontiguousarray(root_freqs, dtype=np.float64)
+        out = C.c_double(0.0)
+        _check(self._lib.hyphy_hip_evaluate_categories_hmm(self._h, _l(un), len(un), _l(qn), len(qn), _d(q), int(q_is_probability),
+                                                           _d(t), _d(f), _d(rf), C.byref(out)))
+        return out.value
+
+    def evaluate_categories_built_hmm(self, update_nodes, q_nodes, T, pi, root_freqs, coeffs: np.ndarray) -> float:
+        """``build_q`` (C*n_q coefficient rows, class-major) + ``evaluate_categories_built`` with the hidden-Markov combine."""
+        un = np.ascontiguousarray(update_nodes, dtype=np.int64)
+        qn = np.ascontiguousarray(q_nodes, dtype=np.int64)
+        t, f = _hmm_params(T, pi, self.C)
+        rf = np.ascontiguousarray(root_freqs, dtype=np.float64)
+        co = np.ascontiguousarray(coeffs, dtype=np.float64)
+        assert co.shape[0] == self.C * len(qn)
+        out = C.c_double(0.0)
+        _check(self._lib.hyphy_hip_build_q(self._h, co.shape[0], _d(co)))
+        _check(self._lib.hyphy_hip_evaluate_categories_built_hmm(self._h, _l(un), len(un), _l(qn), len(qn), _d(t), _d(f), _d(rf),
+                                                                 C.byref(out)))
+        return out.value
 
     def download_partials(self, cat: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         cache = np.zeros((self.I, self.S, self.D))

@@ -588,6 +588,69 @@ int hyphy_hip_simulate(hyphy_hip_partition *p, int64_t n_rep, int64_t n_sites,
 /* host-only, no device: the uniforms the call above would use with uniforms == NULL, out[n_rep][n_nodes][n_sites] */
 int hyphy_hip_simulate_uniforms(uint64_t seed, int64_t n_rep, int64_t n_nodes, int64_t n_sites, double *out);
 
+/* ---- Hidden-Markov rate classes --------------------------------------------------------------------------------------------------------
+ * A category variable that carries an HMM model (`--srv HMM` of BUSTED / RELAX, libv3/models/rate_variation.bf:38-74): the likelihood
+ * is a chain over the sites in alignment order instead of sum_s f_s log sum_c w_c L_{s,c}.  Replaces, over the per-class per-pattern
+ * values that stay on the device behind any evaluation of a class, _LikelihoodFunction::SumUpHiddenMarkov (likefunc2.cpp:1166-1280)
+ * and RunViterbi (likefunc2.cpp:1284-1399, what ConstructCategoryMatrix (.., SHORT) returns).
+ *   e_i[m] = l[m][s(i)] * 2^(-64 c[m][s(i)]): site i (pattern s(i) of the site list) under class m, from the resident (l, c) of class m
+ *   transition [C*C] row-major, T[k][m] = Pr(class m at a site | class k before it); initial [C]
+ * Forward sum:   L = initial^T [ prod_{i=0}^{N-2} T diag(e_i) ] e_{N-1}, the product in site order — the reference's recursion, which
+ *   reads site i < N-1 in the state AFTER its transition and the last site without one; N = 1: sum_k initial[k] e_0[k].  logl_out = log L.
+ * Viterbi path:  z_0 .. z_{N-1} maximising log(initial[z_0] e_0[z_0]) + sum_{i>=1} log(T[z_{i-1}][z_i] e_i[z_i]), exponents entering
+ *   as -64 ln2 c for every state.  Among exact ties the lowest state wins each comparison of the blocked recursion: the path is fixed
+ *   by the inputs alone.  No path of positive probability, or a NaN among the values used: every entry is -1 and the call succeeds.
+ * Deviations from the reference:
+ *   - L == 0 answers -INFINITY (the reference: -INFINITY when a step's maximum is 0, myLog's floor when only the last dot product is);
+ *   - NaN in a value a listed site uses, in transition or in initial answers NaN (forward) / all -1 (Viterbi);
+ *   - RunViterbi ADDS the exponent term for state 0 at its last step (likefunc2.cpp:1364-1368) and in its single-site branch, where
+ *     every other state subtracts it; here every state subtracts it;
+ *   - the matrix ConstructCategoryMatrix hands out is not this path but the path read through the duplicate map once more (RemapMatrix,
+ *     likefunc.cpp:1608-1649: printed[i] = path[pattern_of_site[i]]).  hyphy_hip_hmm_viterbi stands where RunViterbi stands and
+ *     returns RunViterbi's path; what the host does with it afterwards is the host's (tests/golden/hmm_*.npz hold both).
+ * Patterns no site refers to take no part, whatever their values; pattern frequencies take no part either (the site list is the
+ * reference's duplicateMap).  Row sums of `transition` are NOT checked: IsValidTransitionMatrix is the host's business.
+ * Arithmetic (hyphy_amd/csrc/hmm.h): rows of the running product carry one integer exponent each and are rescaled by exact powers of
+ * two; products of blocks align per output row on that row's largest term.  CONTRACT: a term more than 2^-900 below the largest term
+ * of the SAME row of a product is dropped — the limit for chains whose classes do not communicate (block-diagonal transition) yet
+ * trade dominance inside one row; rows of different blocks may lie arbitrarily far apart.  The class values of a site enter
+ * with their own 2^64 exponents and fall under the same contract — unlike the reference, which puts them on the smallest exponent of
+ * the site first (acquireScalerMultiplier) and so zeroes a class 17 exponents above another.
+ * The parenthesisation depends on (n_sites, C) alone (hyphy_hip_plan_hmm): two identical calls give identical bits, whatever
+ * HYPHY_HIP_TUNE says.  Host and device results are NOT bit-identical (-ffp-contract=fast contracts differently on the two sides).
+ * Returns: 0; 1 "use the CPU path" for C == 1 or C > 8; < 0 (hyphy_hip_last_error): a NULL argument, a negative or infinite entry of
+ * transition / initial, no site list, an active pin (hyphy_hip_set_pinned_states), a class that has never been evaluated.
+ * The calls leave no state behind: matrices, images, schedules, tuner state, class tables, branch-cache slots, lazy-persistence flags,
+ * the mixed per-pattern values, the cached weights and hyphy_hip_last_expm_kernel are what they were; scratch comes from the pool and
+ * is back before the call returns.  A multi-shard partition brings every shard's values to shard 0 by device-to-device copies behind
+ * events on the shards' streams and runs there.  hyphy_hip_last_reduce_form answers "hmm sites=<n> segments=<k> levels=<d>" (the host
+ * takes no part: nothing is appended for a multi-shard partition). */
+/* The site list: pattern of each site in alignment order, caller's pattern order, 1 <= n_sites <= 2^31-1, every index validated;
+ * NULL: site j = pattern j, n_sites == S.  Kept on the device with the partition until replaced or the partition is destroyed. */
+int hyphy_hip_hmm_set_sites(hyphy_hip_partition *p, int64_t n_sites, const int64_t *pattern_of_site);
+/* From the RESIDENT per-class per-pattern values (the last evaluation of each class, by any entry point): no tree work at all — the
+ * call a line search on the switching rate makes.  One wait, through the host-mapped result record. */
+int hyphy_hip_hmm_logl(hyphy_hip_partition *p, const double *transition /* [C*C] */, const double *initial /* [C] */, double *logl_out);
+int hyphy_hip_hmm_viterbi(hyphy_hip_partition *p, const double *transition, const double *initial, int8_t *path_out /* [n_sites] */);
+/* hyphy_hip_evaluate_categories / hyphy_hip_evaluate_categories_built with the hidden-Markov combine in place of the weighted mix
+ * (which is skipped altogether: no category floor, no mixed values): ONE wait per call. */
+int hyphy_hip_evaluate_categories_hmm(hyphy_hip_partition *p, const int64_t *update_nodes, int64_t n_update, const int64_t *q_nodes,
+                                      int64_t n_q, const double *q_dense, int q_is_probability, const double *transition,
+                                      const double *initial, const double *root_freqs, double *logl_out);
+int hyphy_hip_evaluate_categories_built_hmm(hyphy_hip_partition *p, const int64_t *update_nodes, int64_t n_update, const int64_t *q_nodes,
+                                            int64_t n_q, const double *transition, const double *initial, const double *root_freqs,
+                                            double *logl_out);
+/* host-only, no device: the launches of a forward sum.  out[0] = G (sites per segment = blocks per combine, a compile-time constant),
+ * out[1] = levels, out[2 .. 2+levels) = work items of each level: (segment, row) pairs — segment j holds the factors
+ * [jG, min((j+1)G, n_sites-1)) —, then (block of G blocks, row) pairs while more than G blocks are left, then 1.  Returns the entries
+ * needed (at most `cap` are written), -1: bad arguments. */
+int64_t hyphy_hip_plan_hmm(int64_t n_sites, int64_t C, int64_t *out, int64_t cap);
+/* host-only, no device: the same plan and the same block algebra run serially over values the caller holds (pattern_of_site NULL:
+ * site j = pattern j, n_sites == S); what a host without the device entry points computes, at C speed. */
+int hyphy_hip_hmm_host(int64_t C, int64_t S, int64_t n_sites, const int64_t *pattern_of_site, const double *lik /* [C][S] */,
+                       const int64_t *cnt /* [C][S] */, const double *transition, const double *initial,
+                       double *logl_out /* or NULL */, int8_t *path_out /* or NULL */);
+
 /* ---- branch cache ---------------------------------------------------------------------
  * Replaces _TheTree::ComputeBranchCache (src/core/tree_evaluator.cpp:4286-4845) and
  * _TheTree::ComputeLLWithBranchCache (src/core/tree.cpp:3383-3936), driven by the policy code of
@@ -639,6 +702,8 @@ const char *hyphy_hip_last_prune_form(const hyphy_hip_partition *p);
  *   "block n=<partials>"          wg_reduce_kernel (HYPHY_HIP_REDUCE=block)
  *   "site S_pad=<padded patterns>[ floor]"  site_reduce_kernel over the stored per-pattern values (an evaluation that recomputed
  *                                 nothing; " floor": behind the category mix, with the category floor)
+ *   "hmm sites=<n> segments=<k> levels=<d>"  the hidden-Markov combine (hyphy_hip_hmm_logl / _viterbi and the two fused entry points):
+ *                                 the plan of hyphy_hip_plan_hmm; shard 0 runs it alone, so nothing follows for a multi-shard partition
  * "" before the first evaluation.  A multi-shard partition reports shard 0, followed by "; host x<shards>" (the shard records meet in
  * the host's compensated sum).  Valid until the calling thread's next call of this function. */
 const char *hyphy_hip_last_reduce_form(const hyphy_hip_partition *p);
