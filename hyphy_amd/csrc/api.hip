@@ -147,6 +147,9 @@ PruneArgs base_prune_args(hyphy_hip_partition *p, Shard &s, int cat, int n_cat_b
 
 namespace {
 
+// Pinned staging of the class-batched mixture entry points (Shard::h_mixst): [C class weights | B + 1 offsets (int) | mixture weights]
+size_t mixst_weights_at(const hyphy_hip_partition *p) { return (size_t)p->C + ((size_t)p->B + 2) / 2; }
+
 // ---- one evaluation on one shard: enqueue_eval runs the stages below, in this order, over one context on its stack ----
 struct Timeline;
 struct EvalCtx {
@@ -171,6 +174,7 @@ struct EvalCtx {
   int enqueue_eval();
   int stage_schedule(), stage_pi(), stage_slot_table(), stage_expm_mixture(), stage_expm_plain(), stage_stamps_open(), stage_prune_nuc(),
       stage_prune_mfma(), stage_stamps_close(), stage_export(), stage_reduce();
+  int stage_expm_class_mixture(bool mix_built);
   void stage_gen_decision();
   ExpmArgs expm_args_common(bool built) const;
   int guard_coeff_slot();
@@ -267,21 +271,32 @@ int EvalCtx::stage_expm_mixture() {
   const int64_t D = p->D, B = p->B, n_q = rq.n_q;
   const int DP = p->DP;
   const bool mix_built = q_on_device() && dense_q() == s.qbuf && p->coeffs_pending;
-  if ((q_on_device() && !mix_built) || rq.q_is_probability || n_cat_batch != 1)
-    return fail("mixture evaluation: host rate matrices or hyphy_hip_build_q rows, one class at a time");
-  const size_t n_tot = (size_t)rq.mix->n_tot, DD = (size_t)D * D;
-  if (mix_built && s.coeff_rows != (int64_t)n_tot)
+  if ((q_on_device() && !mix_built) || rq.q_is_probability || (n_cat_batch != 1 && !rq.batch))
+    return fail("mixture evaluation: host rate matrices or hyphy_hip_build_q rows");
+  // a class batch: the components of ALL classes in one exponential launch, class-major (component (c, k, m) at c * n_tot + off[k] + m)
+  const size_t n_tot = (size_t)rq.mix->n_tot, n_all = n_tot * (size_t)(rq.batch ? n_cat_batch : 1), DD = (size_t)D * D;
+  if (mix_built && s.coeff_rows != (int64_t)n_all)
     return fail("mixture evaluation: hyphy_hip_build_q staged a different number of rows than the components of this evaluation");
   // (rows are staged without saying what they are: the first evaluation that consumes a staging claims it — one row per (branch,
-  //  component) here — and an evaluation of the other kind that happens to need the same number of rows is refused)
+  //  component) here, per (class, branch, component) in a class batch — and an evaluation of another kind that happens to need the
+  //  same number of rows is refused)
+  const int kind = rq.batch ? 3 : 2;
   if (mix_built && s.coeff_kind == 1) return fail("mixture evaluation: the staged rows were consumed as one row per (class, branch): call hyphy_hip_build_q first");
-  if (mix_built) s.coeff_kind = 2;
-  {  // (n_q <= B: eval_common has checked)
-    const size_t cap = std::max(n_tot, (size_t)(2 * B));
-    HIPCHK(s.own.regrow({device_block(s.mix_q, cap * DD * sizeof(double)), device_block(s.mix_p, cap * DD * sizeof(double)),
-                         device_block(s.mix_w, cap * sizeof(double)), device_block(s.mix_off, ((size_t)B + 1) * sizeof(int))},
-                        s.mix_cap, n_tot, cap, FreeMode::Sync));
+  if (mix_built && s.coeff_kind != 0 && s.coeff_kind != kind)
+    return fail(kind == 3 ? "mixture evaluation: the staged rows were consumed as one row per (branch, component) of one class: call hyphy_hip_build_q first"
+                          : "mixture evaluation: the staged rows were consumed as one row per (class, branch, component): call hyphy_hip_build_q first");
+  if (mix_built) s.coeff_kind = kind;
+  {  // (n_q <= B: eval_common has checked); the rate matrices' block only where dense matrices arrive
+    const size_t cap = std::max(n_all, (size_t)(2 * B));
+    if (s.mix_cap < n_all) s.mix_counts_dev.clear();  // (mix_off moves with its group)
+    HIPCHK(s.own.regrow({device_block(s.mix_p, cap * DD * sizeof(double)), device_block(s.mix_w, cap * sizeof(double)),
+                         device_block(s.mix_off, ((size_t)B + 1) * sizeof(int))},
+                        s.mix_cap, n_all, cap, FreeMode::Sync));
+    if (!mix_built || !rq.batch)  // (one-class calls keep the allocations they always made)
+      HIPCHK(s.own.regrow({device_block(s.mix_q, cap * DD * sizeof(double))}, s.mix_q_cap, n_all, cap, FreeMode::Sync));
   }
+  if (rq.batch) return stage_expm_class_mixture(mix_built);
+  s.mix_counts_dev.clear();  // (the offsets of this call replace a class batch's)
   std::vector<int> off((size_t)n_q + 1, 0);
   for (int64_t k = 0; k < n_q; k++) off[k + 1] = off[k] + (int)rq.mix->count[k];
   if (!mix_built) HIPCHK(hipMemcpyAsync(s.mix_q, dense_q(), n_tot * DD * sizeof(double), hipMemcpyHostToDevice, s.stream));
@@ -300,6 +315,41 @@ int EvalCtx::stage_expm_mixture() {
   return 0;
 }
 
+// ... of a class batch (stage_expm_mixture has sized the device blocks and claimed the rows): ONE exponential launch over the C * n_tot
+// components, then mix_class_images_kernel with a grid row per class.  Weights and offsets travel through the pinned staging the entry
+// point prepared (prepare_class_mixture_staging), in-stream: with rows staged by hyphy_hip_build_q nothing here waits for the stream;
+// the offsets are uploaded only when the counts or the list changed.  Dense matrices come from pageable memory: one wait.
+int EvalCtx::stage_expm_class_mixture(bool mix_built) {
+  const int64_t D = p->D, B = p->B, n_q = rq.n_q;
+  const int DP = p->DP;
+  const size_t n_tot = (size_t)rq.mix->n_tot, n_all = n_tot * (size_t)n_cat_batch, DD = (size_t)D * D;
+  if (!s.h_mixst || s.mixst_cap < n_all) return fail("internal: the class-mixture staging was not prepared");
+  int *h_off = reinterpret_cast<int *>(s.h_mixst + p->C);
+  double *h_w = s.h_mixst + mixst_weights_at(p);
+  s.mixst_inflight = true;
+  const std::vector<int64_t> &known = s.mix_counts_dev;
+  if (slots_changed || known.size() != (size_t)n_q || memcmp(known.data(), rq.mix->count, (size_t)n_q * sizeof(int64_t))) {
+    h_off[0] = 0;
+    for (int64_t k = 0; k < n_q; k++) h_off[k + 1] = h_off[k] + (int)rq.mix->count[k];
+    HIPCHK(hipMemcpyAsync(s.mix_off, h_off, ((size_t)n_q + 1) * sizeof(int), hipMemcpyHostToDevice, s.stream));
+    s.mix_counts_dev.assign(rq.mix->count, rq.mix->count + n_q);
+  }
+  memcpy(h_w, rq.mix->weights, n_all * sizeof(double));
+  HIPCHK(hipMemcpyAsync(s.mix_w, h_w, n_all * sizeof(double), hipMemcpyHostToDevice, s.stream));
+  if (!mix_built) {
+    HIPCHK(hipMemcpyAsync(s.mix_q, dense_q(), n_all * DD * sizeof(double), hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipStreamSynchronize(s.stream));  // (pageable source)
+  }
+  ExpmArgs ea = expm_args_common(mix_built);
+  ea.Q = s.mix_q, ea.n = (int)n_all, ea.Prow = s.mix_p;
+  const bool coeffs_consumed = launch_expm(ea, s.stream);
+  if (mix_built && !coeffs_consumed && guard_coeff_slot()) return -1;
+  s.twins_dirty = true;  // (the mixing kernel writes matrix images without their twins)
+  launch_mix_class_images(s.mix_p, s.mix_off, s.mix_w, d_slots(), (int)n_q, n_cat_batch, (int)n_tot, (int)D,
+                          s.Pfrag + (size_t)cat * B * DP * DP, s.PTg + (size_t)cat * B * DP * DP, s.stream);
+  return 0;
+}
+
 int EvalCtx::stage_expm_plain() {
   const int64_t D = p->D, B = p->B, n_q = rq.n_q, n_mat = n_q * n_cat_batch;
   const int DP = p->DP, q_is_prob = rq.q_is_probability;
@@ -311,7 +361,7 @@ int EvalCtx::stage_expm_plain() {
     // (fused construction) or the materialised matrices, with exactly the rows this evaluation consumes
     if (!q_from_templates && !s.qbuf_built) return fail("evaluate from the Q buffer: no rate matrices staged (call hyphy_hip_build_q first)");
     if (s.coeff_rows != n_mat) return fail("evaluate from the Q buffer: hyphy_hip_build_q staged a different number of matrices than this evaluation consumes");
-    if (s.coeff_kind == 2) return fail("evaluate from the Q buffer: the staged rows were consumed as mixture components: call hyphy_hip_build_q first");
+    if (s.coeff_kind >= 2) return fail("evaluate from the Q buffer: the staged rows were consumed as mixture components: call hyphy_hip_build_q first");
     s.coeff_kind = 1;
   }
   if (!q_on_device()) {
@@ -760,12 +810,18 @@ int result_tail(hyphy_hip_partition *p, int cat, TailCombine comb, TailTimings t
 }
 
 // Category mode behind the per-class passes: weights to the device (`always`, or when they changed), mix the classes, reduce the mix
-int mix_and_reduce_categories(hyphy_hip_partition *p, const double *weights, bool always) {
+// (`staged`: the weights sit at the head of every shard's pinned class-mixture staging — prepare_class_mixture_staging — and are
+//  copied from there in-stream at every call, without a wait)
+int mix_and_reduce_categories(hyphy_hip_partition *p, const double *weights, bool always, bool staged = false) {
   const bool w_changed = always || p->cached_weights.size() != (size_t)p->C || memcmp(p->cached_weights.data(), weights, p->C * sizeof(double));
   if (w_changed) p->cached_weights.assign(weights, weights + p->C);
+  if (staged) p->cached_weights.clear();  // (known again once every shard's copy is queued)
   for (Shard &s : p->shards) {
     HIPCHK(hipSetDevice(s.device));
-    if (w_changed && upload_small(s, weights, (size_t)p->C, s.weights)) {
+    if (staged) {
+      s.mixst_inflight = true;
+      HIPCHK(hipMemcpyAsync(s.weights, s.h_mixst, (size_t)p->C * sizeof(double), hipMemcpyHostToDevice, s.stream));
+    } else if (w_changed && upload_small(s, weights, (size_t)p->C, s.weights)) {
       if (!always) p->cached_weights.clear();  // (the always-uploading entry point never cleared the cache on this path: kept)
       return -1;
     }
@@ -774,7 +830,31 @@ int mix_and_reduce_categories(hyphy_hip_partition *p, const double *weights, boo
     launch_site_reduce(s.mixed_lik, s.mixed_cnt, s.freq, s.S_pad, 1, rec, rec + 1, s.status, s.stream, next_seq(s, rec == s.d_hout));
     if (&s == &p->shards[0]) p->last_reduce = {"site", s.S_pad, true};
   }
+  if (staged) p->cached_weights.assign(weights, weights + p->C);
   return 0;
+}
+
+// The pinned staging of a class-batched mixture call on every shard, for `n_w` mixture weights, with the class weights at its head.
+// A copy out of it can still be queued only behind a call that failed before its wait: then, and when the block grows, the stream is
+// waited for; in steady state nothing here waits.
+int prepare_class_mixture_staging(hyphy_hip_partition *p, size_t n_w, const double *class_weights) {
+  for (Shard &s : p->shards) {
+    HIPCHK(hipSetDevice(s.device));
+    if (s.mixst_inflight) {
+      HIPCHK(hipStreamSynchronize(s.stream));
+      s.mixst_inflight = false;
+    }
+    if (!s.h_mixst || s.mixst_cap < n_w) {
+      const size_t cap = std::max(n_w, (size_t)(2 * p->B));
+      s.mix_counts_dev.clear();
+      HIPCHK(s.own.regrow({pinned_block(s.h_mixst, (mixst_weights_at(p) + cap) * sizeof(double))}, s.mixst_cap, n_w + 1, cap, FreeMode::Sync));
+    }
+    memcpy(s.h_mixst, class_weights, (size_t)p->C * sizeof(double));
+  }
+  return 0;
+}
+void class_mixture_staging_done(hyphy_hip_partition *p) {  // (behind the wait for every shard's result record)
+  for (Shard &s : p->shards) s.mixst_inflight = false;
 }
 
 // ---- hyphy_hip_create, step by step --------------------------------------------------------------------------------------------
@@ -1579,6 +1659,73 @@ int hyphy_hip_evaluate_categories_built(hyphy_hip_partition *p, const int64_t *u
   return hyphy_hip_evaluate_categories_built_sites(p, update_nodes, n_update, q_nodes, n_q, weights, root_freqs, logl_out, nullptr, nullptr);
 }
 
+}  // extern "C"
+
+// the two class-batched mixture entry points from the component counts onwards (`rq`: the lists and the matrix source)
+static int evaluate_categories_mixture_common(hyphy_hip_partition *p, EvalRequest rq, const int64_t *n_components, const double *mix_weights,
+                                              const double *class_weights, double *logl_out, double *site_lik_out, int64_t *site_scaler_out) {
+  MixSpec mix{n_components, mix_weights, 0};
+  for (int64_t k = 0; k < rq.n_q; k++) {
+    if (n_components[k] < 1 || n_components[k] > kMixRows) return fail("mixture evaluation: 1..16 components per branch");
+    mix.n_tot += n_components[k];
+  }
+  rq.reduce = false, rq.floor_log = true;  // (the per-pattern values of every class, floored: mixed and reduced below)
+  if (p->nuc) {  // 4 states: the classes one after another through the one-class staging, as hyphy_hip_evaluate_categories does
+    const double *q = rq.q;
+    for (int64_t c = 0; c < p->C; c++) {
+      if (!p->initialized[c]) p->cached_valid = 0;
+      MixSpec one{n_components, mix_weights ? mix_weights + (size_t)c * mix.n_tot : nullptr, mix.n_tot};
+      rq.cat = c;
+      rq.q = q ? q + (size_t)c * mix.n_tot * p->D * p->D : nullptr;
+      rq.mix = rq.n_q > 0 ? &one : nullptr;
+      if (eval_common(p, rq)) return -1;
+    }
+    if (mix_and_reduce_categories(p, class_weights, /* always = */ true)) return -1;
+    return result_tail(p, 0, kCombineHost, kNoTimings, kSitesGatheredMixed, logl_out, site_lik_out, site_scaler_out);
+  }
+  rq.batch = true;
+  rq.mix = rq.n_q > 0 ? &mix : nullptr;
+  if (prepare_class_mixture_staging(p, (size_t)p->C * mix.n_tot, class_weights)) return -1;
+  if (eval_common(p, rq)) return -1;
+  if (mix_and_reduce_categories(p, class_weights, /* always = */ false, /* staged = */ true)) return -1;
+  if (result_tail(p, 0, kCombineHost, kNoTimings, kSitesGatheredMixed, logl_out, site_lik_out, site_scaler_out)) return -1;
+  class_mixture_staging_done(p);
+  return 0;
+}
+
+extern "C" {
+
+/* Rate classes over branch-site mixtures in one batched evaluation (include/hyphy_hip.h): class c evolves on branch q_nodes[k] under
+ * P = sum_m mix_weights[c][.] exp(Q[c][.]); ONE exponential launch over the C * n_tot components, mix_class_images_kernel with a grid
+ * row per class, one pruning launch with a grid row per class, and the class mix of hyphy_hip_evaluate_categories. */
+int hyphy_hip_evaluate_categories_mixture(hyphy_hip_partition *p, const int64_t *update_nodes, int64_t n_update, const int64_t *q_nodes,
+                                          int64_t n_q, const int64_t *n_components, const double *q_dense, const double *mix_weights,
+                                          const double *class_weights, const double *root_freqs, double *logl_out,
+                                          double *site_lik_out, int64_t *site_scaler_out) {
+  if (!p) return fail("partition == NULL");
+  if (!class_weights) return fail("class_weights == NULL");
+  if (n_q > 0 && (!n_components || !mix_weights || !q_dense)) return fail("mixture evaluation: null argument");
+  EvalRequest rq = request_of(0, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::HostDense, rq.q = n_q > 0 ? q_dense : nullptr;
+  return evaluate_categories_mixture_common(p, rq, n_components, mix_weights, class_weights, logl_out, site_lik_out, site_scaler_out);
+}
+
+/* The same from rows staged by hyphy_hip_build_q: C * n_tot rows, one per (class, branch, component) in that order.  In steady
+ * state the host waits once, for the result record. */
+int hyphy_hip_evaluate_categories_mixture_built(hyphy_hip_partition *p, const int64_t *update_nodes, int64_t n_update,
+                                                const int64_t *q_nodes, int64_t n_q, const int64_t *n_components,
+                                                const double *mix_weights, const double *class_weights, const double *root_freqs,
+                                                double *logl_out, double *site_lik_out, int64_t *site_scaler_out) {
+  if (!p) return fail("partition == NULL");
+  if (!p->K) return fail("evaluate_categories_mixture_built: templates not set");
+  if (p->nuc) return fail("evaluate_categories_mixture_built: MFMA partitions only (4-state: hyphy_hip_evaluate_categories_mixture)");
+  if (!class_weights) return fail("class_weights == NULL");
+  if (n_q > 0 && (!n_components || !mix_weights)) return fail("mixture evaluation: null argument");
+  EvalRequest rq = request_of(0, UpdateList{update_nodes, n_update}, MatrixList{q_nodes, n_q}, root_freqs);
+  rq.q_source = QSource::OwnStaged;
+  return evaluate_categories_mixture_common(p, rq, n_components, mix_weights, class_weights, logl_out, site_lik_out, site_scaler_out);
+}
+
 // The two category entry points above with the hidden-Markov combine (hmm.hip) in place of the weighted mix: the class passes are
 // queued as there, mix_and_reduce_categories is skipped altogether, and hmm_combine's last kernel posts the result record: one wait.
 int hyphy_hip_evaluate_categories_hmm(hyphy_hip_partition *p, const int64_t *update_nodes, int64_t n_update, const int64_t *q_nodes,
@@ -1938,7 +2085,9 @@ int hyphy_hip_set_q_templates(hyphy_hip_partition *p, int64_t K, const double *t
                                pinned_block(s.h_tstage, 2 * s.tstage_slot * sizeof(double))};
     s.own.drop(blocks, 5, FreeMode::Sync);
     s.d_hcoeffs = nullptr;
+    s.coeff_rows_cap = 0;
     HIPCHK(s.own.get_group(blocks, 5));
+    s.coeff_rows_cap = coeff_rows_cap;  // (grown on demand by hyphy_hip_build_q: rows per (class, branch, component))
     if (hipHostGetDevicePointer((void **)&s.d_hcoeffs, s.h_coeffs, 0) != hipSuccess) s.d_hcoeffs = nullptr;
     s.coeffs_cur = nullptr;
     s.coeff_rows = 0;
@@ -2008,7 +2157,7 @@ int hyphy_hip_update_q_templates(hyphy_hip_partition *p, int64_t K, const double
 
 int hyphy_hip_build_q(hyphy_hip_partition *p, int64_t n, const double *coeffs) {
   if (!p || !p->K) return fail("build_q: templates not set");
-  if (n < 0 || n > std::max<int64_t>(p->C, kMixRows) * p->B || !coeffs) return fail("build_q: bad arguments");
+  if (n < 0 || n > kMixRows * p->C * p->B || !coeffs) return fail("build_q: bad arguments");  // (most: a row per (class, branch, component))
   Trace tr("build_q");
   // When the matrices are consumed by the next hyphy_hip_evaluate_device(q_buffer) — the normal use —
   // the construction is fused into the expm kernel (no Q round trip through HBM, one launch less).
@@ -2017,12 +2166,23 @@ int hyphy_hip_build_q(hyphy_hip_partition *p, int64_t n, const double *coeffs) {
   for (Shard &s : p->shards) {
     HIPCHK(hipSetDevice(s.device));
     const size_t nbytes = (size_t)n * p->K * sizeof(double);
+    if ((size_t)n > s.coeff_rows_cap) {
+      // more rows than hyphy_hip_set_q_templates sized the ring for (a class batch of mixtures, C > 1): the ring and the device copy
+      // grow, behind a wait for whatever may still read them; a partition that never stages so many keeps what it had
+      HIPCHK(hipStreamSynchronize(s.stream));
+      const size_t cap = (size_t)n;
+      s.d_hcoeffs = nullptr, s.coeffs_cur = nullptr, s.coeff_slot = -1;
+      for (int k = 0; k < 4; k++) s.coeff_busy[k] = false;
+      HIPCHK(s.own.regrow({device_block(s.coeffs, cap * p->K * sizeof(double)), pinned_block(s.h_coeffs, (size_t)4 * cap * p->K * sizeof(double))},
+                          s.coeff_rows_cap, (size_t)n, cap, FreeMode::Sync));
+      if (hipHostGetDevicePointer((void **)&s.d_hcoeffs, s.h_coeffs, 0) != hipSuccess) s.d_hcoeffs = nullptr;
+    }
     const int slot = (int)(s.coeff_turn++ & 3);  // pinned ring of 4
     if (s.coeff_busy[slot]) {  // a queued expm launch may still read this slot
       HIPCHK(hipEventSynchronize(s.coeff_ev[slot]));
       s.coeff_busy[slot] = false;
     }
-    double *stage = s.h_coeffs + (size_t)slot * (size_t)std::max<int64_t>(p->C, kMixRows) * p->B * p->K;
+    double *stage = s.h_coeffs + (size_t)slot * s.coeff_rows_cap * p->K;
     memcpy(stage, coeffs, nbytes);
     s.coeff_slot = slot;
     s.coeff_rows = n;

@@ -340,6 +340,9 @@ const char *last_expm_kernel();                 // the kernel the calling thread
 void set_last_expm_kernel(const char *name);    // ("" when the exponentials are folded into a pruning launch)
 void launch_mix_images(const double *P, const int *off, const double *w, const int32_t *slots, int n, int D, double *Pfrag,
                        double *PTg, double *Prow, hipStream_t stream, double *PTrow = nullptr);
+// ... of a class batch: grid (n_list, n_classes), component (c, k, m) at c * n_tot + off[k] + m, slot slots[c * n_list + k] (MFMA images only)
+void launch_mix_class_images(const double *P, const int *off, const double *w, const int32_t *slots, int n_list, int n_classes, int n_tot,
+                             int D, double *Pfrag, double *PTg, hipStream_t stream);
 void launch_site_fit(const SiteFitArgs &a, hipStream_t stream);
 int launch_prune_mfma(const PruneArgs &a, hipStream_t stream);  // -1: no instantiation serves this launch form (nothing launched)
 // the instantiation the calling thread's last launch_prune_mfma dispatched, as its launcher recorded it (hyphy_hip_last_prune_form)

@@ -1060,7 +1060,56 @@ __global__ __launch_bounds__(256) void mix_images_kernel(const double *__restric
   }
 }
 
+// The same mix for a class batch (hyphy_hip_evaluate_categories_mixture): grid (branch of the list, class).  Component (c, k, m) is
+// matrix c * n_tot + off[k] + m of P and of w; the images go to slot slots[c * n_list + k] (= c * B + branch) behind class 0's.  The
+// workgroup forms the weighted sum ONCE, reading each row-major component coalesced, in ascending component order with the
+// expression mix_images_kernel uses (same rounding), into a DP x (DP + 1) tile in LDS whose padded states are exact zeros; both images
+// are then written from the tile in their own index order, coalesced.  Reads of the tile (ds_read_b64, bank = (a / 4) mod 64, two
+// groups of 32 lanes): the column-gather image takes one column at 16 NT rows, stride DP + 1 doubles: odd, every lane of a group on a
+// bank pair of its own; the A-operand image takes 16 rows x columns {c, c + 4}: 2-way, never a single bank.
+__global__ __launch_bounds__(256) void mix_class_images_kernel(const double *__restrict__ P, const int *__restrict__ off,
+                                                               const double *__restrict__ w, const int32_t *__restrict__ slots,
+                                                               int n_tot, int D, int NT, double *__restrict__ Pfrag,
+                                                               double *__restrict__ PTg) {
+  extern __shared__ double mix_tile[];  // [DP][DP + 1]
+  const int k = blockIdx.x, c = blockIdx.y, n_list = gridDim.x;
+  const int m0 = c * n_tot + off[k], m1 = c * n_tot + off[k + 1], slot = slots[c * n_list + k];
+  const int DP = 16 * NT, LD = DP + 1, NKK = DP / 4, DD = D * D;
+  for (int idx = threadIdx.x; idx < DP * DP; idx += blockDim.x) {
+    const int rr = idx / DP, cc = idx - rr * DP;
+    double v = 0.;
+    if (rr < D && cc < D)
+      for (int m = m0; m < m1; m++) v += w[m] * P[(size_t)m * DD + rr * D + cc];
+    mix_tile[rr * LD + cc] = v;
+  }
+  __syncthreads();
+  {  // wave wb, k-step kk, lane l  <-  P[16 wb + (l & 15)][4 kk + (l >> 4)]
+    double *out = Pfrag + (size_t)slot * DP * DP;
+    for (int idx = threadIdx.x; idx < DP * DP; idx += blockDim.x) {
+      const int wb = idx / (NKK * 64), rem = idx - wb * (NKK * 64);
+      const int kk2 = rem >> 7, l = (rem >> 1) & 63, kb = rem & 1, kk = 2 * kk2 + kb;
+      out[idx] = mix_tile[(16 * wb + (l & 15)) * LD + 4 * kk + (l >> 4)];
+    }
+  }
+  {  // [code][wb][gg][r]  <-  P[16 wb + 4 r + gg][code]
+    double *out = PTg + (size_t)slot * DP * DP;
+    for (int idx = threadIdx.x; idx < DP * DP; idx += blockDim.x) {
+      const int code = idx / (NT * 16), rem = idx - code * (NT * 16);
+      const int wb = rem >> 4, gg = (rem >> 2) & 3, r = rem & 3;
+      out[idx] = mix_tile[(16 * wb + 4 * r + gg) * LD + code];
+    }
+  }
+}
+
 }  // namespace
+
+void launch_mix_class_images(const double *P, const int *off, const double *w, const int32_t *slots, int n_list, int n_classes, int n_tot,
+                             int D, double *Pfrag, double *PTg, hipStream_t stream) {
+  if (n_list <= 0 || n_classes <= 0) return;
+  const int NT = (D + 15) / 16, DP = 16 * NT;
+  hipLaunchKernelGGL(mix_class_images_kernel, dim3(n_list, n_classes), dim3(256), (size_t)DP * (DP + 1) * sizeof(double), stream, P, off,
+                     w, slots, n_tot, D, NT, Pfrag, PTg);
+}
 
 void launch_mix_images(const double *P, const int *off, const double *w, const int32_t *slots, int n, int D, double *Pfrag,
                        double *PTg, double *Prow, hipStream_t stream, double *PTrow) {

@@ -150,7 +150,15 @@ struct Shard {
   void *comm = nullptr;       // ncclComm_t of this shard (hyphy_hip_comm_init_rank / single-process group)
   double *mix_q = nullptr, *mix_p = nullptr, *mix_w = nullptr;  // branch-site mixtures: component rate matrices, their exponentials, weights
   int *mix_off = nullptr;
-  size_t mix_cap = 0;         // components they hold (mix_off: one entry per branch and one more)
+  size_t mix_cap = 0;         // components mix_p and mix_w hold (mix_off: one entry per branch and one more)
+  size_t mix_q_cap = 0;       // ... and mix_q (dense entry points only)
+  // class-batched mixtures (hyphy_hip_evaluate_categories_mixture*): pinned staging [C class weights | B + 1 offsets (int) | mixture
+  // weights], copied in-stream; the counts whose offsets mix_off holds (empty: unknown — a one-class call wrote its own); whether a
+  // copy out of the staging may still be queued (a call that failed before its wait: the next one waits for the stream first)
+  double *h_mixst = nullptr;
+  size_t mixst_cap = 0;       // mixture weights it holds
+  std::vector<int64_t> mix_counts_dev;
+  bool mixst_inflight = false;
   int4 *jn = nullptr;         // chain schedules: per internal node (parent, arrivals needed | child sum << 8, trunk entries offset, count)
   int4 *h_jn = nullptr;
   double *deposits = nullptr; // chain schedules: [C][view's I][ntiles][TILE] edge products of non-last arrivers (allocated on first use: ensure_deposits)
@@ -180,7 +188,8 @@ struct Shard {
   int32_t *d_inv = nullptr;   // device pattern of caller pattern i (nullptr: identity)
   int exported = 0;           // what the last enqueued evaluation exported (1: values, 2: exponents)
   int32_t *h_slots = nullptr;
-  double *h_coeffs = nullptr;  // pinned ring (4 x C*B*K) for build_q coefficients
+  double *h_coeffs = nullptr;  // pinned ring (4 x coeff_rows_cap*K) for build_q coefficients
+  size_t coeff_rows_cap = 0;   // rows a ring slot and `coeffs` hold: max(C, 16)*B from hyphy_hip_set_q_templates, grown on demand up to 16*C*B
   double *d_hcoeffs = nullptr; // ... as the device sees it (host-mapped): the fused expm kernel reads it directly
   const double *coeffs_cur = nullptr;  // coefficients of the pending fused build (device-visible pointer)
   unsigned coeff_turn = 0;
@@ -197,7 +206,8 @@ struct Shard {
   bool coeff_busy[4] = {false, false, false, false};
   int coeff_slot = -1;                 // ring slot of the staged coefficients
   int64_t coeff_rows = 0;              // rows staged by the last hyphy_hip_build_q (0: nothing staged)
-  int coeff_kind = 0;                  // what consumed them first: 0 nobody yet, 1 one row per (class, branch), 2 one row per (branch, mixture component)
+  int coeff_kind = 0;                  // what consumed them first: 0 nobody yet, 1 one row per (class, branch), 2 one row per (branch, mixture component),
+                                       // 3 one row per (class, branch, mixture component)
   bool qbuf_built = false;             // ... and materialised in qbuf (HYPHY_HIP_MATERIALIZE_Q)
   double *h_small = nullptr;  // pi / weights staging
   size_t h_small_cap = 0;
@@ -430,12 +440,13 @@ inline void rows_to_caller(const hyphy_hip_partition *p, const Shard &s, const T
     for (int64_t k = 0; k < n; k++) out[(size_t)r * p->S + caller_pattern(p, s.s0 + (list ? list[k] : k))] = src[(size_t)r * stride + k];
 }
 
-// branch-site mixture: matrix k of the evaluation is sum_m weights[off_k + m] exp(q[off_k + m]), count[k] components
+// branch-site mixture: matrix k of the evaluation is sum_m weights[off_k + m] exp(q[off_k + m]), count[k] components; in a class batch
+// (EvalRequest::batch) class c's weights and matrices sit at c * n_tot + off_k + m, under the same counts
 constexpr int64_t kMixRows = 16;  // most components of an explicit-form mixture per branch
 struct MixSpec {
   const int64_t *count;
   const double *weights;
-  int64_t n_tot;
+  int64_t n_tot;  // components of one class
 };
 
 // One evaluation as eval_common takes it; callers fill it by name.
@@ -457,7 +468,7 @@ struct EvalRequest {
   bool floor_log = false;                // ... of the stored per-pattern values, floored (category mode)
   bool batch = false;                    // all rate classes in one launch (MFMA path)
   bool force_persist = false;            // store every node, under the partition's own tree (restores behind downloads / the branch cache)
-  const MixSpec *mix = nullptr;          // explicit-form branch-site mixture
+  const MixSpec *mix = nullptr;          // explicit-form branch-site mixture (with `batch`: of every class, MixSpec)
 };
 // The two node lists of an entry point, each under a type of its own: a call that swaps them does not compile.
 struct UpdateList { const int64_t *nodes; int64_t n; };

@@ -26,6 +26,7 @@ EXPORTS = [
     "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_joint_ancestral", "hyphy_hip_sample_ancestral", "hyphy_hip_sample_uniforms", "hyphy_hip_simulate", "hyphy_hip_simulate_uniforms", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
     "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_repeat_layout", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_plan_switches", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
     "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error", "hyphy_hip_last_expm_kernel",
+    "hyphy_hip_evaluate_categories_mixture", "hyphy_hip_evaluate_categories_mixture_built",
     "hyphy_hip_hmm_set_sites", "hyphy_hip_hmm_logl", "hyphy_hip_hmm_viterbi", "hyphy_hip_evaluate_categories_hmm", "hyphy_hip_evaluate_categories_built_hmm", "hyphy_hip_plan_hmm", "hyphy_hip_hmm_host",
     "hyphy_hip_version",
 ]
@@ -72,6 +73,10 @@ def load():
     lib.hyphy_hip_evaluate_mixture.argtypes = [vp, C.c_int64, lp, C.c_int64, lp, C.c_int64, lp, dp, dp, dp, dp, dp, lp]
     lib.hyphy_hip_evaluate_mixture_built.restype = C.c_int
     lib.hyphy_hip_evaluate_mixture_built.argtypes = [vp, C.c_int64, lp, C.c_int64, lp, C.c_int64, lp, dp, dp, dp, dp, lp]
+    lib.hyphy_hip_evaluate_categories_mixture.restype = C.c_int
+    lib.hyphy_hip_evaluate_categories_mixture.argtypes = [vp, lp, C.c_int64, lp, C.c_int64, lp, dp, dp, dp, dp, dp, dp, lp]
+    lib.hyphy_hip_evaluate_categories_mixture_built.restype = C.c_int
+    lib.hyphy_hip_evaluate_categories_mixture_built.argtypes = [vp, lp, C.c_int64, lp, C.c_int64, lp, dp, dp, dp, dp, dp, lp]
     lib.hyphy_hip_evaluate_async.restype = C.c_int
     lib.hyphy_hip_evaluate_async.argtypes = [vp, C.c_int64, lp, C.c_int64, lp, C.c_int64, dp, C.c_int, dp]
     lib.hyphy_hip_collect.restype = C.c_int
@@ -509,6 +514,24 @@ def pack_mixture(n_q: int, components, weights, tail_ndim: int):
     return np.ascontiguousarray(np.concatenate(per, axis=0)), np.ascontiguousarray(np.concatenate(wts)), cnt
 
 
+def pack_class_mixture(n_q: int, components, weights, tail_ndim: int):
+    """Host-only: what the class-batched mixture entry points pass on.  ``components`` and ``weights``: a sequence over the rate
+    classes of what ``pack_mixture`` takes for one class, under the same component counts in every class (ValueError otherwise, and
+    for no class at all).  Returns (components [C * n_tot, ...], weights [C * n_tot], counts [n_q]): class-major, inside a class
+    branch-major."""
+    if len(components) != len(weights) or len(components) < 1:
+        raise ValueError(f"pack_class_mixture: {len(components)} classes of components, {len(weights)} of weights")
+    packed = [pack_mixture(n_q, q, w, tail_ndim) for q, w in zip(components, weights)]
+    cnt = packed[0][2]
+    for c, (q, w, k) in enumerate(packed):
+        if not np.array_equal(k, cnt):
+            raise ValueError(f"pack_class_mixture: class {c} has other component counts than class 0")
+        if q.shape[1:] != packed[0][0].shape[1:]:
+            raise ValueError(f"pack_class_mixture: class {c} has components of another shape than class 0")
+    return (np.ascontiguousarray(np.concatenate([x[0] for x in packed], axis=0)), np.ascontiguousarray(np.concatenate([x[1] for x in packed])),
+            cnt)
+
+
 def last_expm_kernel() -> str:
     """The matrix-exponential kernel this thread's last launch ran ("expm64_kernel<2>", "expm_mfma_kernel<4,2>", "expm_nuc_kernel",
     ...); "" before the first launch and when the exponentials were folded into a pruning launch."""
@@ -850,6 +873,49 @@ class HipPartition:
         _check(self._lib.hyphy_hip_evaluate_categories(self._h, _l(un), len(un), _l(qn), len(qn), _d(q),
                                                        int(q_is_probability), _d(w), _d(rf), C.byref(out), _d(sl),
                                                        _l(sc)))
+        return (out.value, sl, sc) if per_site else out.value
+
+    def evaluate_categories_mixture(self, update_nodes, q_nodes, q_components, mix_weights, class_weights, root_freqs,
+                                    per_site: bool = False):
+        """Rate classes over branch-site mixtures in one batched evaluation: ``q_components`` and ``mix_weights`` are sequences
+        over the classes of what ``evaluate_mixture`` takes for one class (the same component counts in every class:
+        ``pack_class_mixture``), ``class_weights`` [C].  With no branch listed both may be empty: a re-mix, or a pure update."""
+        un = np.ascontiguousarray(update_nodes, dtype=np.int64)
+        qn = np.ascontiguousarray(q_nodes, dtype=np.int64)
+        q = w = cnt = None
+        if len(qn):
+            q, w, cnt = pack_class_mixture(len(qn), q_components, mix_weights, 2)
+            assert q.ndim == 3 and q.shape[1:] == (self.D, self.D) and q.shape[0] == self.C * int(cnt.sum()), q.shape
+        cw = None if class_weights is None else np.ascontiguousarray(class_weights, dtype=np.float64)
+        assert cw is None or cw.shape == (self.C,)
+        rf = np.ascontiguousarray(root_freqs, dtype=np.float64)
+        out = C.c_double(0.0)
+        sl = np.zeros(self.S) if per_site else None
+        sc = np.zeros(self.S, dtype=np.int64) if per_site else None
+        _check(self._lib.hyphy_hip_evaluate_categories_mixture(self._h, _l(un), len(un), _l(qn), len(qn), _l(cnt), _d(q), _d(w), _d(cw),
+                                                               _d(rf), C.byref(out), _d(sl), _l(sc)))
+        return (out.value, sl, sc) if per_site else out.value
+
+    def evaluate_categories_mixture_built(self, update_nodes, q_nodes, coeffs, mix_weights, class_weights, root_freqs,
+                                          per_site: bool = False):
+        """The same with the components formed on the device: ``coeffs`` is a sequence over the classes of what
+        ``evaluate_mixture_built`` takes (``hyphy_hip_build_q`` of one row per (class, branch, component) +
+        ``hyphy_hip_evaluate_categories_mixture_built``).  With no branch listed nothing is staged."""
+        un = np.ascontiguousarray(update_nodes, dtype=np.int64)
+        qn = np.ascontiguousarray(q_nodes, dtype=np.int64)
+        w = cnt = None
+        if len(qn):
+            c, w, cnt = pack_class_mixture(len(qn), coeffs, mix_weights, 1)
+            assert c.ndim == 2 and c.shape[0] == self.C * int(cnt.sum()), c.shape
+            _check(self._lib.hyphy_hip_build_q(self._h, c.shape[0], _d(c)))
+        cw = None if class_weights is None else np.ascontiguousarray(class_weights, dtype=np.float64)
+        assert cw is None or cw.shape == (self.C,)
+        rf = np.ascontiguousarray(root_freqs, dtype=np.float64)
+        out = C.c_double(0.0)
+        sl = np.zeros(self.S) if per_site else None
+        sc = np.zeros(self.S, dtype=np.int64) if per_site else None
+        _check(self._lib.hyphy_hip_evaluate_categories_mixture_built(self._h, _l(un), len(un), _l(qn), len(qn), _l(cnt), _d(w), _d(cw),
+                                                                     _d(rf), C.byref(out), _d(sl), _l(sc)))
         return (out.value, sl, sc) if per_site else out.value
 
     def hmm_set_sites(self, pattern_of_site=None):

@@ -294,6 +294,45 @@ int hyphy_hip_evaluate_categories_built_sites(hyphy_hip_partition *p, const int6
                                               int64_t *site_scaler_out);
 
 /*
+ * Rate classes OVER branch-site mixtures in one batched evaluation (BUSTED with --srv, its default: three synonymous-rate classes
+ * over a model that is already an explicit-form mixture of three omega components on every branch,
+ * res/TemplateBatchFiles/SelectionAnalyses/BUSTED.bf:116, :192; RELAX and aBSREL with --srv have the same shape).  Class c evolves on
+ * branch q_nodes[k] under P = sum_m mix_weights[c][.] exp(Q[c][.]); the classes are then mixed by class_weights exactly as
+ * hyphy_hip_evaluate_categories mixes them: the category floor of -1e6 * f, NaN propagates, frequency-0 patterns are skipped, and the
+ * per-pattern outputs are the mixed (likelihood, exponent) in the caller's pattern order.
+ *   n_components [n_q]      1..16 components per branch, a count of its own on each, THE SAME COUNTS IN EVERY CLASS; n_tot = their sum
+ *   q_dense [C][n_tot][D*D] class-major, inside a class branch-major (the components of q_nodes[0], then those of q_nodes[1], ...)
+ *   mix_weights [C][n_tot]  in the same order;  class_weights [C]
+ * The device exponentiates all C * n_tot components in ONE launch (hyphy_hip_last_expm_kernel names it), forms both matrix images of
+ * every (class, branch) with one workgroup each, and prunes every class in one launch.  C == 1 is accepted.  n_q == 0 is accepted (a
+ * re-mix under new class weights, or a pure update list): the component arguments may then be NULL and no staged rows are consumed.
+ * As for the other entry points: the first evaluation of a class lists every branch; a failed call commits nothing; the branch caches
+ * of every class are invalidated; a later one-class call on any class works; the per-class values, matrices and images stay resident
+ * (hyphy_hip_hmm_logl / _viterbi, hyphy_hip_download_partials, hyphy_hip_branch_cache_build, the ancestral entry points and
+ * hyphy_hip_simulate work behind such a pass).  A component that cannot be exponentiated fails the call whatever its weight (< 0,
+ * "Failed to compute a valid transition matrix"); the listed branches are then without usable matrices in EVERY class, and a full
+ * pass with good matrices gives what a fresh partition gives.  4-state partitions run the classes one after another through the
+ * staging of hyphy_hip_evaluate_mixture, as hyphy_hip_evaluate_categories does.  hyphy_hip_last_reduce_form answers what it answers
+ * behind hyphy_hip_evaluate_categories.
+ */
+int hyphy_hip_evaluate_categories_mixture(hyphy_hip_partition *p, const int64_t *update_nodes, int64_t n_update,
+                                          const int64_t *q_nodes, int64_t n_q, const int64_t *n_components /* [n_q] */,
+                                          const double *q_dense /* [C][n_tot][D*D] */, const double *mix_weights /* [C][n_tot] */,
+                                          const double *class_weights /* [C] */, const double *root_freqs, double *logl_out,
+                                          double *site_lik_out /* [S] or NULL */, int64_t *site_scaler_out /* [S] or NULL */);
+/* The same with the components formed on the device: hyphy_hip_build_q(p, C * n_tot, ...) stages one row per (class, branch,
+ * component), in that order (the layout of the adapter's template mode, class c's row at its own template columns); up to 16 * C *
+ * (L + I - 1) rows.  Refused: a different number of rows than the call consumes, and rows an evaluation of another kind — one row per
+ * (class, branch), or per (branch, component) of one class — has already consumed.  MFMA partitions only, as
+ * hyphy_hip_evaluate_categories_built.  With the lists and counts of the previous call the host waits once, for the result record:
+ * the weights travel through pinned staging in-stream, and the offsets are uploaded only when the counts or the list change. */
+int hyphy_hip_evaluate_categories_mixture_built(hyphy_hip_partition *p, const int64_t *update_nodes, int64_t n_update,
+                                                const int64_t *q_nodes, int64_t n_q, const int64_t *n_components /* [n_q] */,
+                                                const double *mix_weights /* [C][n_tot] */, const double *class_weights /* [C] */,
+                                                const double *root_freqs, double *logl_out, double *site_lik_out,
+                                                int64_t *site_scaler_out);
+
+/*
  * Copies device partials back in the reference's host layout for code that reads the caches
  * directly (ReconstructAncestors likefunc2.cpp:416-449, FillInConditionals tree.cpp:3335-3371):
  *   inode_cache [I*S*D]  iNodeCache[(node*S + pattern)*D + state] (tree_evaluator.cpp:3608-3617)
