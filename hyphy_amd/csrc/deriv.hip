@@ -1,0 +1,443 @@
+// Every branch's first and second derivative of log L along a generator, from one outside pass.  With the outside vector V_c of
+// branch c (outside.h), its conditional in_c and its resident matrix P_c, E = P_c in_c, the likelihood under P_c(theta) =
+// exp(theta G) P_c is  l(theta) = sum_i V[i] (exp(theta G) E)[i]  per pattern, hence at theta = 0
+//   l0 = V . E        l1 = V . (G E)        l2 = V . (G (G E)),      2^64 exponent of all three = exponent(V_c) + exponent(in_c),
+//   d log l / d theta = l1 / l0,    d^2 log l / d theta^2 = l2 / l0 - (l1 / l0)^2.
+// No exponential is computed and the exponents cancel inside each pattern's ratio.  Rate classes: (l0, l1, l2) are mixed by weight
+// with their exponents aligned on the smallest, then the ratios are taken of the mixed (L0, L1, L2).
+//
+// Phase 1 (outside_store_kernel<NW>, outside_store_nuc_kernel of outside.h): the walk with the OutsideStore sink, as the branch
+// trials run it.
+// Generator images (deriv_image_kernel): the row-major G of every (derivative, class) as an A-operand image, zero-padded to DP
+// (4 states: [16] row-major as given).
+// Phase 2 (branch_derivs_kernel<NW>, branch_derivs_nuc_kernel): one wave per (branch with a derivative, tile), the tile the fastest
+// grid index.  V and E (outside.h's edge_product over the resident images) are formed once; every generator of the branch is two
+// [D x D] x [D x 16] products on the FP64 MFMA — the C/D fragment of G E is the B operand of G (G E) — and three row sums.  Classes
+// run one launch after another; the last class's launch forms r1, r2 and one partial record per (derivative, tile).
+// Reduction (derivs_reduce_kernel): one wave per derivative, combine.h's fixed-order compensated sum, once per total.
+// Nothing joins by order of arrival: two identical calls give identical bits.  Chunks of tiles as in trials.hip, under the same
+// budget (HYPHY_HIP_TRIALS_MB); all scratch comes from the pool and goes back before the call returns.  The partition's matrices,
+// images, schedules and caches are not written.
+#include "combine.h"
+#include "devutil.h"
+#include "outside.h"
+#include "partition.h"
+
+using namespace hyhip;
+
+namespace hyhip {
+namespace {
+
+struct DerivArgs {
+  int NW, L, S_pad, tile0, ct;          // (4 states: tiles of 64 patterns)
+  int C, cls, first, last, b0;          // classes, class of this launch, it is the first / the last one, first branch of the grid
+  double w;                             // weight of this class (1 when C == 1)
+  const int *branch;                    // [branches with a derivative] node codes
+  const int *d_off, *d_idx;             // derivatives of branch k: d_idx[d_off[k] .. d_off[k + 1])
+  const double *img;                    // [n][C] generators: A-operand images (4 states: [16] row-major)
+  const double *V;                      // phase 1's blocks of this chunk
+  const int32_t *Vcnt;
+  const double *freq;
+  double *L0, *L1, *L2;                 // [n][S_pad] per pattern: classes mixed so far; behind the last class L1 = r1, L2 = r2
+  int32_t *cnt;                         // their common exponent
+  double *part_d1, *part_d2;            // [n][part_stride] per (derivative, tile): sum_s f_s r1, sum_s f_s r2
+  long long *part_skip;                 // patterns of positive frequency with L0 == 0
+  int *part_flag;                       // 2: not a number
+  int part_stride;
+};
+
+// hyphy_hip_last_reduce_form and hyphy_hip_last_expm_kernel answer behind the call what they answered before it
+struct KeepForms {
+  hyphy_hip_partition *p;
+  hyphy_hip_partition::ReduceForm reduce;
+  const char *expm;
+  ~KeepForms() {
+    p->last_reduce = reduce;
+    set_last_expm_kernel(expm);
+  }
+};
+
+// this class's (l0, l1, l2; exponent e) of pattern q into the mix of the classes before it, aligned on the smaller exponent as
+// mix_in of trials.hip aligns likelihoods.  A triple of exact zeros (a weight of 0, an impossible pattern) carries no exponent: it
+// leaves the others as they are, where aligning on its exponent could flush them to zero.
+__device__ __forceinline__ void mix3(const DerivArgs &a, size_t q, double &l0, double &l1, double &l2, int &e) {
+  l0 *= a.w, l1 *= a.w, l2 *= a.w;
+  if (a.first) return;
+  const double o0 = a.L0[q], o1 = a.L1[q], o2 = a.L2[q];
+  const int e_old = a.cnt[q];
+  if (l0 == 0. && l1 == 0. && l2 == 0.) {
+    l0 = o0, l1 = o1, l2 = o2, e = e_old;
+  } else if (!(o0 == 0. && o1 == 0. && o2 == 0.)) {
+    const int e_new = min(e_old, e);
+    const double so = ldexp(1.0, -64 * (e_old - e_new)), sn = ldexp(1.0, -64 * (e - e_new));
+    l0 = o0 * so + l0 * sn, l1 = o1 * so + l1 * sn, l2 = o2 * so + l2 * sn;
+    e = e_new;
+  }
+}
+
+// r1, r2 of the mixed (L0, L1, L2) and the pattern's terms of the totals
+__device__ __forceinline__ void site_ratio(double l0, double l1, double l2, double f, double &r1, double &r2, double &s1, double &s2,
+                                           long long &skip, int &flag) {
+  if (l0 != l0 || l1 != l1 || l2 != l2) {
+    r1 = r2 = NAN;
+    if (f != 0.) flag |= 2;
+  } else if (l0 == 0.) {
+    r1 = r2 = NAN;
+    if (f != 0.) skip += 1;
+  } else {
+    r1 = l1 / l0;
+    r2 = l2 / l0 - r1 * r1;
+    if (f != 0.) {
+      if (r1 != r1 || r2 != r2) flag |= 2;
+      s1 += f * r1;
+      s2 += f * r2;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void deriv_image_kernel(const double *__restrict__ G, double *__restrict__ img, int D, int NW, int nuc) {
+  const double *src = G + (size_t)blockIdx.x * D * D;
+  if (nuc) {
+    if (threadIdx.x < 16) img[(size_t)blockIdx.x * 16 + threadIdx.x] = src[threadIdx.x];
+    return;
+  }
+  const int DP = 16 * NW;
+  double *dst = img + (size_t)blockIdx.x * DP * DP;
+  for (int idx = threadIdx.x; idx < DP * DP; idx += blockDim.x) {
+    int r, c;
+    frag_image_rc(idx, NW, r, c);
+    dst[idx] = r < D && c < D ? src[r * D + c] : 0.;
+  }
+}
+
+template <int NW>
+__global__ __launch_bounds__(64) void branch_derivs_kernel(WalkArgs wa, DerivArgs a) {
+  constexpr int NKK = 4 * NW, DP = 16 * NW, TILE = NKK * 64;
+  const int lane = threadIdx.x, g = lane >> 4, sl = lane & 15;
+  const int lt = blockIdx.x, tile = a.tile0 + lt, site = tile * 16 + sl;
+  const int bi = a.b0 + blockIdx.y, node = a.branch[bi];
+  double V[NKK], E[NKK];
+  ld_vec<NKK>(a.V + ((size_t)node * a.ct + lt) * TILE, lane, V);
+  int bcnt = a.Vcnt[((size_t)node * a.ct + lt) * 16 + sl], ecnt;
+  edge_product<NW>(wa, make_int4(1, node, node >= a.L ? node - a.L : -1, 0), tile, lane, E, ecnt);
+  bcnt += ecnt;
+  double s0 = 0.;
+#pragma unroll
+  for (int kk = 0; kk < NKK; kk++) s0 += V[kk] * E[kk];
+  s0 = row_sum4(s0);
+  const double f = a.freq[site];
+  for (int k = a.d_off[bi]; k < a.d_off[bi + 1]; k++) {
+    const int t = a.d_idx[k];
+    const double *G = a.img + ((size_t)t * a.C + a.cls) * DP * DP;
+    double X[NKK];
+    mfma_product<NW>(G, E, lane, X);
+    double s1 = 0., s2 = 0.;
+#pragma unroll
+    for (int kk = 0; kk < NKK; kk++) s1 += V[kk] * X[kk];
+    __builtin_amdgcn_sched_barrier(0);  // (the second product's operand loads stay behind the first product: registers)
+    {
+      double Y[NKK];
+      mfma_product<NW>(G, X, lane, Y);
+#pragma unroll
+      for (int kk = 0; kk < NKK; kk++) s2 += V[kk] * Y[kk];
+    }
+    s1 = row_sum4(s1);
+    s2 = row_sum4(s2);
+    double w1 = 0., w2 = 0.;
+    long long wskip = 0;
+    int wflag = 0;
+    if (g == 0) {
+      const size_t q = (size_t)t * a.S_pad + site;
+      double l0 = s0;
+      int e = bcnt;
+      mix3(a, q, l0, s1, s2, e);
+      if (a.last) {
+        double r1, r2;
+        site_ratio(l0, s1, s2, f, r1, r2, w1, w2, wskip, wflag);
+        s1 = r1, s2 = r2;
+      }
+      a.L0[q] = l0;
+      a.L1[q] = s1;
+      a.L2[q] = s2;
+      a.cnt[q] = e;
+    }
+    if (a.last) {
+#pragma unroll
+      for (int off = 8; off > 0; off >>= 1) {
+        w1 += __shfl_xor(w1, off);
+        w2 += __shfl_xor(w2, off);
+        wskip += __shfl_xor(wskip, off);
+        wflag |= __shfl_xor(wflag, off);
+      }
+      if (lane == 0) {
+        const size_t pq = (size_t)t * a.part_stride + tile;
+        a.part_d1[pq] = w1;
+        a.part_d2[pq] = w2;
+        a.part_skip[pq] = wskip;
+        a.part_flag[pq] = wflag;
+      }
+    }
+  }
+}
+
+// 4 states: one thread per pattern, one wave per (branch, 64 patterns)
+__global__ __launch_bounds__(64) void branch_derivs_nuc_kernel(WalkArgs wa, DerivArgs a) {
+  const int lane = threadIdx.x;
+  const int lt = blockIdx.x, tile = a.tile0 + lt;
+  const size_t ls = (size_t)lt * 64 + lane, s = (size_t)tile * 64 + lane, CS = (size_t)a.ct * 64, SP = a.S_pad;
+  const int bi = a.b0 + blockIdx.y, node = a.branch[bi];
+  double V[4], in[4], E[4];
+  for (int j = 0; j < 4; j++) V[j] = a.V[((size_t)node * 4 + j) * CS + ls];
+  int bcnt = a.Vcnt[(size_t)node * CS + ls];
+  if (node >= a.L) {
+    for (int j = 0; j < 4; j++) in[j] = wa.partials[((size_t)(node - a.L) * 4 + j) * SP + s];
+    bcnt += wa.counts[(size_t)(node - a.L) * SP + s];
+  } else {
+    nuc_leaf_vec(wa, (int)wa.codes[(size_t)node * SP + s], in);
+  }
+  const double *P = wa.Prow + (size_t)node * 16;
+  for (int x = 0; x < 4; x++) E[x] = P[4 * x] * in[0] + P[4 * x + 1] * in[1] + P[4 * x + 2] * in[2] + P[4 * x + 3] * in[3];
+  const double s0 = (V[0] * E[0] + V[1] * E[1]) + (V[2] * E[2] + V[3] * E[3]);
+  const double f = a.freq[s];
+  for (int k = a.d_off[bi]; k < a.d_off[bi + 1]; k++) {
+    const int t = a.d_idx[k];
+    const double *G = a.img + ((size_t)t * a.C + a.cls) * 16;
+    double X[4], Y[4];
+    for (int x = 0; x < 4; x++) X[x] = G[4 * x] * E[0] + G[4 * x + 1] * E[1] + G[4 * x + 2] * E[2] + G[4 * x + 3] * E[3];
+    for (int x = 0; x < 4; x++) Y[x] = G[4 * x] * X[0] + G[4 * x + 1] * X[1] + G[4 * x + 2] * X[2] + G[4 * x + 3] * X[3];
+    double l0 = s0, l1 = (V[0] * X[0] + V[1] * X[1]) + (V[2] * X[2] + V[3] * X[3]);
+    double l2 = (V[0] * Y[0] + V[1] * Y[1]) + (V[2] * Y[2] + V[3] * Y[3]);
+    const size_t q = (size_t)t * SP + s;
+    int e = bcnt;
+    mix3(a, q, l0, l1, l2, e);
+    double w1 = 0., w2 = 0.;
+    long long wskip = 0;
+    int wflag = 0;
+    if (a.last) {
+      double r1, r2;
+      site_ratio(l0, l1, l2, f, r1, r2, w1, w2, wskip, wflag);
+      l1 = r1, l2 = r2;
+    }
+    a.L0[q] = l0;
+    a.L1[q] = l1;
+    a.L2[q] = l2;
+    a.cnt[q] = e;
+    if (a.last) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        w1 += __shfl_xor(w1, off);
+        w2 += __shfl_xor(w2, off);
+        wskip += __shfl_xor(wskip, off);
+        wflag |= __shfl_xor(wflag, off);
+      }
+      if (lane == 0) {
+        const size_t pq = (size_t)t * a.part_stride + tile;
+        a.part_d1[pq] = w1;
+        a.part_d2[pq] = w2;
+        a.part_skip[pq] = wskip;
+        a.part_flag[pq] = wflag;
+      }
+    }
+  }
+}
+
+// totals of derivative blockIdx.x from its per-tile records: one wave, fixed order, compensated; out = [n] d1, [n] d2, [n] skipped
+__global__ __launch_bounds__(64) void derivs_reduce_kernel(double *part_d1, double *part_d2, long long *part_skip, int *part_flag, int n,
+                                                           int stride, double *__restrict__ out, long long *__restrict__ skip_out) {
+  const size_t o = (size_t)blockIdx.x * stride;
+  double s1, c1, s2, c2;
+  long long k1, k2;
+  int f1, f2;
+  combine_range(part_d1 + o, part_skip + o, part_flag + o, n, 0, n, (int)threadIdx.x, s1, c1, k1, f1);
+  combine_range(part_d2 + o, part_skip + o, part_flag + o, n, 0, n, (int)threadIdx.x, s2, c2, k2, f2);
+  if (threadIdx.x == 0) {
+    const bool bad = ((f1 | f2) & 2) != 0;
+    out[blockIdx.x] = bad ? NAN : s1 - c1;
+    out[gridDim.x + blockIdx.x] = bad ? NAN : s2 - c2;
+    skip_out[blockIdx.x] = k1;
+  }
+}
+
+int derivs_common(const char *what, hyphy_hip_partition *p, int64_t n, const int64_t *nodes, const double *g_dense, const double *coeffs,
+                  const double *weights, double *d1_out, double *d2_out, int64_t *skipped_out, double *site_d1_out,
+                  double *site_d2_out) {
+  const std::string pre = std::string(what) + ": ";
+  if (!p) return fail(pre + "partition == NULL");
+  if (n < 0) return fail(pre + "n < 0");
+  if (check_unpinned(p, pre)) return -1;
+  const int C = (int)p->C;
+  if (C > 1 && !weights) return fail(pre + "class weights are required when C > 1");
+  if (check_evaluated(p, pre)) return -1;
+  if (n == 0) return 0;
+  if (!nodes || !d1_out || !d2_out || (!g_dense && !coeffs)) return fail(pre + "null argument");
+  if (coeffs && !p->K) return fail(pre + "templates not set (hyphy_hip_set_q_templates)");
+  if (n * (int64_t)C > 0x3fffffff) return fail(pre + "too many derivatives");
+  const int64_t D = p->D, L = p->L, I = p->I, B = p->B;
+  for (int64_t t = 0; t < n; t++)
+    if (nodes[t] < 0 || nodes[t] >= B)
+      return fail(pre + "derivative " + std::to_string(t) + ": node code out of range (the root has no branch)");
+  const KeepForms keep = {p, p->last_reduce, last_expm_kernel()};
+  if (finish_pending_async(p)) return -1;
+  for (int c = 0; c < C; c++)
+    if (ensure_resident(p, c)) return -1;
+  const int DP = p->DP, NW = p->NW;
+  const bool nuc = p->nuc;
+  if (p->marg_prog.empty()) p->marg_prog = plan_marginal_program(L, I, p->parents.data(), &p->marg_maxk);
+  const std::vector<int4> &prog = p->marg_prog;
+  const int maxk = p->marg_maxk;
+  const std::vector<double> pi_pad = padded_pi(p);
+  // derivatives grouped by branch, branches in ascending node code, the derivatives of a branch in the caller's order
+  std::vector<int> order((size_t)n), branch, d_off;
+  for (int64_t t = 0; t < n; t++) order[(size_t)t] = (int)t;
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return nodes[x] < nodes[y]; });
+  for (int64_t k = 0; k < n; k++)
+    if (k == 0 || nodes[order[(size_t)k]] != nodes[order[(size_t)k - 1]]) {
+      branch.push_back((int)nodes[order[(size_t)k]]);
+      d_off.push_back((int)k);
+    }
+  d_off.push_back((int)n);
+  const int n_branch = (int)branch.size();
+  const double budget = sw::scratch_budget(sw::TRIALS_MB);
+  const size_t MS = nuc ? 16 : (size_t)DP * DP;     // doubles of a generator on the device
+  const size_t TILE = nuc ? 256 : (size_t)16 * DP;  // doubles of one tile of one node
+  const int TP = nuc ? 64 : 16;                     // its patterns
+  std::vector<double> totals((size_t)2 * n), h_r;
+  std::vector<long long> h_skip((size_t)n);
+  std::vector<std::vector<double>> parts1((size_t)n), parts2((size_t)n);
+  std::vector<int64_t> skipped((size_t)n, 0);
+  for (Shard &s : p->shards) {
+    HIPCHK(hipSetDevice(s.device));
+    HIPCHK(hipStreamSynchronize(s.stream));
+    Blocks blk;
+    const int ntiles = s.S_pad / TP;
+    const int ct = (int)std::min<double>(ntiles, std::max(1., floor(budget / ((double)B * TILE * sizeof(double)))));
+    const int part_stride = (ntiles + 3) / 4 * 4 + 4;  // (combine_range reads whole 16-byte words)
+    const size_t nm = (size_t)n * C;
+    double *img = nullptr, *src = nullptr, *gq = nullptr, *L0 = nullptr, *L1 = nullptr, *L2 = nullptr, *part_d1 = nullptr, *part_d2 = nullptr;
+    double *d_tot = nullptr, *d_pi = nullptr, *PT = nullptr, *V = nullptr, *U = nullptr, *work = nullptr;
+    int32_t *cnt = nullptr, *Vcnt = nullptr, *Ucnt = nullptr, *wcnt = nullptr;
+    long long *part_skip = nullptr, *d_skip = nullptr;
+    int *part_flag = nullptr, *d_branch = nullptr, *d_doff = nullptr, *d_idx = nullptr;
+    int4 *d_prog = nullptr;
+    HIPCHK(blk.get(&img, nm * MS));
+    HIPCHK(blk.get(&src, g_dense ? nm * D * D : nm * p->K));
+    if (coeffs) HIPCHK(blk.get(&gq, nm * D * D));
+    HIPCHK(blk.get(&L0, (size_t)n * s.S_pad));
+    HIPCHK(blk.get(&L1, (size_t)n * s.S_pad));
+    HIPCHK(blk.get(&L2, (size_t)n * s.S_pad));
+    HIPCHK(blk.get(&cnt, (size_t)n * s.S_pad));
+    HIPCHK(blk.get(&part_d1, (size_t)n * part_stride));
+    HIPCHK(blk.get(&part_d2, (size_t)n * part_stride));
+    HIPCHK(blk.get(&part_skip, (size_t)n * part_stride));
+    HIPCHK(blk.get(&part_flag, (size_t)n * part_stride));
+    HIPCHK(blk.get(&d_tot, (size_t)2 * n));
+    HIPCHK(blk.get(&d_skip, (size_t)n));
+    HIPCHK(blk.get(&d_pi, pi_pad.size()));
+    HIPCHK(blk.get(&d_prog, prog.size()));
+    HIPCHK(blk.get(&d_branch, (size_t)n_branch));
+    HIPCHK(blk.get(&d_doff, (size_t)n_branch + 1));
+    HIPCHK(blk.get(&d_idx, (size_t)n));
+    if (!nuc) HIPCHK(blk.get(&PT, (size_t)B * DP * DP));
+    HIPCHK(blk.get(&V, (size_t)B * ct * TILE));
+    HIPCHK(blk.get(&Vcnt, (size_t)B * ct * TP));
+    HIPCHK(blk.get(&U, (size_t)I * ct * TILE));
+    HIPCHK(blk.get(&Ucnt, (size_t)I * ct * TP));
+    HIPCHK(blk.get(&work, (size_t)ct * 2 * maxk * TILE));
+    HIPCHK(blk.get(&wcnt, (size_t)ct * 2 * maxk * TP));
+    HIPCHK(hipMemcpyAsync(src, g_dense ? g_dense : coeffs, (g_dense ? nm * D * D : nm * p->K) * sizeof(double), hipMemcpyHostToDevice,
+                          s.stream));
+    HIPCHK(hipMemcpyAsync(d_pi, pi_pad.data(), pi_pad.size() * sizeof(double), hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(d_prog, prog.data(), prog.size() * sizeof(int4), hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(d_branch, branch.data(), branch.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(d_doff, d_off.data(), d_off.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(d_idx, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
+    // generators: built from the templates into the call's own scratch (never the partition's Q buffer), then their images
+    if (coeffs) launch_build_q(s.templates, src, (int)nm, (int)p->K, (int)D, gq, s.stream);
+    hipLaunchKernelGGL(deriv_image_kernel, dim3((unsigned)nm), dim3(256), 0, s.stream, coeffs ? gq : src, img, (int)D, NW, nuc ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    for (int tile0 = 0; tile0 < ntiles; tile0 += ct) {
+      const int nt = std::min(ct, ntiles - tile0);
+      for (int c = 0; c < C; c++) {
+        DerivArgs da;
+        da.NW = NW, da.L = (int)L, da.S_pad = s.S_pad, da.tile0 = tile0, da.ct = ct;
+        da.C = C, da.cls = c, da.first = c == 0, da.last = c == C - 1, da.b0 = 0;
+        da.w = C > 1 ? weights[c] : 1.0;
+        da.branch = d_branch, da.d_off = d_doff, da.d_idx = d_idx;
+        da.img = img;
+        da.V = V, da.Vcnt = Vcnt;
+        da.freq = s.freq;
+        da.L0 = L0, da.L1 = L1, da.L2 = L2, da.cnt = cnt;
+        da.part_d1 = part_d1, da.part_d2 = part_d2, da.part_skip = part_skip, da.part_flag = part_flag, da.part_stride = part_stride;
+        WalkArgs a = walk_args(p, s, c);
+        a.prog = d_prog, a.pi = d_pi, a.PT = PT;
+        a.U = U, a.Ucnt = Ucnt, a.work = work, a.wcnt = wcnt;
+        const int unit = nuc ? TP : 1;  // (4 states: the walk counts patterns)
+        a.first = tile0 * unit, a.count = nt * unit, a.chunk = ct * unit;
+        const OutsideStore o = {V, Vcnt};
+        if (nuc) {
+          hipLaunchKernelGGL(outside_store_nuc_kernel, dim3((unsigned)((a.count + 255) / 256)), dim3(256), 0, s.stream, a, o);
+        } else {
+          if (C > 1 || tile0 == 0)
+            hipLaunchKernelGGL(marg_transpose_kernel, dim3((unsigned)B), dim3(256), 0, s.stream, a.Pfrag, a.PTg, PT, NW, (int)L);
+          LAUNCH_NW(outside_store_kernel, NW, dim3((unsigned)nt), dim3(64), s.stream, a, o);
+        }
+        for (da.b0 = 0; da.b0 < n_branch; da.b0 += 65535) {
+          const dim3 grid((unsigned)nt, (unsigned)std::min(65535, n_branch - da.b0)), block(64);
+          if (nuc) hipLaunchKernelGGL(branch_derivs_nuc_kernel, grid, block, 0, s.stream, a, da);
+          else LAUNCH_NW(branch_derivs_kernel, NW, grid, block, s.stream, a, da);
+        }
+        HIPCHK(hipGetLastError());
+      }
+    }
+    hipLaunchKernelGGL(derivs_reduce_kernel, dim3((unsigned)n), dim3(64), 0, s.stream, part_d1, part_d2, part_skip, part_flag, ntiles,
+                       part_stride, d_tot, d_skip);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(totals.data(), d_tot, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(hipMemcpyAsync(h_skip.data(), d_skip, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(hipStreamSynchronize(s.stream));
+    for (int64_t t = 0; t < n; t++) {
+      parts1[(size_t)t].push_back(totals[(size_t)t]);
+      parts2[(size_t)t].push_back(totals[(size_t)(n + t)]);
+      skipped[(size_t)t] += (int64_t)h_skip[(size_t)t];
+    }
+    // per-pattern results -> the caller's pattern order: out[derivative][caller pattern]
+    if (site_d1_out) {
+      h_r.resize((size_t)n * s.S_pad);
+      HIPCHK(hipMemcpy(h_r.data(), L1, h_r.size() * sizeof(double), hipMemcpyDeviceToHost));
+      rows_to_caller(p, s, h_r.data(), (size_t)s.S_pad, n, s.S, site_d1_out);
+    }
+    if (site_d2_out) {
+      h_r.resize((size_t)n * s.S_pad);
+      HIPCHK(hipMemcpy(h_r.data(), L2, h_r.size() * sizeof(double), hipMemcpyDeviceToHost));
+      rows_to_caller(p, s, h_r.data(), (size_t)s.S_pad, n, s.S, site_d2_out);
+    }
+  }
+  for (int64_t t = 0; t < n; t++) {
+    d1_out[t] = combine(parts1[(size_t)t]);
+    d2_out[t] = combine(parts2[(size_t)t]);
+    if (skipped_out) skipped_out[t] = skipped[(size_t)t];
+  }
+  return 0;
+}
+
+}  // namespace
+}  // namespace hyhip
+
+extern "C" {
+
+int hyphy_hip_branch_derivatives(hyphy_hip_partition *p, int64_t n, const int64_t *nodes, const double *g_dense, const double *weights,
+                                 double *d1_out, double *d2_out, int64_t *skipped_out, double *site_d1_out, double *site_d2_out) {
+  if (p && n > 0 && !g_dense) return fail("branch_derivatives: null generator pointer");
+  return derivs_common("branch_derivatives", p, n, nodes, g_dense, nullptr, weights, d1_out, d2_out, skipped_out, site_d1_out,
+                       site_d2_out);
+}
+
+int hyphy_hip_branch_derivatives_built(hyphy_hip_partition *p, int64_t n, const int64_t *nodes, const double *coeffs,
+                                       const double *weights, double *d1_out, double *d2_out, int64_t *skipped_out, double *site_d1_out,
+                                       double *site_d2_out) {
+  if (p && n > 0 && !coeffs) return fail("branch_derivatives_built: null coefficient pointer");
+  return derivs_common("branch_derivatives_built", p, n, nodes, nullptr, coeffs, weights, d1_out, d2_out, skipped_out, site_d1_out,
+                       site_d2_out);
+}
+
+}  // extern "C"

@@ -8,7 +8,8 @@
 //   branch    a child's rescaled V and its exponent
 //   leaf      a leaf's U = P_l^T V_l (not rescaled), formed only when the sink's kLeafProduct is set
 // in two forms each, told apart by their arguments: (tile, lane, fragment vector) and (pattern, 4 values).  The marginal
-// reconstruction (marginal.hip) accumulates support in `node` / `leaf`; the branch trials (trials.hip) store V in `branch`.
+// reconstruction (marginal.hip) accumulates support in `node` / `leaf`; the branch trials (trials.hip) and the branch derivatives
+// (deriv.hip) store V in `branch`, through the OutsideStore sink and its two kernels at the end of this file.
 // U, Ucnt, work and wcnt are indexed by (tile or pattern within the chunk, size of the chunk): a chunk that is the whole shard gives
 // the [I][ntiles][TILE] / [I][S_pad] shapes of the partials.  gfx950 only.
 #pragma once
@@ -316,6 +317,39 @@ __device__ __forceinline__ void outside_walk_nuc(const WalkArgs &a, Sink &sink) 
     pc += 1 + k;
   }
 }
+
+// phase 1's sink: V_c and its exponent of every child, leaves included, into blocks of one chunk of tiles (a.chunk of them), indexed
+// by the tile within the chunk.  A leaf's U is not formed.
+struct OutsideStore {
+  static constexpr bool kLeafProduct = false;
+  double *V;      // [B][ct][TILE]   (4 states: [B][4][ct * 64])
+  int32_t *Vcnt;  // [B][ct][16]     (4 states: [B][ct * 64])
+
+  __device__ __forceinline__ bool leaves() const { return true; }
+  template <int NKK>
+  __device__ __forceinline__ void node(const WalkArgs &, int, int, int, const double (&)[NKK], int) const {}
+  template <int NKK>
+  __device__ __forceinline__ void branch(const WalkArgs &a, int c, int lt, int lane, const double (&v)[NKK], int vcnt) const {
+    st_vec<NKK>(V + ((size_t)c * a.chunk + lt) * (NKK * 64), lane, v);
+    Vcnt[((size_t)c * a.chunk + lt) * 16 + (lane & 15)] = vcnt;
+  }
+  template <int NKK>
+  __device__ __forceinline__ void leaf(const WalkArgs &, int, int, int, const double (&)[NKK], int) const {}
+  // 4 states
+  __device__ __forceinline__ void node(const WalkArgs &, int, size_t, const double (&)[4], int) const {}
+  __device__ __forceinline__ void branch(const WalkArgs &a, int c, size_t ls, const double (&v)[4], int vcnt) const {
+    for (int j = 0; j < 4; j++) V[((size_t)c * 4 + j) * a.chunk + ls] = v[j];
+    Vcnt[(size_t)c * a.chunk + ls] = vcnt;
+  }
+  __device__ __forceinline__ void leaf(const WalkArgs &, int, size_t, const double (&)[4], int) const {}
+};
+
+template <int NW>
+__global__ __launch_bounds__(64) void outside_store_kernel(WalkArgs a, OutsideStore o) {
+  outside_walk<NW>(a, o);
+}
+
+__global__ __launch_bounds__(256) void outside_store_nuc_kernel(WalkArgs a, OutsideStore o) { outside_walk_nuc(a, o); }
 
 }  // namespace
 }  // namespace hyhip

@@ -23,7 +23,7 @@ EXPORTS = [
     "hyphy_hip_expm_batch", "hyphy_hip_set_q_templates", "hyphy_hip_build_q", "hyphy_hip_q_buffer",
     "hyphy_hip_evaluate_built", "hyphy_hip_evaluate_built_sites", "hyphy_hip_update_q_templates", "hyphy_hip_evaluate_categories_built", "hyphy_hip_evaluate_categories_built_sites", "hyphy_hip_prune_timings", "hyphy_hip_prune_launches",
     "hyphy_hip_prune_kernel_name", "hyphy_hip_last_prune_form", "hyphy_hip_last_reduce_form", "hyphy_hip_branch_cache_build", "hyphy_hip_branch_cache_evaluate",
-    "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_joint_ancestral", "hyphy_hip_sample_ancestral", "hyphy_hip_sample_uniforms", "hyphy_hip_simulate", "hyphy_hip_simulate_uniforms", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
+    "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_joint_ancestral", "hyphy_hip_sample_ancestral", "hyphy_hip_sample_uniforms", "hyphy_hip_simulate", "hyphy_hip_simulate_uniforms", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_branch_derivatives", "hyphy_hip_branch_derivatives_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
     "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_repeat_layout", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_plan_switches", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
     "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error", "hyphy_hip_last_expm_kernel",
     "hyphy_hip_evaluate_categories_mixture", "hyphy_hip_evaluate_categories_mixture_built",
@@ -169,6 +169,9 @@ def load():
     lib.hyphy_hip_branch_trials.argtypes = [vp, C.c_int64, lp, dp, C.c_int, dp, dp, dp, lp]
     lib.hyphy_hip_branch_trials_built.restype = C.c_int
     lib.hyphy_hip_branch_trials_built.argtypes = [vp, C.c_int64, lp, dp, dp, dp, dp, lp]
+    for fn in (lib.hyphy_hip_branch_derivatives, lib.hyphy_hip_branch_derivatives_built):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, C.c_int64, lp, dp, dp, dp, dp, lp, dp, dp]
     lib.hyphy_hip_plan_marginal.restype = C.c_int64
     lib.hyphy_hip_plan_marginal.argtypes = [C.c_int64, C.c_int64, lp, lp, C.c_int64]
     lib.hyphy_hip_plan_trunk_walk.restype = C.c_int64
@@ -1101,6 +1104,38 @@ class HipPartition:
         nd, co, w, ll, sl, sc = self._trial_args(nodes, coeffs, (K,), weights, per_site)
         _check(self._lib.hyphy_hip_branch_trials_built(self._h, len(nd), _l(nd), _d(co), _d(w), _d(ll), _d(sl), _l(sc)))
         return (ll, sl, sc) if per_site else ll
+
+    # -- first and second log-L derivatives of any number of branches from one outside pass --------
+    def _derivative_call(self, fn, nodes, mats, tail, weights, per_site):
+        nd = np.ascontiguousarray(nodes, dtype=np.int64).reshape(-1)
+        m = np.ascontiguousarray(mats, dtype=np.float64)
+        if m.size != len(nd) * self.C * int(np.prod(tail)):
+            raise ValueError(f"expected [{len(nd)}, {self.C}, {', '.join(str(x) for x in tail)}] values, got {m.shape}")
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            if w.shape != (self.C,):
+                raise ValueError(f"expected {self.C} class weights, got {w.shape}")
+        d1, d2 = np.zeros(len(nd)), np.zeros(len(nd))
+        sk = np.zeros(len(nd), dtype=np.int64)
+        s1 = np.zeros((len(nd), self.S)) if per_site else None
+        s2 = np.zeros((len(nd), self.S)) if per_site else None
+        _check(getattr(self._lib, fn)(self._h, len(nd), _l(nd), _d(m), _d(w), _d(d1), _d(d2), _l(sk), _d(s1), _d(s2)))
+        return (d1, d2, sk, s1, s2) if per_site else (d1, d2, sk)
+
+    def branch_derivatives(self, nodes, g_dense, weights=None, per_site: bool = False):
+        """(d1, d2, skipped), [n] each: the first and second derivative at theta = 0 of log L under P_b(theta) = exp(theta G) P_b for
+        branch ``nodes[t]`` and generator ``g_dense[t]`` ([n, D, D], or [n, C, D, D] with one generator per rate class), everything
+        else as at the last evaluation of every class; ``skipped``: the patterns of positive frequency whose likelihood is exactly 0
+        (they take no part).  With G = Q_b the derivatives in log t_b are d1 and d2 + d1.  ``per_site``: also the per-pattern r1 and
+        r2, [n, S] each (NaN at skipped patterns).  Nothing on the device changes."""
+        return self._derivative_call("hyphy_hip_branch_derivatives", nodes, g_dense, (self.D, self.D), weights, per_site)
+
+    def branch_derivatives_built(self, nodes, coeffs, weights=None, per_site: bool = False):
+        """``branch_derivatives`` with the generators formed on the device from coefficient rows over the templates of
+        ``set_q_templates`` (``coeffs``: [n, K] or [n, C, K]), as ``build_q`` forms rate matrices."""
+        K = int(np.asarray(coeffs).shape[-1])
+        return self._derivative_call("hyphy_hip_branch_derivatives_built", nodes, coeffs, (K,), weights, per_site)
 
     # -- branch cache (one-branch line searches) --------------------------------------------------
     def branch_cache_build(self, node: int, cat: int = 0):

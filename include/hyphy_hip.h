@@ -518,6 +518,42 @@ int hyphy_hip_branch_trials_built(hyphy_hip_partition *p, int64_t n_trials, cons
                                   const double *weights /* [C] or NULL */, double *logl_out, double *site_lik_out,
                                   int64_t *site_scaler_out);
 
+/* ---- every branch's first and second log-L derivatives from one outside pass ---------------------------------
+ * The exact derivatives an optimiser moves branch lengths with, all branches in one call and without an exponential.  With V the
+ * outside vector of branch b and E = P_b in_b its edge product (both exactly what the pass above forms), per pattern and class
+ *   l0 = sum_i V[i] E[i]     l1 = sum_i V[i] (G E)[i]     l2 = sum_i V[i] (G (G E))[i]
+ * carry one 2^64 exponent, exponent(V) + exponent(in_b).  For C > 1 the three are mixed over the classes by weight with their
+ * exponents aligned on the smallest (a class whose three values are exactly 0, a weight of 0 among them, takes no part in the
+ * alignment) into L0, L1, L2; for C == 1 they are l0, l1, l2.  Per pattern r1 = L1 / L0 and r2 = L2 / L0 - r1^2, and
+ *   d1_out[t] = sum_s f_s r1     d2_out[t] = sum_s f_s r2:
+ * the first and second derivative at theta = 0 of log L under P_b(theta) = exp(theta G) P_b, P_b the resident matrix.  With
+ * G = Q_b, the scaled rate matrix the branch was last evaluated with, they are the derivatives in a multiplier lambda on the
+ * branch's matrix at lambda = 1; in theta = log t_b the first derivative is d1 and the second is d2 + d1.  This is a model
+ * parameter's derivative exactly when that parameter scales the whole matrix (a branch length, a class's rate multiplier); for a
+ * mixture branch only if the caller accepts G P for it.
+ *   nodes    [n]            node codes (leaf l -> l, internal i -> L + i, never the root), any order, repeats allowed
+ *   g_dense  [n][C][D*D]    row-major generators, one per class; hyphy_hip_branch_derivatives_built takes coeffs [n][C][K] over the
+ *                           templates of hyphy_hip_set_q_templates instead (G = sum_k coeffs_k T_k, diagonal -(row sum), formed as
+ *                           hyphy_hip_build_q forms it but into scratch of the call, not into the partition's Q buffer)
+ *   weights  [C] (NULL when C == 1)
+ *   d1_out, d2_out [n]; skipped_out [n] or NULL; site_d1_out, site_d2_out [n][S] or NULL: r1, r2 in the caller's pattern order
+ * A pattern with f_s == 0 takes no part.  A pattern of positive frequency whose mixed L0 is exactly 0 takes no part, is counted in
+ * skipped_out[t], and its per-pattern values are NaN.  A NaN in L0, L1 or L2 of a pattern of positive frequency makes both totals
+ * NaN.  G == 0 gives exactly 0.0 and 0.0.  4-state partitions are served; there is no "unsupported" return.
+ * Call after an evaluation of every class.  Leaves no state behind: the device's matrices and images, the schedules, the tuner's
+ * state, the class tables, the branch-cache slots and hyphy_hip_last_expm_kernel are what they were (persisted copies are restored
+ * first if the last full pass kept them on chip, as before a marginal reconstruction); hyphy_hip_last_reduce_form is what it was
+ * too.  Two identical calls give identical bits: the totals are fixed-order compensated sums per shard, combined over shards as
+ * the log-likelihoods are.  Chunks of tiles and scratch as hyphy_hip_branch_trials, under the same budget (HYPHY_HIP_TRIALS_MB).
+ * Returns < 0 for a NULL partition or output, an active pin, a class never evaluated, C > 1 without weights, a node code out of
+ * range or the root's, templates not set (_built); n == 0 returns 0 and writes nothing. */
+int hyphy_hip_branch_derivatives(hyphy_hip_partition *p, int64_t n, const int64_t *nodes, const double *g_dense,
+                                 const double *weights /* [C] or NULL */, double *d1_out, double *d2_out, int64_t *skipped_out,
+                                 double *site_d1_out, double *site_d2_out);
+int hyphy_hip_branch_derivatives_built(hyphy_hip_partition *p, int64_t n, const int64_t *nodes, const double *coeffs,
+                                       const double *weights /* [C] or NULL */, double *d1_out, double *d2_out, int64_t *skipped_out,
+                                       double *site_d1_out, double *site_d2_out);
+
 /* ---- joint maximum-likelihood ancestral reconstruction ------------------------------------------------------
  * Replaces _TheTree::RecoverAncestralSequences (src/core/tree.cpp:4209-4510), the max-product pass behind
  * `ReconstructAncestors (lf)` without MARGINAL: per pattern an upward pass over the nodes in ascending node code
