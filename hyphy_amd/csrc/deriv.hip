@@ -15,12 +15,12 @@
 // [D x D] x [D x 16] products on the FP64 MFMA — the C/D fragment of G E is the B operand of G (G E) — and three row sums.  Classes
 // run one launch after another; the last class's launch forms r1, r2 and one partial record per (derivative, tile).
 // Reduction (derivs_reduce_kernel): one wave per derivative, combine.h's fixed-order compensated sum, once per total.
-// Nothing joins by order of arrival: two identical calls give identical bits.  Chunks of tiles as in trials.hip, under the same
-// budget (HYPHY_HIP_TRIALS_MB); all scratch comes from the pool and goes back before the call returns.  The partition's matrices,
-// images, schedules and caches are not written.
+// Nothing joins by order of arrival: two identical calls give identical bits.  The refusals, the scratch of the walk and the loop over
+// chunks of tiles and classes are outside_pass.h's, as for trials.hip and under the same budget (HYPHY_HIP_TRIALS_MB); all scratch
+// comes from the pool and goes back before the call returns.  The partition's matrices, images, schedules and caches are not written.
 #include "combine.h"
 #include "devutil.h"
-#include "outside.h"
+#include "outside_pass.h"
 #include "partition.h"
 
 using namespace hyhip;
@@ -264,44 +264,18 @@ int derivs_common(const char *what, hyphy_hip_partition *p, int64_t n, const int
   const std::string pre = std::string(what) + ": ";
   if (!p) return fail(pre + "partition == NULL");
   if (n < 0) return fail(pre + "n < 0");
-  if (check_unpinned(p, pre)) return -1;
-  const int C = (int)p->C;
-  if (C > 1 && !weights) return fail(pre + "class weights are required when C > 1");
-  if (check_evaluated(p, pre)) return -1;
+  if (check_pass_ready(p, pre, weights)) return -1;
   if (n == 0) return 0;
   if (!nodes || !d1_out || !d2_out || (!g_dense && !coeffs)) return fail(pre + "null argument");
-  if (coeffs && !p->K) return fail(pre + "templates not set (hyphy_hip_set_q_templates)");
-  if (n * (int64_t)C > 0x3fffffff) return fail(pre + "too many derivatives");
-  const int64_t D = p->D, L = p->L, I = p->I, B = p->B;
-  for (int64_t t = 0; t < n; t++)
-    if (nodes[t] < 0 || nodes[t] >= B)
-      return fail(pre + "derivative " + std::to_string(t) + ": node code out of range (the root has no branch)");
+  if (check_requests(p, pre, "derivative", n, nodes, coeffs != nullptr)) return -1;
   const KeepForms keep = {p, p->last_reduce, last_expm_kernel()};
-  if (finish_pending_async(p)) return -1;
-  for (int c = 0; c < C; c++)
-    if (ensure_resident(p, c)) return -1;
-  const int DP = p->DP, NW = p->NW;
+  OutsideCall oc;
+  if (begin_outside(p, oc, nodes, n)) return -1;
+  const int C = (int)p->C, NW = p->NW;
+  const int64_t D = p->D;
   const bool nuc = p->nuc;
-  if (p->marg_prog.empty()) p->marg_prog = plan_marginal_program(L, I, p->parents.data(), &p->marg_maxk);
-  const std::vector<int4> &prog = p->marg_prog;
-  const int maxk = p->marg_maxk;
-  const std::vector<double> pi_pad = padded_pi(p);
-  // derivatives grouped by branch, branches in ascending node code, the derivatives of a branch in the caller's order
-  std::vector<int> order((size_t)n), branch, d_off;
-  for (int64_t t = 0; t < n; t++) order[(size_t)t] = (int)t;
-  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return nodes[x] < nodes[y]; });
-  for (int64_t k = 0; k < n; k++)
-    if (k == 0 || nodes[order[(size_t)k]] != nodes[order[(size_t)k - 1]]) {
-      branch.push_back((int)nodes[order[(size_t)k]]);
-      d_off.push_back((int)k);
-    }
-  d_off.push_back((int)n);
-  const int n_branch = (int)branch.size();
-  const double budget = sw::scratch_budget(sw::TRIALS_MB);
-  const size_t MS = nuc ? 16 : (size_t)DP * DP;     // doubles of a generator on the device
-  const size_t TILE = nuc ? 256 : (size_t)16 * DP;  // doubles of one tile of one node
-  const int TP = nuc ? 64 : 16;                     // its patterns
-  std::vector<double> totals((size_t)2 * n), h_r;
+  const size_t MS = nuc ? 16 : (size_t)p->DP * p->DP;  // doubles of a generator on the device
+  std::vector<double> totals((size_t)2 * n);
   std::vector<long long> h_skip((size_t)n);
   std::vector<std::vector<double>> parts1((size_t)n), parts2((size_t)n);
   std::vector<int64_t> skipped((size_t)n, 0);
@@ -309,88 +283,51 @@ int derivs_common(const char *what, hyphy_hip_partition *p, int64_t n, const int
     HIPCHK(hipSetDevice(s.device));
     HIPCHK(hipStreamSynchronize(s.stream));
     Blocks blk;
-    const int ntiles = s.S_pad / TP;
-    const int ct = (int)std::min<double>(ntiles, std::max(1., floor(budget / ((double)B * TILE * sizeof(double)))));
-    const int part_stride = (ntiles + 3) / 4 * 4 + 4;  // (combine_range reads whole 16-byte words)
-    const size_t nm = (size_t)n * C;
+    OutsideScratch sc;
+    sc.plan(p, s, oc);
+    const size_t nm = (size_t)n * C, nq = g_dense ? nm * D * D : nm * p->K, np = (size_t)n * sc.part_stride;
     double *img = nullptr, *src = nullptr, *gq = nullptr, *L0 = nullptr, *L1 = nullptr, *L2 = nullptr, *part_d1 = nullptr, *part_d2 = nullptr;
-    double *d_tot = nullptr, *d_pi = nullptr, *PT = nullptr, *V = nullptr, *U = nullptr, *work = nullptr;
-    int32_t *cnt = nullptr, *Vcnt = nullptr, *Ucnt = nullptr, *wcnt = nullptr;
+    double *d_tot = nullptr;
+    int32_t *cnt = nullptr;
     long long *part_skip = nullptr, *d_skip = nullptr;
-    int *part_flag = nullptr, *d_branch = nullptr, *d_doff = nullptr, *d_idx = nullptr;
-    int4 *d_prog = nullptr;
+    int *part_flag = nullptr;
     HIPCHK(blk.get(&img, nm * MS));
-    HIPCHK(blk.get(&src, g_dense ? nm * D * D : nm * p->K));
+    HIPCHK(blk.get(&src, nq));
     if (coeffs) HIPCHK(blk.get(&gq, nm * D * D));
     HIPCHK(blk.get(&L0, (size_t)n * s.S_pad));
     HIPCHK(blk.get(&L1, (size_t)n * s.S_pad));
     HIPCHK(blk.get(&L2, (size_t)n * s.S_pad));
     HIPCHK(blk.get(&cnt, (size_t)n * s.S_pad));
-    HIPCHK(blk.get(&part_d1, (size_t)n * part_stride));
-    HIPCHK(blk.get(&part_d2, (size_t)n * part_stride));
-    HIPCHK(blk.get(&part_skip, (size_t)n * part_stride));
-    HIPCHK(blk.get(&part_flag, (size_t)n * part_stride));
+    HIPCHK(blk.get(&part_d1, np));
+    HIPCHK(blk.get(&part_d2, np));
+    HIPCHK(blk.get(&part_skip, np));
+    HIPCHK(blk.get(&part_flag, np));
     HIPCHK(blk.get(&d_tot, (size_t)2 * n));
     HIPCHK(blk.get(&d_skip, (size_t)n));
-    HIPCHK(blk.get(&d_pi, pi_pad.size()));
-    HIPCHK(blk.get(&d_prog, prog.size()));
-    HIPCHK(blk.get(&d_branch, (size_t)n_branch));
-    HIPCHK(blk.get(&d_doff, (size_t)n_branch + 1));
-    HIPCHK(blk.get(&d_idx, (size_t)n));
-    if (!nuc) HIPCHK(blk.get(&PT, (size_t)B * DP * DP));
-    HIPCHK(blk.get(&V, (size_t)B * ct * TILE));
-    HIPCHK(blk.get(&Vcnt, (size_t)B * ct * TP));
-    HIPCHK(blk.get(&U, (size_t)I * ct * TILE));
-    HIPCHK(blk.get(&Ucnt, (size_t)I * ct * TP));
-    HIPCHK(blk.get(&work, (size_t)ct * 2 * maxk * TILE));
-    HIPCHK(blk.get(&wcnt, (size_t)ct * 2 * maxk * TP));
-    HIPCHK(hipMemcpyAsync(src, g_dense ? g_dense : coeffs, (g_dense ? nm * D * D : nm * p->K) * sizeof(double), hipMemcpyHostToDevice,
-                          s.stream));
-    HIPCHK(hipMemcpyAsync(d_pi, pi_pad.data(), pi_pad.size() * sizeof(double), hipMemcpyHostToDevice, s.stream));
-    HIPCHK(hipMemcpyAsync(d_prog, prog.data(), prog.size() * sizeof(int4), hipMemcpyHostToDevice, s.stream));
-    HIPCHK(hipMemcpyAsync(d_branch, branch.data(), branch.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
-    HIPCHK(hipMemcpyAsync(d_doff, d_off.data(), d_off.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
-    HIPCHK(hipMemcpyAsync(d_idx, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
+    if (sc.get(p, oc, blk)) return -1;
+    HIPCHK(hipMemcpyAsync(src, g_dense ? g_dense : coeffs, nq * sizeof(double), hipMemcpyHostToDevice, s.stream));
+    if (sc.upload(p, oc, s.stream)) return -1;
     // generators: built from the templates into the call's own scratch (never the partition's Q buffer), then their images
     if (coeffs) launch_build_q(s.templates, src, (int)nm, (int)p->K, (int)D, gq, s.stream);
     hipLaunchKernelGGL(deriv_image_kernel, dim3((unsigned)nm), dim3(256), 0, s.stream, coeffs ? gq : src, img, (int)D, NW, nuc ? 1 : 0);
     HIPCHK(hipGetLastError());
-    for (int tile0 = 0; tile0 < ntiles; tile0 += ct) {
-      const int nt = std::min(ct, ntiles - tile0);
-      for (int c = 0; c < C; c++) {
-        DerivArgs da;
-        da.NW = NW, da.L = (int)L, da.S_pad = s.S_pad, da.tile0 = tile0, da.ct = ct;
-        da.C = C, da.cls = c, da.first = c == 0, da.last = c == C - 1, da.b0 = 0;
-        da.w = C > 1 ? weights[c] : 1.0;
-        da.branch = d_branch, da.d_off = d_doff, da.d_idx = d_idx;
-        da.img = img;
-        da.V = V, da.Vcnt = Vcnt;
-        da.freq = s.freq;
-        da.L0 = L0, da.L1 = L1, da.L2 = L2, da.cnt = cnt;
-        da.part_d1 = part_d1, da.part_d2 = part_d2, da.part_skip = part_skip, da.part_flag = part_flag, da.part_stride = part_stride;
-        WalkArgs a = walk_args(p, s, c);
-        a.prog = d_prog, a.pi = d_pi, a.PT = PT;
-        a.U = U, a.Ucnt = Ucnt, a.work = work, a.wcnt = wcnt;
-        const int unit = nuc ? TP : 1;  // (4 states: the walk counts patterns)
-        a.first = tile0 * unit, a.count = nt * unit, a.chunk = ct * unit;
-        const OutsideStore o = {V, Vcnt};
-        if (nuc) {
-          hipLaunchKernelGGL(outside_store_nuc_kernel, dim3((unsigned)((a.count + 255) / 256)), dim3(256), 0, s.stream, a, o);
-        } else {
-          if (C > 1 || tile0 == 0)
-            hipLaunchKernelGGL(marg_transpose_kernel, dim3((unsigned)B), dim3(256), 0, s.stream, a.Pfrag, a.PTg, PT, NW, (int)L);
-          LAUNCH_NW(outside_store_kernel, NW, dim3((unsigned)nt), dim3(64), s.stream, a, o);
-        }
-        for (da.b0 = 0; da.b0 < n_branch; da.b0 += 65535) {
-          const dim3 grid((unsigned)nt, (unsigned)std::min(65535, n_branch - da.b0)), block(64);
-          if (nuc) hipLaunchKernelGGL(branch_derivs_nuc_kernel, grid, block, 0, s.stream, a, da);
-          else LAUNCH_NW(branch_derivs_kernel, NW, grid, block, s.stream, a, da);
-        }
-        HIPCHK(hipGetLastError());
-      }
-    }
-    hipLaunchKernelGGL(derivs_reduce_kernel, dim3((unsigned)n), dim3(64), 0, s.stream, part_d1, part_d2, part_skip, part_flag, ntiles,
-                       part_stride, d_tot, d_skip);
+    const int walked = outside_chunks(p, s, oc, sc, weights, [&](const WalkArgs &a, const OutsideSlice &sl, dim3 grid) {
+      DerivArgs da;
+      da.NW = NW, da.L = a.L, da.S_pad = a.S_pad, da.tile0 = sl.tile0, da.ct = sl.ct;
+      da.C = sl.C, da.cls = sl.cls, da.first = sl.first, da.last = sl.last, da.b0 = sl.b0;
+      da.w = sl.w;
+      da.branch = sl.branch, da.d_off = sl.off, da.d_idx = sl.idx;
+      da.img = img;
+      da.V = sl.V, da.Vcnt = sl.Vcnt;
+      da.freq = s.freq;
+      da.L0 = L0, da.L1 = L1, da.L2 = L2, da.cnt = cnt;
+      da.part_d1 = part_d1, da.part_d2 = part_d2, da.part_skip = part_skip, da.part_flag = part_flag, da.part_stride = sl.part_stride;
+      if (nuc) hipLaunchKernelGGL(branch_derivs_nuc_kernel, grid, dim3(64), 0, s.stream, a, da);
+      else LAUNCH_NW(branch_derivs_kernel, NW, grid, dim3(64), s.stream, a, da);
+    });
+    if (walked) return -1;
+    hipLaunchKernelGGL(derivs_reduce_kernel, dim3((unsigned)n), dim3(64), 0, s.stream, part_d1, part_d2, part_skip, part_flag, sc.ntiles,
+                       sc.part_stride, d_tot, d_skip);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(totals.data(), d_tot, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, s.stream));
     HIPCHK(hipMemcpyAsync(h_skip.data(), d_skip, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost, s.stream));
@@ -400,17 +337,8 @@ int derivs_common(const char *what, hyphy_hip_partition *p, int64_t n, const int
       parts2[(size_t)t].push_back(totals[(size_t)(n + t)]);
       skipped[(size_t)t] += (int64_t)h_skip[(size_t)t];
     }
-    // per-pattern results -> the caller's pattern order: out[derivative][caller pattern]
-    if (site_d1_out) {
-      h_r.resize((size_t)n * s.S_pad);
-      HIPCHK(hipMemcpy(h_r.data(), L1, h_r.size() * sizeof(double), hipMemcpyDeviceToHost));
-      rows_to_caller(p, s, h_r.data(), (size_t)s.S_pad, n, s.S, site_d1_out);
-    }
-    if (site_d2_out) {
-      h_r.resize((size_t)n * s.S_pad);
-      HIPCHK(hipMemcpy(h_r.data(), L2, h_r.size() * sizeof(double), hipMemcpyDeviceToHost));
-      rows_to_caller(p, s, h_r.data(), (size_t)s.S_pad, n, s.S, site_d2_out);
-    }
+    if (site_d1_out && download_rows(p, s, L1, n, site_d1_out)) return -1;
+    if (site_d2_out && download_rows(p, s, L2, n, site_d2_out)) return -1;
   }
   for (int64_t t = 0; t < n; t++) {
     d1_out[t] = combine(parts1[(size_t)t]);

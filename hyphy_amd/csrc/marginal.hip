@@ -221,22 +221,15 @@ int hyphy_hip_marginal_ancestral(hyphy_hip_partition *p, int64_t which, const do
                                  int64_t *map_state_out, double *map_support_out) {
   if (!p) return fail("marginal_ancestral: partition == NULL");
   if (which != 0 && which != 1) return fail("marginal_ancestral: which must be 0 (internal nodes) or 1 (leaves)");
-  if (check_unpinned(p, "marginal_ancestral: ")) return -1;
+  if (check_pass_ready(p, "marginal_ancestral: ", weights)) return -1;
+  std::vector<double> pi_pad;
+  if (begin_outside(p, pi_pad)) return -1;
   const int C = (int)p->C;
-  if (C > 1 && !weights) return fail("marginal_ancestral: class weights are required when C > 1");
-  if (check_evaluated(p, "marginal_ancestral: ")) return -1;
-  if (finish_pending_async(p)) return -1;
-  for (int c = 0; c < C; c++)
-    if (ensure_resident(p, c)) return -1;
-  // (the pass reads the plain tree's persisted copies.  When ensure_resident has to restore them, its persisting pass switches the
-  //  partition to the plain view and marks the class tables stale, as before a branch-cache build; the next evaluation switches back)
   const int64_t D = p->D, L = p->L, I = p->I, B = p->B, S = p->S;
   const int DP = p->DP, NW = p->NW;
   const int64_t rows = which == 0 ? I : L;
-  if (p->marg_prog.empty()) p->marg_prog = plan_marginal_program(L, I, p->parents.data(), &p->marg_maxk);
   const std::vector<int4> &prog = p->marg_prog;
   const int maxk = p->marg_maxk;
-  const std::vector<double> pi_pad = padded_pi(p);
   for (Shard &s : p->shards) {
     HIPCHK(hipSetDevice(s.device));
     HIPCHK(hipStreamSynchronize(s.stream));
@@ -267,9 +260,7 @@ int hyphy_hip_marginal_ancestral(hyphy_hip_partition *p, int64_t which, const do
     if (e == hipSuccess) e = blk.get(&msup, nrs);
     if (e == hipSuccess) e = blk.get(&mst, nrs);
     for (int c = 0; c < C && e == hipSuccess; c++) {
-      WalkArgs a = walk_args(p, s, c);
-      a.prog = s.marg_prog, a.pi = s.marg_pi, a.PT = s.marg_PT;
-      a.U = s.marg_U, a.Ucnt = s.marg_Ucnt, a.work = s.marg_work, a.wcnt = s.marg_wcnt;
+      const WalkArgs a = walk_args(p, s, c, {s.marg_prog, s.marg_pi, s.marg_PT, s.marg_U, s.marg_Ucnt, s.marg_work, s.marg_wcnt});
       const MargSink k = {C > 1 ? weights[c] : 1.0, c == 0, (int)which, (int)D, (int)s.S, acc, den, aexp};
       if (p->nuc) {
         hipLaunchKernelGGL(marginal_nuc_kernel, dim3((unsigned)((s.S_pad + 255) / 256)), dim3(256), 0, s.stream, a, k);

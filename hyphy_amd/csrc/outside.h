@@ -9,7 +9,8 @@
 //   leaf      a leaf's U = P_l^T V_l (not rescaled), formed only when the sink's kLeafProduct is set
 // in two forms each, told apart by their arguments: (tile, lane, fragment vector) and (pattern, 4 values).  The marginal
 // reconstruction (marginal.hip) accumulates support in `node` / `leaf`; the branch trials (trials.hip) and the branch derivatives
-// (deriv.hip) store V in `branch`, through the OutsideStore sink and its two kernels at the end of this file.
+// (deriv.hip) store V in `branch`, through the OutsideStore sink and its two kernels at the end of this file, launched by the host
+// driver they share (outside_pass.h).  What all three do on the host before a launch is here too: check_pass_ready, begin_outside.
 // U, Ucnt, work and wcnt are indexed by (tile or pattern within the chunk, size of the chunk): a chunk that is the whole shard gives
 // the [I][ntiles][TILE] / [I][S_pad] shapes of the partials.  gfx950 only.
 #pragma once
@@ -42,10 +43,20 @@ struct WalkArgs {  // what the walks read; "tile" below: 16 patterns (4 states: 
   int32_t *wcnt;             // [chunk][2 maxk][16]                  (4 states: [2 maxk][chunk])
 };
 
-// the block for class c of shard s with the whole shard as the chunk; the caller adds prog, pi and the scratch (PT, U, Ucnt, work, wcnt)
-inline WalkArgs walk_args(const hyphy_hip_partition *p, const Shard &s, int c) {
+struct WalkScratch {  // what a pass brings to the walk: the uploaded program and pi, and the blocks the walk writes
+  const int4 *prog;
+  const double *pi;
+  double *PT, *U;
+  int32_t *Ucnt;
+  double *work;
+  int32_t *wcnt;
+};
+
+// the block for class c of shard s over the pass's scratch, with the whole shard as the chunk
+inline WalkArgs walk_args(const hyphy_hip_partition *p, const Shard &s, int c, const WalkScratch &w) {
   const size_t img = (size_t)c * p->B * p->DP * p->DP;
   WalkArgs a = {};
+  a.prog = w.prog, a.pi = w.pi, a.PT = w.PT, a.U = w.U, a.Ucnt = w.Ucnt, a.work = w.work, a.wcnt = w.wcnt;
   a.n_prog = (int)p->marg_prog.size();
   a.L = (int)p->L, a.S_pad = s.S_pad, a.ntiles = s.ntiles, a.maxk = p->marg_maxk;
   a.count = a.chunk = p->nuc ? s.S_pad : s.ntiles;
@@ -55,6 +66,26 @@ inline WalkArgs walk_args(const hyphy_hip_partition *p, const Shard &s, int c) {
   a.partials = s.partials + (size_t)c * s.partial_stride;
   a.counts = s.counts + (size_t)c * p->I * s.S_pad;
   return a;
+}
+
+// ---- what every pass over the walk does on the host before it launches anything ----
+// pinned states, class weights, every class evaluated (`pre`: the entry point's name and ": ")
+inline int check_pass_ready(const hyphy_hip_partition *p, const std::string &pre, const double *weights) {
+  if (check_unpinned(p, pre)) return -1;
+  if (p->C > 1 && !weights) return fail(pre + "class weights are required when C > 1");
+  return check_evaluated(p, pre);
+}
+
+// Pending work finished, every class resident, the program planned (once per partition), pi padded.
+// (the pass reads the plain tree's persisted copies.  When ensure_resident has to restore them, its persisting pass switches the
+//  partition to the plain view and marks the class tables stale, as before a branch-cache build; the next evaluation switches back)
+inline int begin_outside(hyphy_hip_partition *p, std::vector<double> &pi) {
+  if (finish_pending_async(p)) return -1;
+  for (int c = 0; c < (int)p->C; c++)
+    if (ensure_resident(p, c)) return -1;
+  if (p->marg_prog.empty()) p->marg_prog = plan_marginal_program(p->L, p->I, p->parents.data(), &p->marg_maxk);
+  pi = padded_pi(p);
+  return 0;
 }
 
 // transposed A-operand images M[r][c] = P[c][r] of every branch of one class: leaves from the column-gather image (the only

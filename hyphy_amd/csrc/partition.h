@@ -412,7 +412,7 @@ inline size_t ops_capacity(const hyphy_hip_partition *p) { return (size_t)(p->L 
 inline int64_t caller_pattern(const hyphy_hip_partition *p, int64_t j) { return p->perm.empty() ? j : p->perm[j]; }
 inline int twin_slot0(const hyphy_hip_partition *p) { return (int)(p->B + (p->I + 2)); }
 
-// ---- shared by the passes over the resident conditionals (marginal.hip, trials.hip, joint.hip, sample.hip) ----------------
+// ---- shared by the passes over the resident conditionals (marginal.hip, trials.hip, deriv.hip, joint.hip, sample.hip) -----
 // what they refuse (`pre`: the entry point's name and ": "; `used`: the classes the call reads, nullptr: all)
 inline int check_unpinned(const hyphy_hip_partition *p, const std::string &pre) {
   return p->pin_node >= 0 ? fail(pre + "a node's states are pinned (clear the pin first)") : 0;

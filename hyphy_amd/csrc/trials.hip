@@ -16,14 +16,13 @@
 // Reduction (trials_reduce_kernel): one wave per trial, combine.h's fixed-order compensated sum over the partial sums.
 // Nothing here joins by order of arrival: two identical calls give identical bits.
 //
-// Tiles are independent in both phases: phases 1-2 run over chunks of tiles so that the V scratch ([B][tiles of the chunk][TILE]
-// doubles) stays within HYPHY_HIP_TRIALS_MB (default 1024, read at every call, never less than one tile).  All scratch comes from the
-// pool and goes back before the call returns.  The partition's matrices, images, schedules and caches are not written.
-// 4 states: one thread per pattern over the plane layout and row-major matrices; a "tile" of the chunking is then one wave's
-// 64 patterns.
+// The refusals, the scratch of the walk and the loop over chunks of tiles and classes are outside_pass.h's, shared with deriv.hip; what
+// is here is the trials' own: their result blocks, the trial images, phase 2 and the reduction.  All scratch comes from the pool and
+// goes back before the call returns.  The partition's matrices, images, schedules and caches are not written.
+// 4 states: one thread per pattern over the plane layout and row-major matrices.
 #include "combine.h"
 #include "devutil.h"
-#include "outside.h"
+#include "outside_pass.h"
 #include "partition.h"
 
 using namespace hyhip;
@@ -208,90 +207,42 @@ int trials_common(const char *what, hyphy_hip_partition *p, int64_t n_trials, co
   const std::string pre = std::string(what) + ": ";
   if (!p) return fail(pre + "partition == NULL");
   if (n_trials < 0) return fail(pre + "n_trials < 0");
-  if (check_unpinned(p, pre)) return -1;
-  const int C = (int)p->C;
-  if (C > 1 && !weights) return fail(pre + "class weights are required when C > 1");
-  if (check_evaluated(p, pre)) return -1;
+  if (check_pass_ready(p, pre, weights)) return -1;
   if (n_trials == 0) return 0;
   if (!nodes || !logl_out || (!q_dense && !coeffs)) return fail(pre + "null argument");
-  if (coeffs && !p->K) return fail(pre + "templates not set (hyphy_hip_set_q_templates)");
-  if (n_trials * (int64_t)C > 0x3fffffff) return fail(pre + "too many trials");
-  const int64_t D = p->D, L = p->L, I = p->I, B = p->B;
-  for (int64_t t = 0; t < n_trials; t++)
-    if (nodes[t] < 0 || nodes[t] >= B)
-      return fail(pre + "trial " + std::to_string(t) + ": node code out of range (the root has no branch)");
-  if (finish_pending_async(p)) return -1;
-  for (int c = 0; c < C; c++)
-    if (ensure_resident(p, c)) return -1;
-  // (the pass reads the plain tree's persisted copies; when ensure_resident has to restore them it switches to the plain view, as
-  //  before a marginal reconstruction or a branch-cache build, and the next evaluation switches back)
-  const int DP = p->DP, NW = p->NW;
+  if (check_requests(p, pre, "trial", n_trials, nodes, coeffs != nullptr)) return -1;
+  OutsideCall oc;
+  if (begin_outside(p, oc, nodes, n_trials)) return -1;
+  const int C = (int)p->C, NW = p->NW;
+  const int64_t D = p->D;
   const bool nuc = p->nuc;
-  if (p->marg_prog.empty()) p->marg_prog = plan_marginal_program(L, I, p->parents.data(), &p->marg_maxk);
-  const std::vector<int4> &prog = p->marg_prog;
-  const int maxk = p->marg_maxk;
-  const std::vector<double> pi_pad = padded_pi(p);
-  // trials grouped by branch, branches in ascending node code, the trials of a branch in the caller's order
-  std::vector<int> order((size_t)n_trials), branch, tr_off;
-  for (int64_t t = 0; t < n_trials; t++) order[(size_t)t] = (int)t;
-  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return nodes[x] < nodes[y]; });
-  for (int64_t k = 0; k < n_trials; k++)
-    if (k == 0 || nodes[order[(size_t)k]] != nodes[order[(size_t)k - 1]]) {
-      branch.push_back((int)nodes[order[(size_t)k]]);
-      tr_off.push_back((int)k);
-    }
-  tr_off.push_back((int)n_trials);
-  const int n_branch = (int)branch.size();
-  const double budget = sw::scratch_budget(sw::TRIALS_MB);
-  const size_t MS = nuc ? 16 : (size_t)DP * DP;     // doubles of a trial matrix on the device
-  const size_t TILE = nuc ? 256 : (size_t)16 * DP;  // doubles of one tile of one node
-  const int TP = nuc ? 64 : 16;                     // its patterns
-  std::vector<double> totals((size_t)n_trials), h_l;
+  const size_t MS = nuc ? 16 : (size_t)p->DP * p->DP;  // doubles of a trial matrix on the device
+  std::vector<double> totals((size_t)n_trials);
   std::vector<std::vector<double>> parts((size_t)n_trials);
-  std::vector<int32_t> h_c;
   for (Shard &s : p->shards) {
     HIPCHK(hipSetDevice(s.device));
     HIPCHK(hipStreamSynchronize(s.stream));
     Blocks blk;
-    const int ntiles = s.S_pad / TP;
-    const int ct = (int)std::min<double>(ntiles, std::max(1., floor(budget / ((double)B * TILE * sizeof(double)))));
-    const int part_stride = (ntiles + 3) / 4 * 4 + 4;  // (combine_range reads whole 16-byte words)
-    const size_t nm = (size_t)n_trials * C;
-    double *img = nullptr, *src = nullptr, *lik = nullptr, *part_sum = nullptr, *d_tot = nullptr, *d_pi = nullptr, *PT = nullptr;
-    double *V = nullptr, *U = nullptr, *work = nullptr;
-    int32_t *cnt = nullptr, *status = nullptr, *Vcnt = nullptr, *Ucnt = nullptr, *wcnt = nullptr;
+    OutsideScratch sc;
+    sc.plan(p, s, oc);
+    const size_t nm = (size_t)n_trials * C, nq = q_dense ? nm * D * D : nm * p->K, np = (size_t)n_trials * sc.part_stride;
+    double *img = nullptr, *src = nullptr, *lik = nullptr, *part_sum = nullptr, *d_tot = nullptr;
+    int32_t *cnt = nullptr, *status = nullptr;
     long long *part_cnt = nullptr;
-    int *part_flag = nullptr, *d_branch = nullptr, *d_off = nullptr, *d_idx = nullptr;
-    int4 *d_prog = nullptr;
+    int *part_flag = nullptr;
     HIPCHK(blk.get(&img, nm * MS));
-    HIPCHK(blk.get(&src, q_dense ? nm * D * D : nm * p->K));
+    HIPCHK(blk.get(&src, nq));
     HIPCHK(blk.get(&lik, (size_t)n_trials * s.S_pad));
     HIPCHK(blk.get(&cnt, (size_t)n_trials * s.S_pad));
-    HIPCHK(blk.get(&part_sum, (size_t)n_trials * part_stride));
-    HIPCHK(blk.get(&part_cnt, (size_t)n_trials * part_stride));
-    HIPCHK(blk.get(&part_flag, (size_t)n_trials * part_stride));
+    HIPCHK(blk.get(&part_sum, np));
+    HIPCHK(blk.get(&part_cnt, np));
+    HIPCHK(blk.get(&part_flag, np));
     HIPCHK(blk.get(&d_tot, (size_t)n_trials));
     HIPCHK(blk.get(&status, 1));
-    HIPCHK(blk.get(&d_pi, pi_pad.size()));
-    HIPCHK(blk.get(&d_prog, prog.size()));
-    HIPCHK(blk.get(&d_branch, (size_t)n_branch));
-    HIPCHK(blk.get(&d_off, (size_t)n_branch + 1));
-    HIPCHK(blk.get(&d_idx, (size_t)n_trials));
-    if (!nuc) HIPCHK(blk.get(&PT, (size_t)B * DP * DP));
-    HIPCHK(blk.get(&V, (size_t)B * ct * TILE));
-    HIPCHK(blk.get(&Vcnt, (size_t)B * ct * TP));
-    HIPCHK(blk.get(&U, (size_t)I * ct * TILE));
-    HIPCHK(blk.get(&Ucnt, (size_t)I * ct * TP));
-    HIPCHK(blk.get(&work, (size_t)ct * 2 * maxk * TILE));
-    HIPCHK(blk.get(&wcnt, (size_t)ct * 2 * maxk * TP));
+    if (sc.get(p, oc, blk)) return -1;
     HIPCHK(hipMemsetAsync(status, 0, sizeof(int32_t), s.stream));
-    HIPCHK(hipMemcpyAsync(src, q_dense ? q_dense : coeffs, (q_dense ? nm * D * D : nm * p->K) * sizeof(double), hipMemcpyHostToDevice,
-                          s.stream));
-    HIPCHK(hipMemcpyAsync(d_pi, pi_pad.data(), pi_pad.size() * sizeof(double), hipMemcpyHostToDevice, s.stream));
-    HIPCHK(hipMemcpyAsync(d_prog, prog.data(), prog.size() * sizeof(int4), hipMemcpyHostToDevice, s.stream));
-    HIPCHK(hipMemcpyAsync(d_branch, branch.data(), branch.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
-    HIPCHK(hipMemcpyAsync(d_off, tr_off.data(), tr_off.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
-    HIPCHK(hipMemcpyAsync(d_idx, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(src, q_dense ? q_dense : coeffs, nq * sizeof(double), hipMemcpyHostToDevice, s.stream));
+    if (sc.upload(p, oc, s.stream)) return -1;
     // trial images: one launch of the exponential kernels into the call's own slots (slot = trial * C + class)
     ExpmArgs ea;
     ea.n = (int)nm, ea.D = (int)D, ea.status = status;
@@ -303,46 +254,26 @@ int trials_common(const char *what, hyphy_hip_partition *p, int64_t n_trials, co
     launch_expm(ea, s.stream);
     set_last_expm_kernel(expm_before);
     HIPCHK(hipGetLastError());
-    for (int tile0 = 0; tile0 < ntiles; tile0 += ct) {
-      const int nt = std::min(ct, ntiles - tile0);
-      for (int c = 0; c < C; c++) {
-        TrialArgs ta;
-        ta.NW = NW, ta.L = (int)L, ta.S_pad = s.S_pad, ta.ntiles = s.ntiles, ta.tile0 = tile0, ta.ct = ct;
-        ta.C = C, ta.cls = c, ta.first = c == 0, ta.last = c == C - 1, ta.b0 = 0;
-        ta.w = C > 1 ? weights[c] : 1.0;
-        ta.branch = d_branch, ta.tr_off = d_off, ta.tr_idx = d_idx;
-        ta.img = img;
-        ta.V = V, ta.Vcnt = Vcnt;
-        ta.partials = s.partials + (size_t)c * s.partial_stride;
-        ta.counts = s.counts + (size_t)c * I * s.S_pad;
-        ta.codes_tile = s.codes_tile, ta.codes = s.codes;
-        ta.ambig = s.ambig, ta.freq = s.freq;
-        ta.lik = lik, ta.cnt = cnt;
-        ta.part_sum = part_sum, ta.part_cnt = part_cnt, ta.part_flag = part_flag, ta.part_stride = part_stride;
-        WalkArgs a = walk_args(p, s, c);
-        a.prog = d_prog, a.pi = d_pi, a.PT = PT;
-        a.U = U, a.Ucnt = Ucnt, a.work = work, a.wcnt = wcnt;
-        const int unit = nuc ? TP : 1;  // (4 states: the walk counts patterns)
-        a.first = tile0 * unit, a.count = nt * unit, a.chunk = ct * unit;
-        const OutsideStore o = {V, Vcnt};
-        if (nuc) {
-          hipLaunchKernelGGL(outside_store_nuc_kernel, dim3((unsigned)((a.count + 255) / 256)), dim3(256), 0, s.stream, a, o);
-        } else {
-          if (C > 1 || tile0 == 0)
-            hipLaunchKernelGGL(marg_transpose_kernel, dim3((unsigned)B), dim3(256), 0, s.stream, a.Pfrag, a.PTg, PT, NW, (int)L);
-          LAUNCH_NW(outside_store_kernel, NW, dim3((unsigned)nt), dim3(64), s.stream, a, o);
-        }
-        for (ta.b0 = 0; ta.b0 < n_branch; ta.b0 += 65535) {
-          const dim3 grid((unsigned)nt, (unsigned)std::min(65535, n_branch - ta.b0)), block(64);
-          if (nuc) hipLaunchKernelGGL(branch_trials_nuc_kernel, grid, block, 0, s.stream, ta);
-          else LAUNCH_NW(branch_trials_kernel, NW, grid, block, s.stream, ta);
-        }
-        HIPCHK(hipGetLastError());
-      }
-    }
-    hipLaunchKernelGGL(trials_reduce_kernel, dim3((unsigned)n_trials), dim3(64), 0, s.stream, part_sum, part_cnt, part_flag, ntiles,
-                       part_stride, d_tot);
-    if (&s == &p->shards[0]) p->last_reduce = {"wave", ntiles, false};  // (one wave per trial over its own partials)
+    const int walked = outside_chunks(p, s, oc, sc, weights, [&](const WalkArgs &a, const OutsideSlice &sl, dim3 grid) {
+      TrialArgs ta;
+      ta.NW = NW, ta.L = a.L, ta.S_pad = a.S_pad, ta.ntiles = a.ntiles, ta.tile0 = sl.tile0, ta.ct = sl.ct;
+      ta.C = sl.C, ta.cls = sl.cls, ta.first = sl.first, ta.last = sl.last, ta.b0 = sl.b0;
+      ta.w = sl.w;
+      ta.branch = sl.branch, ta.tr_off = sl.off, ta.tr_idx = sl.idx;
+      ta.img = img;
+      ta.V = sl.V, ta.Vcnt = sl.Vcnt;
+      ta.partials = a.partials, ta.counts = a.counts;
+      ta.codes_tile = a.codes_tile, ta.codes = a.codes;
+      ta.ambig = a.ambig, ta.freq = s.freq;
+      ta.lik = lik, ta.cnt = cnt;
+      ta.part_sum = part_sum, ta.part_cnt = part_cnt, ta.part_flag = part_flag, ta.part_stride = sl.part_stride;
+      if (nuc) hipLaunchKernelGGL(branch_trials_nuc_kernel, grid, dim3(64), 0, s.stream, ta);
+      else LAUNCH_NW(branch_trials_kernel, NW, grid, dim3(64), s.stream, ta);
+    });
+    if (walked) return -1;
+    hipLaunchKernelGGL(trials_reduce_kernel, dim3((unsigned)n_trials), dim3(64), 0, s.stream, part_sum, part_cnt, part_flag, sc.ntiles,
+                       sc.part_stride, d_tot);
+    if (&s == &p->shards[0]) p->last_reduce = {"wave", sc.ntiles, false};  // (one wave per trial over its own partials)
     HIPCHK(hipGetLastError());
     int32_t h_status = 0;
     HIPCHK(hipMemcpyAsync(totals.data(), d_tot, (size_t)n_trials * sizeof(double), hipMemcpyDeviceToHost, s.stream));
@@ -352,17 +283,8 @@ int trials_common(const char *what, hyphy_hip_partition *p, int64_t n_trials, co
       return fail(pre + "Failed to compute a valid transition matrix; this is usually caused by ill-conditioned rate matrices "
                         "(e.g. very large rate values)");
     for (int64_t t = 0; t < n_trials; t++) parts[(size_t)t].push_back(totals[(size_t)t]);
-    // per-pattern results -> the caller's pattern order: out[trial][caller pattern]
-    if (site_lik_out) {
-      h_l.resize((size_t)n_trials * s.S_pad);
-      HIPCHK(hipMemcpy(h_l.data(), lik, h_l.size() * sizeof(double), hipMemcpyDeviceToHost));
-      rows_to_caller(p, s, h_l.data(), (size_t)s.S_pad, n_trials, s.S, site_lik_out);
-    }
-    if (site_scaler_out) {
-      h_c.resize((size_t)n_trials * s.S_pad);
-      HIPCHK(hipMemcpy(h_c.data(), cnt, h_c.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-      rows_to_caller(p, s, h_c.data(), (size_t)s.S_pad, n_trials, s.S, site_scaler_out);
-    }
+    if (site_lik_out && download_rows(p, s, lik, n_trials, site_lik_out)) return -1;
+    if (site_scaler_out && download_rows(p, s, cnt, n_trials, site_scaler_out)) return -1;
   }
   for (int64_t t = 0; t < n_trials; t++) logl_out[t] = combine(parts[(size_t)t]);
   return 0;

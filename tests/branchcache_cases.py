@@ -223,6 +223,22 @@ def class_cases():
     return out
 
 
+def chunked_class_case(D, S):
+    """``class_cases``' recipe (three rate classes with off-diagonals 1e-2, 1e-12, 1e-30, weights 0.5, 0.3, 0.2) on the shape the
+    chunking tests walk in chunks: the 32-taxon binary tree (62 branches), ``S`` patterns, twelve sampled branches."""
+    rng = np.random.default_rng(7360 + D)
+    fp, L = sf.balanced_tree(2, 5)
+    codes = _mixed_patterns(rng, fp, L, D, S, 4, lambda l: l % 5 == 0, False)
+    B = len(fp) - 1
+    P = np.stack([sf.near_identity(rng, B, D, e, spread=D * e < 0.3) for e in (1e-2, 1e-12, 1e-30)])
+    pi = rng.random(D) + 0.1
+    cs = sf._case(f"wide_bal2x5_classes_D{D}", D, fp, L, codes, P, rng, root_freqs=pi / pi.sum(), weights=np.array([0.5, 0.3, 0.2]))
+    cs["seed"] = 7360 + D
+    cs["eps"] = 1e-12
+    cs["branches"] = [int(b) for b in rng.choice(B, size=12, replace=False)]
+    return cs
+
+
 # ---- trial matrices and references ------------------------------------------------------------------------------------------------
 
 def trials(cs, node, cls=None):

@@ -187,6 +187,33 @@ def test_chunks_of_tiles_four_states(monkeypatch):
         assert _same(whole, chunked)
 
 
+@pytest.mark.parametrize("D,S,mb", [(33, 70, "1"), (4, 200, "0.1")], ids=["D33", "D4"])
+def test_rate_classes_in_chunks_of_tiles(D, S, mb, monkeypatch):
+    """Three rate classes on the chunked shapes: 33 states, five tiles in chunks of 2, 2 and 1; 4 states, four waves of 64 patterns,
+    one a chunk.  The transposed images belong to a class, so every class of every chunk needs its own: the unchunked call is held
+    to the reference as ``test_rate_classes`` holds it, and the chunked call gives the same bits."""
+    _env(monkeypatch)
+    cs = bc.chunked_class_case(D, S)
+    B = len(cs["flat_parents"]) - 1
+    w = cs["weights"]
+    if D == 33:
+        tile_bytes = B * 16 * 48 * 8
+        assert (S + 15) // 16 == 5 and (1 << 20) // tile_bytes == 2, tile_bytes
+    else:
+        assert (S + 63) // 64 == 4 and int(0.1 * (1 << 20)) // (B * 256 * 8) == 0
+    gl = _gen_list(cs, C=3)
+    with _mk(cs, C=3) as part:
+        for c in range(3):
+            ref = bc.reference(cs, key="base", cls=c)
+            _hold(f"{cs['name']} class {c} pass", _full(cs, part, cs["P"][c], cat=c), ref["site_logl"], ref["logl"])
+        whole = _call(part, gl, weights=w)
+        _hold_all(cs, f"{cs['name']} weights {list(w)}", gl, whole, weights=w)
+        monkeypatch.setenv("HYPHY_HIP_TRIALS_MB", mb)
+        chunked = _call(part, gl, weights=w)
+        monkeypatch.delenv("HYPHY_HIP_TRIALS_MB")
+        assert _same(whole, chunked)
+
+
 # ---- 5 ----------------------------------------------------------------------------------------------------------------------------
 
 FORMS = {"lazy": dict(HYPHY_HIP_REPEATS="0"),

@@ -269,6 +269,43 @@ def test_chunks_of_tiles(depth, monkeypatch):
             assert a.tobytes() == b.tobytes()
 
 
+@pytest.mark.parametrize("D,S,mb", [(33, 70, "1"), (4, 200, "0.1")], ids=["D33", "D4"])
+def test_rate_classes_in_chunks_of_tiles(D, S, mb, monkeypatch):
+    """Three rate classes on the chunked shapes: 33 states, five tiles in chunks of 2, 2 and 1; 4 states, four waves of 64 patterns,
+    one a chunk.  The transposed images belong to a class, so every class of every chunk needs its own: the unchunked call is held
+    to the reference as ``test_rate_classes`` holds it, and the chunked call gives the same bits."""
+    _env(monkeypatch)
+    cs = bc.chunked_class_case(D, S)
+    B = len(cs["flat_parents"]) - 1
+    w = cs["weights"]
+    if D == 33:
+        tile_bytes = B * 16 * 48 * 8
+        assert (S + 15) // 16 == 5 and (1 << 20) // tile_bytes == 2, tile_bytes
+    else:
+        assert (S + 63) // 64 == 4 and int(0.1 * (1 << 20)) // (B * 256 * 8) == 0
+    with _mk(cs, C=3) as part:
+        for c in range(3):
+            ref = bc.reference(cs, key="base", cls=c)
+            _hold(f"{cs['name']} class {c} pass", _full(cs, part, cs["P"][c], cat=c), ref["site_logl"], ref["logl"])
+        per = {node: [bc.trials(cs, node, c) for c in range(3)] for node in cs["branches"]}
+        tl = [(node, k) for k in range(len(bc.TRIAL_KINDS)) for node in cs["branches"]]
+        nodes = np.array([t[0] for t in tl], dtype=np.int64)
+        Ms = np.stack([np.stack([per[node][c][k][1] for c in range(3)]) for node, k in tl])
+        whole = part.branch_trials(nodes, Ms, weights=w, q_is_probability=True, per_site=True)
+        for t, (node, k) in enumerate(tl):
+            P = cs["P"].copy()
+            P[:, node] = Ms[t]
+            ref = sf.prune(cs["D"], cs["flat_parents"], cs["L"], cs["leaf_codes"], cs["ambig"], cs["pattern_freq"], P, cs["root_freqs"],
+                           weights=w)
+            _hold(f"{cs['name']} branch {node} {bc.TRIAL_KINDS[k]}", (float(whole[0][t]), whole[1][t], whole[2][t]),
+                  ref["site_logl"], ref["logl"])
+        monkeypatch.setenv("HYPHY_HIP_TRIALS_MB", mb)
+        chunked = part.branch_trials(nodes, Ms, weights=w, q_is_probability=True, per_site=True)
+        monkeypatch.delenv("HYPHY_HIP_TRIALS_MB")
+        for a, b in zip(whole, chunked):
+            assert a.tobytes() == b.tobytes()
+
+
 # ---- 8 ----------------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("name", ["bal2x4_D5", "bal2x4_D33", "bal2x4_D61", "bal2x4_D4"])
