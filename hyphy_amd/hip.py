@@ -23,7 +23,7 @@ EXPORTS = [
     "hyphy_hip_expm_batch", "hyphy_hip_set_q_templates", "hyphy_hip_build_q", "hyphy_hip_q_buffer",
     "hyphy_hip_evaluate_built", "hyphy_hip_evaluate_built_sites", "hyphy_hip_update_q_templates", "hyphy_hip_evaluate_categories_built", "hyphy_hip_evaluate_categories_built_sites", "hyphy_hip_prune_timings", "hyphy_hip_prune_launches",
     "hyphy_hip_prune_kernel_name", "hyphy_hip_last_prune_form", "hyphy_hip_last_reduce_form", "hyphy_hip_branch_cache_build", "hyphy_hip_branch_cache_evaluate",
-    "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_joint_ancestral", "hyphy_hip_sample_ancestral", "hyphy_hip_sample_uniforms", "hyphy_hip_simulate", "hyphy_hip_simulate_uniforms", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_branch_derivatives", "hyphy_hip_branch_derivatives_built", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
+    "hyphy_hip_set_pinned_states", "hyphy_hip_marginal_ancestral", "hyphy_hip_plan_marginal", "hyphy_hip_joint_ancestral", "hyphy_hip_sample_ancestral", "hyphy_hip_sample_uniforms", "hyphy_hip_simulate", "hyphy_hip_simulate_uniforms", "hyphy_hip_branch_trials", "hyphy_hip_branch_trials_built", "hyphy_hip_branch_derivatives", "hyphy_hip_branch_derivatives_built", "hyphy_hip_branch_sensitivities", "hyphy_hip_branch_gradient", "hyphy_hip_branch_gradient_built", "hyphy_hip_expm_frechet_adjoint_batch", "hyphy_hip_site_fits_evaluate", "hyphy_hip_site_fits_evaluate_mixture", "hyphy_hip_site_fits_kernel_ms",
     "hyphy_hip_synchronize", "hyphy_hip_stream", "hyphy_hip_set_stream", "hyphy_hip_last_timings", "hyphy_hip_set_timing_detail", "hyphy_hip_schedule_info", "hyphy_hip_set_repeats", "hyphy_hip_repeat_stats", "hyphy_hip_plan_repeats", "hyphy_hip_plan_repeat_layout", "hyphy_hip_plan_trunk_walk", "hyphy_hip_plan_nucgen", "hyphy_hip_plan_switches", "hyphy_hip_comm_init_host", "hyphy_hip_evaluate_exchange", "hyphy_hip_evaluate_built_exchange",
     "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error", "hyphy_hip_last_expm_kernel",
     "hyphy_hip_evaluate_categories_mixture", "hyphy_hip_evaluate_categories_mixture_built",
@@ -172,6 +172,13 @@ def load():
     for fn in (lib.hyphy_hip_branch_derivatives, lib.hyphy_hip_branch_derivatives_built):
         fn.restype = C.c_int
         fn.argtypes = [vp, C.c_int64, lp, dp, dp, dp, dp, lp, dp, dp]
+    lib.hyphy_hip_branch_sensitivities.restype = C.c_int
+    lib.hyphy_hip_branch_sensitivities.argtypes = [vp, C.c_int64, lp, dp, dp, lp]
+    for fn in (lib.hyphy_hip_branch_gradient, lib.hyphy_hip_branch_gradient_built):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, C.c_int64, lp, dp, dp, dp, lp]
+    lib.hyphy_hip_expm_frechet_adjoint_batch.restype = C.c_int
+    lib.hyphy_hip_expm_frechet_adjoint_batch.argtypes = [C.c_int64, C.c_int64, dp, dp, dp]
     lib.hyphy_hip_plan_marginal.restype = C.c_int64
     lib.hyphy_hip_plan_marginal.argtypes = [C.c_int64, C.c_int64, lp, lp, C.c_int64]
     lib.hyphy_hip_plan_trunk_walk.restype = C.c_int64
@@ -478,6 +485,20 @@ def expm_batch(Q: np.ndarray) -> np.ndarray:
     P = np.empty_like(Qb)
     _check(load().hyphy_hip_expm_batch(Qb.shape[1], Qb.shape[0], _d(Qb), _d(P)))
     return P[0] if single else P
+
+
+def expm_frechet_adjoint_batch(Q: np.ndarray, W: np.ndarray) -> np.ndarray:
+    """Batched L(Q^T, W) on the device, L(A, E) = int_0^1 exp(sA) E exp((1 - s)A) ds: with W = d f / d exp(Q) it is d f / d Q, the
+    entries of Q taken as independent.  NaN where a matrix cannot be handled."""
+    Q = np.ascontiguousarray(Q, dtype=np.float64)
+    W = np.ascontiguousarray(W, dtype=np.float64)
+    if Q.shape != W.shape or Q.ndim not in (2, 3) or Q.shape[-1] != Q.shape[-2]:
+        raise ValueError(f"expected two arrays of [n, D, D], got {Q.shape} and {W.shape}")
+    single = Q.ndim == 2
+    Qb, Wb = (Q[None], W[None]) if single else (Q, W)
+    out = np.empty_like(Qb)
+    _check(load().hyphy_hip_expm_frechet_adjoint_batch(Qb.shape[1], Qb.shape[0], _d(Qb), _d(Wb), _d(out)))
+    return out[0] if single else out
 
 
 def sample_uniforms(seed: int, n_rep: int, I: int, n_sites: int) -> np.ndarray:
@@ -1136,6 +1157,44 @@ class HipPartition:
         ``set_q_templates`` (``coeffs``: [n, K] or [n, C, K]), as ``build_q`` forms rate matrices."""
         K = int(np.asarray(coeffs).shape[-1])
         return self._derivative_call("hyphy_hip_branch_derivatives_built", nodes, coeffs, (K,), weights, per_site)
+
+    # -- the gradient of log L in every matrix entry, rate-matrix entry and template coefficient ----
+    def _gradient_call(self, fn, nodes, mats, tail, out_tail, weights):
+        nd = np.ascontiguousarray(nodes, dtype=np.int64).reshape(-1)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            if w.shape != (self.C,):
+                raise ValueError(f"expected {self.C} class weights, got {w.shape}")
+        out = np.zeros((len(nd), self.C) + tuple(out_tail))
+        sk = np.zeros(len(nd), dtype=np.int64)
+        if mats is None:
+            _check(getattr(self._lib, fn)(self._h, len(nd), _l(nd), _d(w), _d(out), _l(sk)))
+        else:
+            m = np.ascontiguousarray(mats, dtype=np.float64)
+            if m.size != len(nd) * self.C * int(np.prod(tail)):
+                raise ValueError(f"expected [{len(nd)}, {self.C}, {', '.join(str(x) for x in tail)}] values, got {m.shape}")
+            _check(getattr(self._lib, fn)(self._h, len(nd), _l(nd), _d(m), _d(w), _d(out), _l(sk)))
+        return (out[:, 0] if self.C == 1 else out), sk
+
+    def branch_sensitivities(self, nodes, weights=None):
+        """(W, skipped): W[t] = d log L / d P of branch ``nodes[t]``, [n, D, D] (or [n, C, D, D]: class c's block is the derivative
+        in class c's matrix and contains its weight), everything as at the last evaluation of every class; ``skipped``: the patterns
+        of positive frequency whose likelihood is exactly 0.  Holds for any resident matrix.  Nothing on the device changes."""
+        return self._gradient_call("hyphy_hip_branch_sensitivities", nodes, None, None, (self.D, self.D), weights)
+
+    def branch_gradient(self, nodes, q_dense, weights=None):
+        """(S, skipped): S[t] = d log L / d Q of branch ``nodes[t]`` where its resident matrix is exp(``q_dense[t]``) ([n, D, D] or
+        [n, C, D, D]), the entries of Q taken as independent, the diagonal included.  For a mixture branch pass a component's rate
+        matrix and multiply the result by that component's mixture weight."""
+        return self._gradient_call("hyphy_hip_branch_gradient", nodes, q_dense, (self.D, self.D), (self.D, self.D), weights)
+
+    def branch_gradient_built(self, nodes, coeffs, weights=None):
+        """(grad, skipped): grad[t][k] = d log L / d ``coeffs[t][k]`` where the resident matrix of branch ``nodes[t]`` is the
+        exponential of the rate matrix ``build_q`` forms from ``coeffs[t]`` ([n, K] or [n, C, K]) over the templates of
+        ``set_q_templates``."""
+        K = int(np.asarray(coeffs).shape[-1])
+        return self._gradient_call("hyphy_hip_branch_gradient_built", nodes, coeffs, (K,), (K,), weights)
 
     # -- branch cache (one-branch line searches) --------------------------------------------------
     def branch_cache_build(self, node: int, cat: int = 0):

@@ -554,6 +554,57 @@ int hyphy_hip_branch_derivatives_built(hyphy_hip_partition *p, int64_t n, const 
                                        const double *weights /* [C] or NULL */, double *d1_out, double *d2_out, int64_t *skipped_out,
                                        double *site_d1_out, double *site_d2_out);
 
+/* ---- the gradient of log L in every matrix entry, rate-matrix entry and template coefficient, one outside pass ----
+ * The exact first derivatives of everything that does not merely scale a branch's matrix (omega, kappa, the nucleotide rates, a
+ * per-branch (alpha, beta) pair, a mixture component's omega).  With V the outside vector of branch b, in_b the conditional below
+ * the branch (the persisted vector of an internal child, the state or ambiguity vector of a leaf) and L_s the pattern's likelihood
+ * (mixed over the classes when C > 1), per branch and class c
+ *   W_b[i][j] = d log L / d P_b[i][j] = sum_s f_s w_c V_{b,s}[i] in_{b,s}[j] / L_s          (hyphy_hip_branch_sensitivities)
+ * whatever P_b was made from (plain, template, mixture or trial matrices).  Where P_b = exp(Q_b), the chain rule is the adjoint of
+ * the exponential's Frechet derivative L(A, E) = int_0^1 e^{sA} E e^{(1-s)A} ds:
+ *   S_b = d log L / d Q_b = L(Q_b^T, W_b)                                                   (hyphy_hip_branch_gradient)
+ * with the entries of Q_b taken as independent, the diagonal included; and for Q_b = sum_k x_bk T_k off the diagonal, diagonal
+ * -(row sum),
+ *   d log L / d x_bk = sum_{i != j} T_k[i][j] (S_b[i][j] - S_b[i][i])                       (hyphy_hip_branch_gradient_built)
+ * from which the host chains any parameter by a K-term dot product per branch.
+ *   nodes    [n]            node codes (leaf l -> l, internal i -> L + i, never the root), any order, repeats allowed
+ *   weights  [C] (NULL when C == 1)
+ *   q_dense  [n][C][D*D]    the scaled rate matrices the branches were last evaluated with, row-major
+ *   coeffs   [n][C][K]      their coefficient rows over the templates of hyphy_hip_set_q_templates (the matrices are formed as
+ *                           hyphy_hip_build_q forms them, into scratch of the call, not into the partition's Q buffer)
+ *   dp_out, dq_out [n][C][D*D] row-major; grad_out [n][C][K]; skipped_out [n] or NULL
+ * Class c's block of an output is the derivative in class c's matrix: it already contains the weight w_c and the mixed L_s.  The
+ * 2^64 exponents of V, in_b and the mixed likelihood are aligned as hyphy_hip_branch_derivatives aligns them; a class that is exactly
+ * zero at a pattern, or has weight 0, contributes nothing there and does not move the alignment.  A pattern with f_s == 0 takes no
+ * part.  A pattern of positive frequency whose mixed L_s is exactly 0 takes no part and is counted in skipped_out[t].  A NaN in a
+ * value used by a pattern of positive frequency makes the request's whole output block NaN.
+ * Mixture branches: hyphy_hip_branch_sensitivities is exact for them; for hyphy_hip_branch_gradient the caller passes component m's
+ * rate matrix and multiplies the result by that component's mixture weight.
+ * A rate matrix that cannot be handled (a NaN, an infinity-norm of 2^40 or more, an overflow) is a hard error of the two gradient
+ * entry points, with hyphy_hip_last_error set.
+ * Call after an evaluation of every class.  Leaves no state behind, as hyphy_hip_branch_derivatives: the device's matrices and images,
+ * the Q buffer, the schedules, the tuner's state, the class tables, the branch-cache slots, the lazy-persistence flags,
+ * hyphy_hip_last_expm_kernel and hyphy_hip_last_reduce_form are what they were.  Two identical calls give identical bits: every
+ * (branch, class, segment of 512 patterns) leaves one partial, the partials are summed in ascending segment order and the shards in
+ * shard order; the order may depend on the budget, the allowances do not.  (L_s is formed at the requested branch of lowest node code:
+ * calls that request different sets of branches may differ in the last bits of a branch they share.)  Chunks of tiles and scratch as hyphy_hip_branch_trials,
+ * under the same budget (HYPHY_HIP_TRIALS_MB); with C > 1 the walk runs twice (the mixed L_s must be complete before any class's sum).
+ * 4-state partitions are served; there is no "unsupported" return.  Returns < 0 for a NULL partition or output, an active pin, a class
+ * never evaluated, C > 1 without weights, a node code out of range or the root's, templates not set (_built); n == 0 returns 0 and
+ * writes nothing.
+ * Out of scope: the derivatives in the class weights and in the root frequencies (the host has both from the per-class per-pattern
+ * values), an adapter hook, and second derivatives. */
+int hyphy_hip_branch_sensitivities(hyphy_hip_partition *p, int64_t n, const int64_t *nodes, const double *weights /* [C] or NULL */,
+                                   double *dp_out, int64_t *skipped_out);
+int hyphy_hip_branch_gradient(hyphy_hip_partition *p, int64_t n, const int64_t *nodes, const double *q_dense,
+                              const double *weights /* [C] or NULL */, double *dq_out, int64_t *skipped_out);
+int hyphy_hip_branch_gradient_built(hyphy_hip_partition *p, int64_t n, const int64_t *nodes, const double *coeffs,
+                                    const double *weights /* [C] or NULL */, double *grad_out, int64_t *skipped_out);
+/* Stand-alone, as hyphy_hip_expm_batch is for the exponential: out[m] = L(q[m]^T, w[m]), n matrices of D x D (2 <= D <= 64), row-major.
+ * Scaling X = q^T / 2^p with ||X||_inf <= 1/4, the degree-13 Taylor pair of exp and its derivative (remainder < 2.5e-18 ||w / 2^p||),
+ * p squarings L <- P L + L P, P <- P P; no row-sum correction is applied.  A matrix that cannot be handled gives NaN output. */
+int hyphy_hip_expm_frechet_adjoint_batch(int64_t D, int64_t n, const double *q_dense, const double *w_dense, double *out);
+
 /* ---- joint maximum-likelihood ancestral reconstruction ------------------------------------------------------
  * Replaces _TheTree::RecoverAncestralSequences (src/core/tree.cpp:4209-4510), the max-product pass behind
  * `ReconstructAncestors (lf)` without MARGINAL: per pattern an upward pass over the nodes in ascending node code
