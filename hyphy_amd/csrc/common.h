@@ -47,6 +47,24 @@ __host__ __device__ inline void frag_image_rc(int idx, int NW, int &row, int &co
     case 3: hipLaunchKernelGGL(kernel<3>, grid, block, 0, stream, __VA_ARGS__); break;       \
     default: hipLaunchKernelGGL(kernel<4>, grid, block, 0, stream, __VA_ARGS__); break;      \
   }
+// ... with `lds` bytes of dynamic LDS, behind the attribute that allows them.  hipFuncAttributeMaxDynamicSharedMemorySize is a
+// per-device property of the function: `set` is the caller's static bool [devices][5], indexed by `dev` and nw, and remembers only
+// THAT it was set, so `lds` must depend on nothing but nw.  A refused attribute returns through HIPCHK.
+#define LAUNCH_NW_DYN_LDS_(k, done, grid, block, lds, stream, ...)                                                        \
+  {                                                                                                                       \
+    if (!(done)) {                                                                                                        \
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+      (done) = true;                                                                                                      \
+    }                                                                                                                     \
+    hipLaunchKernelGGL(k, grid, block, lds, stream, __VA_ARGS__);                                                         \
+  }
+#define LAUNCH_NW_DYN_LDS(kernel, nw, set, dev, ...)                               \
+  switch (nw) {                                                                    \
+    case 1: LAUNCH_NW_DYN_LDS_(kernel<1>, set[dev][1], __VA_ARGS__) break;          \
+    case 2: LAUNCH_NW_DYN_LDS_(kernel<2>, set[dev][2], __VA_ARGS__) break;          \
+    case 3: LAUNCH_NW_DYN_LDS_(kernel<3>, set[dev][3], __VA_ARGS__) break;          \
+    default: LAUNCH_NW_DYN_LDS_(kernel<4>, set[dev][4], __VA_ARGS__) break;         \
+  }
 
 // Host-compiled schedule entry (int4), built by build_schedule() in api.hip:
 //   x  bits 0-1  kind: OPK_LEAF (group of <= 2 leaf children), OPK_INTERNAL (child vector in an LDS

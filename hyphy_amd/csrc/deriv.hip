@@ -15,9 +15,11 @@
 // [D x D] x [D x 16] products on the FP64 MFMA — the C/D fragment of G E is the B operand of G (G E) — and three row sums.  Classes
 // run one launch after another; the last class's launch forms r1, r2 and one partial record per (derivative, tile).
 // Reduction (derivs_reduce_kernel): one wave per derivative, combine.h's fixed-order compensated sum, once per total.
-// Nothing joins by order of arrival: two identical calls give identical bits.  The refusals, the scratch of the walk and the loop over
-// chunks of tiles and classes are outside_pass.h's, as for trials.hip and under the same budget (HYPHY_HIP_TRIALS_MB); all scratch
-// comes from the pool and goes back before the call returns.  The partition's matrices, images, schedules and caches are not written.
+// Nothing joins by order of arrival: two identical calls give identical bits.  The refusals, the scratch of the walk, the loop over
+// chunks of tiles and classes and KeepForms are outside_pass.h's, as for trials.hip and under the same budget (HYPHY_HIP_TRIALS_MB);
+// the kernels get (WalkArgs, OutsideSlice, DerivArgs) and take the branch, V, E (4 states: mat4_vec), the exponent alignment and the
+// wave sums of their records from outside.h; all scratch comes from the pool and goes back before the call returns.  The partition's
+// matrices, images, schedules and caches are not written.
 #include "combine.h"
 #include "devutil.h"
 #include "outside_pass.h"
@@ -28,50 +30,29 @@ using namespace hyhip;
 namespace hyhip {
 namespace {
 
-struct DerivArgs {
-  int NW, L, S_pad, tile0, ct;          // (4 states: tiles of 64 patterns)
-  int C, cls, first, last, b0;          // classes, class of this launch, it is the first / the last one, first branch of the grid
-  double w;                             // weight of this class (1 when C == 1)
-  const int *branch;                    // [branches with a derivative] node codes
-  const int *d_off, *d_idx;             // derivatives of branch k: d_idx[d_off[k] .. d_off[k + 1])
-  const double *img;                    // [n][C] generators: A-operand images (4 states: [16] row-major)
-  const double *V;                      // phase 1's blocks of this chunk
-  const int32_t *Vcnt;
-  const double *freq;
-  double *L0, *L1, *L2;                 // [n][S_pad] per pattern: classes mixed so far; behind the last class L1 = r1, L2 = r2
-  int32_t *cnt;                         // their common exponent
-  double *part_d1, *part_d2;            // [n][part_stride] per (derivative, tile): sum_s f_s r1, sum_s f_s r2
-  long long *part_skip;                 // patterns of positive frequency with L0 == 0
-  int *part_flag;                       // 2: not a number
-  int part_stride;
-};
-
-// hyphy_hip_last_reduce_form and hyphy_hip_last_expm_kernel answer behind the call what they answered before it
-struct KeepForms {
-  hyphy_hip_partition *p;
-  hyphy_hip_partition::ReduceForm reduce;
-  const char *expm;
-  ~KeepForms() {
-    p->last_reduce = reduce;
-    set_last_expm_kernel(expm);
-  }
+struct DerivArgs {             // the derivatives' own blocks, beside the WalkArgs and the OutsideSlice
+  const double *img;           // [n][C] generators: A-operand images (4 states: [16] row-major)
+  double *L0, *L1, *L2;        // [n][S_pad] per pattern: classes mixed so far; behind the last class L1 = r1, L2 = r2
+  int32_t *cnt;                // their common exponent
+  double *part_d1, *part_d2;   // [n][part_stride] per (derivative, tile): sum_s f_s r1, sum_s f_s r2
+  long long *part_skip;        // patterns of positive frequency with L0 == 0
+  int *part_flag;              // 2: not a number
 };
 
 // this class's (l0, l1, l2; exponent e) of pattern q into the mix of the classes before it, aligned on the smaller exponent as
 // mix_in of trials.hip aligns likelihoods.  A triple of exact zeros (a weight of 0, an impossible pattern) carries no exponent: it
 // leaves the others as they are, where aligning on its exponent could flush them to zero.
-__device__ __forceinline__ void mix3(const DerivArgs &a, size_t q, double &l0, double &l1, double &l2, int &e) {
-  l0 *= a.w, l1 *= a.w, l2 *= a.w;
-  if (a.first) return;
+__device__ __forceinline__ void mix3(const OutsideSlice &sl, const DerivArgs &a, size_t q, double &l0, double &l1, double &l2, int &e) {
+  l0 *= sl.w, l1 *= sl.w, l2 *= sl.w;
+  if (sl.first) return;
   const double o0 = a.L0[q], o1 = a.L1[q], o2 = a.L2[q];
   const int e_old = a.cnt[q];
   if (l0 == 0. && l1 == 0. && l2 == 0.) {
     l0 = o0, l1 = o1, l2 = o2, e = e_old;
   } else if (!(o0 == 0. && o1 == 0. && o2 == 0.)) {
-    const int e_new = min(e_old, e);
-    const double so = ldexp(1.0, -64 * (e_old - e_new)), sn = ldexp(1.0, -64 * (e - e_new));
+    double so, sn;
+    e = align_exponents(e_old, e, so, sn);
     l0 = o0 * so + l0 * sn, l1 = o1 * so + l1 * sn, l2 = o2 * so + l2 * sn;
-    e = e_new;
   }
 }
 
@@ -95,6 +76,20 @@ __device__ __forceinline__ void site_ratio(double l0, double l1, double l2, doub
   }
 }
 
+// the record of (derivative t, tile): the terms of its W lanes summed, written by lane 0
+template <int W>
+__device__ __forceinline__ void put_record(const OutsideSlice &sl, const DerivArgs &a, int t, int tile, int lane, double w1, double w2,
+                                           long long wskip, int wflag) {
+  w1 = wave_sum<W>(w1), w2 = wave_sum<W>(w2), wskip = wave_sum<W>(wskip), wflag = wave_or<W>(wflag);
+  if (lane == 0) {
+    const size_t pq = (size_t)t * sl.part_stride + tile;
+    a.part_d1[pq] = w1;
+    a.part_d2[pq] = w2;
+    a.part_skip[pq] = wskip;
+    a.part_flag[pq] = wflag;
+  }
+}
+
 __global__ __launch_bounds__(256) void deriv_image_kernel(const double *__restrict__ G, double *__restrict__ img, int D, int NW, int nuc) {
   const double *src = G + (size_t)blockIdx.x * D * D;
   if (nuc) {
@@ -111,24 +106,24 @@ __global__ __launch_bounds__(256) void deriv_image_kernel(const double *__restri
 }
 
 template <int NW>
-__global__ __launch_bounds__(64) void branch_derivs_kernel(WalkArgs wa, DerivArgs a) {
-  constexpr int NKK = 4 * NW, DP = 16 * NW, TILE = NKK * 64;
-  const int lane = threadIdx.x, g = lane >> 4, sl = lane & 15;
-  const int lt = blockIdx.x, tile = a.tile0 + lt, site = tile * 16 + sl;
-  const int bi = a.b0 + blockIdx.y, node = a.branch[bi];
+__global__ __launch_bounds__(64) void branch_derivs_kernel(WalkArgs wa, OutsideSlice sl, DerivArgs a) {
+  constexpr int NKK = 4 * NW, DP = 16 * NW;
+  const int lane = threadIdx.x, g = lane >> 4;
+  const int tile = sl.tile0 + blockIdx.x, site = tile * 16 + (lane & 15);
+  const int bi = sl.b0 + blockIdx.y;
   double V[NKK], E[NKK];
-  ld_vec<NKK>(a.V + ((size_t)node * a.ct + lt) * TILE, lane, V);
-  int bcnt = a.Vcnt[((size_t)node * a.ct + lt) * 16 + sl], ecnt;
-  edge_product<NW>(wa, make_int4(1, node, node >= a.L ? node - a.L : -1, 0), tile, lane, E, ecnt);
+  int bcnt, ecnt;
+  const int4 ce = branch_outside<NKK>(wa, sl, bi, tile, lane, V, bcnt);
+  edge_product<NW>(wa, ce, tile, lane, E, ecnt);
   bcnt += ecnt;
   double s0 = 0.;
 #pragma unroll
   for (int kk = 0; kk < NKK; kk++) s0 += V[kk] * E[kk];
   s0 = row_sum4(s0);
-  const double f = a.freq[site];
-  for (int k = a.d_off[bi]; k < a.d_off[bi + 1]; k++) {
-    const int t = a.d_idx[k];
-    const double *G = a.img + ((size_t)t * a.C + a.cls) * DP * DP;
+  const double f = sl.freq[site];
+  for (int k = sl.off[bi]; k < sl.off[bi + 1]; k++) {
+    const int t = sl.idx[k];
+    const double *G = a.img + ((size_t)t * sl.C + sl.cls) * DP * DP;
     double X[NKK];
     mfma_product<NW>(G, E, lane, X);
     double s1 = 0., s2 = 0.;
@@ -147,11 +142,11 @@ __global__ __launch_bounds__(64) void branch_derivs_kernel(WalkArgs wa, DerivArg
     long long wskip = 0;
     int wflag = 0;
     if (g == 0) {
-      const size_t q = (size_t)t * a.S_pad + site;
+      const size_t q = (size_t)t * wa.S_pad + site;
       double l0 = s0;
       int e = bcnt;
-      mix3(a, q, l0, s1, s2, e);
-      if (a.last) {
+      mix3(sl, a, q, l0, s1, s2, e);
+      if (sl.last) {
         double r1, r2;
         site_ratio(l0, s1, s2, f, r1, r2, w1, w2, wskip, wflag);
         s1 = r1, s2 = r2;
@@ -161,59 +156,37 @@ __global__ __launch_bounds__(64) void branch_derivs_kernel(WalkArgs wa, DerivArg
       a.L2[q] = s2;
       a.cnt[q] = e;
     }
-    if (a.last) {
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) {
-        w1 += __shfl_xor(w1, off);
-        w2 += __shfl_xor(w2, off);
-        wskip += __shfl_xor(wskip, off);
-        wflag |= __shfl_xor(wflag, off);
-      }
-      if (lane == 0) {
-        const size_t pq = (size_t)t * a.part_stride + tile;
-        a.part_d1[pq] = w1;
-        a.part_d2[pq] = w2;
-        a.part_skip[pq] = wskip;
-        a.part_flag[pq] = wflag;
-      }
-    }
+    if (sl.last) put_record<16>(sl, a, t, tile, lane, w1, w2, wskip, wflag);
   }
 }
 
 // 4 states: one thread per pattern, one wave per (branch, 64 patterns)
-__global__ __launch_bounds__(64) void branch_derivs_nuc_kernel(WalkArgs wa, DerivArgs a) {
-  const int lane = threadIdx.x;
-  const int lt = blockIdx.x, tile = a.tile0 + lt;
-  const size_t ls = (size_t)lt * 64 + lane, s = (size_t)tile * 64 + lane, CS = (size_t)a.ct * 64, SP = a.S_pad;
-  const int bi = a.b0 + blockIdx.y, node = a.branch[bi];
+__global__ __launch_bounds__(64) void branch_derivs_nuc_kernel(WalkArgs wa, OutsideSlice sl, DerivArgs a) {
+  const int lane = threadIdx.x, tile = sl.tile0 + blockIdx.x;
+  const size_t s = (size_t)tile * 64 + lane;
+  const int bi = sl.b0 + blockIdx.y;
   double V[4], in[4], E[4];
-  for (int j = 0; j < 4; j++) V[j] = a.V[((size_t)node * 4 + j) * CS + ls];
-  int bcnt = a.Vcnt[(size_t)node * CS + ls];
-  if (node >= a.L) {
-    for (int j = 0; j < 4; j++) in[j] = wa.partials[((size_t)(node - a.L) * 4 + j) * SP + s];
-    bcnt += wa.counts[(size_t)(node - a.L) * SP + s];
-  } else {
-    nuc_leaf_vec(wa, (int)wa.codes[(size_t)node * SP + s], in);
-  }
-  const double *P = wa.Prow + (size_t)node * 16;
-  for (int x = 0; x < 4; x++) E[x] = P[4 * x] * in[0] + P[4 * x + 1] * in[1] + P[4 * x + 2] * in[2] + P[4 * x + 3] * in[3];
-  const double s0 = (V[0] * E[0] + V[1] * E[1]) + (V[2] * E[2] + V[3] * E[3]);
-  const double f = a.freq[s];
-  for (int k = a.d_off[bi]; k < a.d_off[bi + 1]; k++) {
-    const int t = a.d_idx[k];
-    const double *G = a.img + ((size_t)t * a.C + a.cls) * 16;
+  int bcnt, ecnt;
+  const int4 ce = nuc_branch_outside(wa, sl, bi, tile, lane, V, bcnt);
+  nuc_child_vec(wa, ce, s, in, ecnt);
+  bcnt += ecnt;
+  mat4_vec(wa.Prow + (size_t)ce.y * 16, in, E);
+  const double s0 = dot4(V, E);
+  const double f = sl.freq[s];
+  for (int k = sl.off[bi]; k < sl.off[bi + 1]; k++) {
+    const int t = sl.idx[k];
+    const double *G = a.img + ((size_t)t * sl.C + sl.cls) * 16;
     double X[4], Y[4];
-    for (int x = 0; x < 4; x++) X[x] = G[4 * x] * E[0] + G[4 * x + 1] * E[1] + G[4 * x + 2] * E[2] + G[4 * x + 3] * E[3];
-    for (int x = 0; x < 4; x++) Y[x] = G[4 * x] * X[0] + G[4 * x + 1] * X[1] + G[4 * x + 2] * X[2] + G[4 * x + 3] * X[3];
-    double l0 = s0, l1 = (V[0] * X[0] + V[1] * X[1]) + (V[2] * X[2] + V[3] * X[3]);
-    double l2 = (V[0] * Y[0] + V[1] * Y[1]) + (V[2] * Y[2] + V[3] * Y[3]);
-    const size_t q = (size_t)t * SP + s;
+    mat4_vec(G, E, X);
+    mat4_vec(G, X, Y);
+    double l0 = s0, l1 = dot4(V, X), l2 = dot4(V, Y);
+    const size_t q = (size_t)t * wa.S_pad + s;
     int e = bcnt;
-    mix3(a, q, l0, l1, l2, e);
+    mix3(sl, a, q, l0, l1, l2, e);
     double w1 = 0., w2 = 0.;
     long long wskip = 0;
     int wflag = 0;
-    if (a.last) {
+    if (sl.last) {
       double r1, r2;
       site_ratio(l0, l1, l2, f, r1, r2, w1, w2, wskip, wflag);
       l1 = r1, l2 = r2;
@@ -222,22 +195,7 @@ __global__ __launch_bounds__(64) void branch_derivs_nuc_kernel(WalkArgs wa, Deri
     a.L1[q] = l1;
     a.L2[q] = l2;
     a.cnt[q] = e;
-    if (a.last) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        w1 += __shfl_xor(w1, off);
-        w2 += __shfl_xor(w2, off);
-        wskip += __shfl_xor(wskip, off);
-        wflag |= __shfl_xor(wflag, off);
-      }
-      if (lane == 0) {
-        const size_t pq = (size_t)t * a.part_stride + tile;
-        a.part_d1[pq] = w1;
-        a.part_d2[pq] = w2;
-        a.part_skip[pq] = wskip;
-        a.part_flag[pq] = wflag;
-      }
-    }
+    if (sl.last) put_record<64>(sl, a, t, tile, lane, w1, w2, wskip, wflag);
   }
 }
 
@@ -311,19 +269,10 @@ int derivs_common(const char *what, hyphy_hip_partition *p, int64_t n, const int
     if (coeffs) launch_build_q(s.templates, src, (int)nm, (int)p->K, (int)D, gq, s.stream);
     hipLaunchKernelGGL(deriv_image_kernel, dim3((unsigned)nm), dim3(256), 0, s.stream, coeffs ? gq : src, img, (int)D, NW, nuc ? 1 : 0);
     HIPCHK(hipGetLastError());
+    const DerivArgs da = {img, L0, L1, L2, cnt, part_d1, part_d2, part_skip, part_flag};
     const int walked = outside_chunks(p, s, oc, sc, weights, [&](const WalkArgs &a, const OutsideSlice &sl, dim3 grid) {
-      DerivArgs da;
-      da.NW = NW, da.L = a.L, da.S_pad = a.S_pad, da.tile0 = sl.tile0, da.ct = sl.ct;
-      da.C = sl.C, da.cls = sl.cls, da.first = sl.first, da.last = sl.last, da.b0 = sl.b0;
-      da.w = sl.w;
-      da.branch = sl.branch, da.d_off = sl.off, da.d_idx = sl.idx;
-      da.img = img;
-      da.V = sl.V, da.Vcnt = sl.Vcnt;
-      da.freq = s.freq;
-      da.L0 = L0, da.L1 = L1, da.L2 = L2, da.cnt = cnt;
-      da.part_d1 = part_d1, da.part_d2 = part_d2, da.part_skip = part_skip, da.part_flag = part_flag, da.part_stride = sl.part_stride;
-      if (nuc) hipLaunchKernelGGL(branch_derivs_nuc_kernel, grid, dim3(64), 0, s.stream, a, da);
-      else LAUNCH_NW(branch_derivs_kernel, NW, grid, dim3(64), s.stream, a, da);
+      if (nuc) hipLaunchKernelGGL(branch_derivs_nuc_kernel, grid, dim3(64), 0, s.stream, a, sl, da);
+      else LAUNCH_NW(branch_derivs_kernel, NW, grid, dim3(64), s.stream, a, sl, da);
     });
     if (walked) return -1;
     hipLaunchKernelGGL(derivs_reduce_kernel, dim3((unsigned)n), dim3(64), 0, s.stream, part_d1, part_d2, part_skip, part_flag, sc.ntiles,

@@ -4,7 +4,10 @@
 //   S_b       = d log L / d Q_b       = L(Q_b^T, W_b),   L(A, E) = int_0^1 e^{sA} E e^{(1-s)A} ds           (P_b = exp(Q_b))
 //   d log L / d x_bk                  = sum_{i != j} T_k[i][j] (S_b[i][j] - S_b[i][i])                      (Q_b = sum_k x_bk T_k)
 // Phase 1 (outside_store_kernel<NW>, outside_store_nuc_kernel of outside.h): the walk with the OutsideStore sink, as the branch trials
-// and the branch derivatives run it, under the same chunks of tiles and the same budget (outside_pass.h).
+// and the branch derivatives run it, under the same chunks of tiles and the same budget (outside_pass.h).  Like theirs, the kernels
+// below get (WalkArgs, OutsideSlice, GradArgs) and take the branch, its V, the conditional below it and the exponent alignment from
+// outside.h's phase-2 helpers (grad_accum_kernel: branch_entry once, outside_index per tile, its own quarter loads of V and of the
+// conditional — per-tile address helpers cost it 1 %); the adjoint's launch is common.h's LAUNCH_NW_DYN_LDS.
 // Pattern weights (grad_weight_kernel<NW>, grad_weight_nuc_kernel): per pattern l0 = V . (P in) at the first requested branch, as
 // deriv.hip forms it, mixed over the classes by weight with the exponents aligned on the smallest (mix3's rule: an exact zero carries
 // no exponent), then ginv = f_s / L_s (0: the pattern takes no part).  With one class this runs inside the chunk it serves; with several
@@ -33,54 +36,36 @@ constexpr int kSegPatterns = 512;  // a segment: 32 tiles of 16 patterns (4 stat
 constexpr int kTaylorDegree = 13;
 constexpr double kFrechetMaxNorm = 1099511627776.0;  // 2^40: beyond it the matrix is refused (output NaN)
 
-struct GradArgs {
-  int L, S_pad, tile0, ct, nt;  // (4 states: tiles of 64 patterns); nt: tiles of the chunk that exist
-  int C, cls, first, last, b0;
-  double w;                     // weight of this class (1 when C == 1)
-  const int *branch;            // [branches with a request] node codes
-  const double *V;              // phase 1's blocks of this chunk
-  const int32_t *Vcnt;
-  const double *freq;
-  double *Lm;                   // [S_pad] likelihood mixed over the classes so far
-  int32_t *em;                  // its exponent
-  int32_t *live;                // [C][S_pad] the class's weighted likelihood is not exactly 0
-  double *ginv;                 // [S_pad] f_s / L_s, 0 where the pattern takes no part
-  long long *tile_skip;         // [tiles] patterns of positive frequency with L_s == 0
+struct GradArgs {        // the gradient's own blocks, beside the WalkArgs and the OutsideSlice
+  double *Lm;            // [S_pad] likelihood mixed over the classes so far
+  int32_t *em;           // its exponent
+  int32_t *live;         // [C][S_pad] the class's weighted likelihood is not exactly 0
+  double *ginv;          // [S_pad] f_s / L_s, 0 where the pattern takes no part
+  long long *tile_skip;  // [tiles] patterns of positive frequency with L_s == 0
   int seg_tiles, nseg, D;
-  double *part;                 // [branches][C][nseg][D * D]
-};
-
-// hyphy_hip_last_reduce_form and hyphy_hip_last_expm_kernel answer behind the call what they answered before it (deriv.hip's)
-struct KeepForms {
-  hyphy_hip_partition *p;
-  hyphy_hip_partition::ReduceForm reduce;
-  const char *expm;
-  ~KeepForms() {
-    p->last_reduce = reduce;
-    set_last_expm_kernel(expm);
-  }
+  double *part;          // [branches][C][nseg][D * D]
 };
 
 // this class's l0 (exponent e) of pattern `site` into the mix; behind the last class ginv.  Returns 1 for a skipped pattern.
-__device__ __forceinline__ int mix_weight(const GradArgs &a, int site, double l0, int e) {
-  l0 *= a.w;
-  a.live[(size_t)a.cls * a.S_pad + site] = l0 != 0.;
-  if (!a.first) {
+__device__ __forceinline__ int mix_weight(const WalkArgs &wa, const OutsideSlice &sl, const GradArgs &a, int site, double l0, int e) {
+  l0 *= sl.w;
+  a.live[(size_t)sl.cls * wa.S_pad + site] = l0 != 0.;
+  if (!sl.first) {
     const double o = a.Lm[site];
     const int eo = a.em[site];
     if (l0 == 0.) {
       l0 = o, e = eo;
     } else if (o != 0.) {
-      const int en = min(eo, e);
-      l0 = o * ldexp(1.0, -64 * (eo - en)) + l0 * ldexp(1.0, -64 * (e - en));
-      e = en;
+      double so, sn;
+      e = align_exponents(eo, e, so, sn);
+      l0 = o * so + l0 * sn;
     }
   }
   a.Lm[site] = l0;
   a.em[site] = e;
   int skip = 0;
-  if (a.last) {
-    const double f = a.freq[site];
+  if (sl.last) {
+    const double f = sl.freq[site];
     double gi = 0.;
     if (f != 0.) {
       if (l0 == 0.) skip = 1;
@@ -91,120 +76,107 @@ __device__ __forceinline__ int mix_weight(const GradArgs &a, int site, double l0
   return skip;
 }
 
-// g_{s,c}: what multiplies V in^T of pattern `site` in class a.cls (e: exponent of V plus exponent of in)
-__device__ __forceinline__ double pattern_scale(const GradArgs &a, int site, int e) {
+// g_{s,c}: what multiplies V in^T of pattern `site` in class sl.cls (e: exponent of V plus exponent of in)
+__device__ __forceinline__ double pattern_scale(const WalkArgs &wa, const OutsideSlice &sl, const GradArgs &a, int site, int e) {
   double gs = a.ginv[site];
-  if (a.C > 1 && !a.live[(size_t)a.cls * a.S_pad + site]) gs = 0.;
-  return gs == 0. ? 0. : a.w * gs * ldexp(1.0, -64 * (e - a.em[site]));
+  if (sl.C > 1 && !a.live[(size_t)sl.cls * wa.S_pad + site]) gs = 0.;
+  return gs == 0. ? 0. : sl.w * gs * ldexp(1.0, -64 * (e - a.em[site]));
 }
 
 template <int NW>
-__global__ __launch_bounds__(64) void grad_weight_kernel(WalkArgs wa, GradArgs a) {
-  constexpr int NKK = 4 * NW, TILE = NKK * 64;
-  const int lane = threadIdx.x, g = lane >> 4, sl = lane & 15;
-  const int lt = blockIdx.x, tile = a.tile0 + lt, site = tile * 16 + sl;
-  const int node = a.branch[0];
+__global__ __launch_bounds__(64) void grad_weight_kernel(WalkArgs wa, OutsideSlice sl, GradArgs a) {
+  constexpr int NKK = 4 * NW;
+  const int lane = threadIdx.x, tile = sl.tile0 + blockIdx.x, site = tile * 16 + (lane & 15);
   double V[NKK], E[NKK];
-  ld_vec<NKK>(a.V + ((size_t)node * a.ct + lt) * TILE, lane, V);
-  int e = a.Vcnt[((size_t)node * a.ct + lt) * 16 + sl], ecnt;
-  edge_product<NW>(wa, make_int4(1, node, node >= a.L ? node - a.L : -1, 0), tile, lane, E, ecnt);
+  int e, ecnt;
+  const int4 ce = branch_outside<NKK>(wa, sl, 0, tile, lane, V, e);
+  edge_product<NW>(wa, ce, tile, lane, E, ecnt);
   e += ecnt;
   double l0 = 0.;
 #pragma unroll
   for (int kk = 0; kk < NKK; kk++) l0 += V[kk] * E[kk];
   l0 = row_sum4(l0);
   int skip = 0;
-  if (g == 0) skip = mix_weight(a, site, l0, e);
-  if (a.last) {
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) skip += __shfl_xor(skip, off);
+  if (lane >> 4 == 0) skip = mix_weight(wa, sl, a, site, l0, e);
+  if (sl.last) {
+    skip = wave_sum<16>(skip);
     if (lane == 0) a.tile_skip[tile] = skip;
   }
 }
 
-__global__ __launch_bounds__(64) void grad_weight_nuc_kernel(WalkArgs wa, GradArgs a) {
-  const int lane = threadIdx.x;
-  const int lt = blockIdx.x, tile = a.tile0 + lt;
-  const size_t ls = (size_t)lt * 64 + lane, s = (size_t)tile * 64 + lane, CS = (size_t)a.ct * 64, SP = a.S_pad;
-  const int node = a.branch[0];
+__global__ __launch_bounds__(64) void grad_weight_nuc_kernel(WalkArgs wa, OutsideSlice sl, GradArgs a) {
+  const int lane = threadIdx.x, tile = sl.tile0 + blockIdx.x;
+  const size_t s = (size_t)tile * 64 + lane;
   double V[4], in[4], E[4];
-  for (int j = 0; j < 4; j++) V[j] = a.V[((size_t)node * 4 + j) * CS + ls];
-  int e = a.Vcnt[(size_t)node * CS + ls];
-  if (node >= a.L) {
-    for (int j = 0; j < 4; j++) in[j] = wa.partials[((size_t)(node - a.L) * 4 + j) * SP + s];
-    e += wa.counts[(size_t)(node - a.L) * SP + s];
-  } else {
-    nuc_leaf_vec(wa, (int)wa.codes[(size_t)node * SP + s], in);
-  }
-  const double *P = wa.Prow + (size_t)node * 16;
-  for (int x = 0; x < 4; x++) E[x] = P[4 * x] * in[0] + P[4 * x + 1] * in[1] + P[4 * x + 2] * in[2] + P[4 * x + 3] * in[3];
-  const double l0 = (V[0] * E[0] + V[1] * E[1]) + (V[2] * E[2] + V[3] * E[3]);
-  int skip = mix_weight(a, (int)s, l0, e);
-  if (a.last) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) skip += __shfl_xor(skip, off);
+  int e, ecnt;
+  const int4 ce = nuc_branch_outside(wa, sl, 0, tile, lane, V, e);
+  nuc_child_vec(wa, ce, s, in, ecnt);
+  e += ecnt;
+  mat4_vec(wa.Prow + (size_t)ce.y * 16, in, E);
+  int skip = mix_weight(wa, sl, a, (int)s, dot4(V, E), e);
+  if (sl.last) {
+    skip = wave_sum<64>(skip);
     if (lane == 0) a.tile_skip[tile] = skip;
   }
 }
 
 // W += V_tile diag(g) in_tile^T over the tiles of one segment that this chunk holds
 template <int NW>
-__global__ __launch_bounds__(64 * NW) void grad_accum_kernel(WalkArgs wa, GradArgs a) {
+__global__ __launch_bounds__(64 * NW) void grad_accum_kernel(WalkArgs wa, OutsideSlice sl, GradArgs a) {
   constexpr int NKK = 4 * NW, DP = 16 * NW, TILE = NKK * 64, LD = 17;
   __shared__ double As[DP * LD], Bs[DP * LD];  // [state][pattern of the tile]: V g and in
-  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, sl = lane & 15;
+  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, sp = lane & 15;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int seg = a.tile0 / a.seg_tiles + (int)blockIdx.x;
-  const int t_lo = max(seg * a.seg_tiles, a.tile0), t_hi = min((seg + 1) * a.seg_tiles, a.tile0 + a.nt);
-  const int bi = a.b0 + (int)blockIdx.y, node = a.branch[bi], in_idx = node >= a.L ? node - a.L : -1;
+  const int seg = sl.tile0 / a.seg_tiles + (int)blockIdx.x;
+  const int t_lo = max(seg * a.seg_tiles, sl.tile0), t_hi = min((seg + 1) * a.seg_tiles, sl.tile0 + sl.nt);
+  const int bi = sl.b0 + (int)blockIdx.y;
+  const int4 ce = branch_entry(wa, sl, bi);  // (.y the node code, .z the internal index below the branch or -1)
   const int D = a.D;
-  double *part = a.part + (((size_t)bi * a.C + a.cls) * a.nseg + seg) * D * D;
+  double *part = a.part + (((size_t)bi * sl.C + sl.cls) * a.nseg + seg) * D * D;
   const bool cont = t_lo > seg * a.seg_tiles;  // an earlier chunk began this segment
   f64x4 acc[NW];
 #pragma unroll
   for (int w = 0; w < NW; w++)
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-      const int row = 16 * wv + 4 * r + g, col = 16 * w + sl;
+      const int row = 16 * wv + 4 * r + g, col = 16 * w + sp;
       acc[w][r] = cont && row < D && col < D ? part[row * D + col] : 0.;
     }
   for (int tile = t_lo; tile < t_hi; tile++) {
-    const int lt = tile - a.tile0, site = tile * 16 + sl;
-    int e = a.Vcnt[((size_t)node * a.ct + lt) * 16 + sl];
+    const int site = tile * 16 + sp;
+    const size_t o = outside_index(sl, ce.y, tile);
+    int e = sl.Vcnt[o * 16 + sp];
     int code = 0;
-    if (in_idx >= 0) e += wa.counts[(size_t)in_idx * a.S_pad + site];
-    else code = (int)wa.codes_tile[((size_t)tile * a.L + node) * 16 + sl];
-    const double sc = pattern_scale(a, site, e);
-    const double *vb = a.V + ((size_t)node * a.ct + lt) * TILE;
-    const double *ib = wa.partials + ((size_t)max(in_idx, 0) * wa.ntiles + tile) * TILE;
+    if (ce.z >= 0) e += wa.counts[(size_t)ce.z * wa.S_pad + site];
+    else code = (int)wa.codes_tile[((size_t)tile * wa.L + ce.y) * 16 + sp];
+    const double sc = pattern_scale(wa, sl, a, site, e);
+    const double *vb = sl.V + o * TILE;
+    const double *ib = wa.partials + ((size_t)max(ce.z, 0) * wa.ntiles + tile) * TILE;
 #pragma unroll
     for (int q = 0; q < 2; q++) {
       const int k2 = 2 * wv + q;
       const unsigned off = (unsigned)(k2 * 64 + lane) * 16u;
       const f64x2 v = ld16(vb, off);
       f64x2 b;
-      if (in_idx >= 0) {
+      if (ce.z >= 0) {
         b = ld16(ib, off);
       } else {
 #pragma unroll
-        for (int h = 0; h < 2; h++) {
-          const int st = 4 * (2 * k2 + h) + g;
-          b[h] = code >= 0 ? (st == code ? 1. : 0.) : wa.ambig[(size_t)(-code - 1) * DP + st];
-        }
+        for (int h = 0; h < 2; h++) b[h] = leaf_value<DP>(wa, code, 4 * (2 * k2 + h) + g);
       }
 #pragma unroll
       for (int h = 0; h < 2; h++) {
         const int st = 4 * (2 * k2 + h) + g;
-        As[st * LD + sl] = sc != 0. ? v[h] * sc : 0.;  // (a pattern that takes no part must not bring a NaN of its own)
-        Bs[st * LD + sl] = sc != 0. ? b[h] : 0.;
+        As[st * LD + sp] = sc != 0. ? v[h] * sc : 0.;  // (a pattern that takes no part must not bring a NaN of its own)
+        Bs[st * LD + sp] = sc != 0. ? b[h] : 0.;
       }
     }
     __syncthreads();
 #pragma unroll
     for (int ks = 0; ks < 4; ks++) {
-      const double av = As[(16 * wv + sl) * LD + 4 * ks + g];
+      const double av = As[(16 * wv + sp) * LD + 4 * ks + g];
 #pragma unroll
-      for (int w = 0; w < NW; w++) acc[w] = mfma(av, Bs[(16 * w + sl) * LD + 4 * ks + g], acc[w]);
+      for (int w = 0; w < NW; w++) acc[w] = mfma(av, Bs[(16 * w + sp) * LD + 4 * ks + g], acc[w]);
     }
     __syncthreads();
   }
@@ -212,33 +184,27 @@ __global__ __launch_bounds__(64 * NW) void grad_accum_kernel(WalkArgs wa, GradAr
   for (int w = 0; w < NW; w++)
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-      const int row = 16 * wv + 4 * r + g, col = 16 * w + sl;
+      const int row = 16 * wv + 4 * r + g, col = 16 * w + sp;
       if (row < D && col < D) part[row * D + col] = acc[w][r];
     }
 }
 
 // 4 states: one wave per (branch, segment), one thread per pattern of a tile of 64
-__global__ __launch_bounds__(64) void grad_accum_nuc_kernel(WalkArgs wa, GradArgs a) {
+__global__ __launch_bounds__(64) void grad_accum_nuc_kernel(WalkArgs wa, OutsideSlice sl, GradArgs a) {
   const int lane = threadIdx.x;
-  const int seg = a.tile0 / a.seg_tiles + (int)blockIdx.x;
-  const int t_lo = max(seg * a.seg_tiles, a.tile0), t_hi = min((seg + 1) * a.seg_tiles, a.tile0 + a.nt);
-  const int bi = a.b0 + (int)blockIdx.y, node = a.branch[bi];
-  const size_t CS = (size_t)a.ct * 64, SP = a.S_pad;
-  double *part = a.part + (((size_t)bi * a.C + a.cls) * a.nseg + seg) * 16;
+  const int seg = sl.tile0 / a.seg_tiles + (int)blockIdx.x;
+  const int t_lo = max(seg * a.seg_tiles, sl.tile0), t_hi = min((seg + 1) * a.seg_tiles, sl.tile0 + sl.nt);
+  const int bi = sl.b0 + (int)blockIdx.y;
+  double *part = a.part + (((size_t)bi * sl.C + sl.cls) * a.nseg + seg) * 16;
   double acc[16];
   for (int k = 0; k < 16; k++) acc[k] = 0.;
   for (int tile = t_lo; tile < t_hi; tile++) {
-    const size_t ls = (size_t)(tile - a.tile0) * 64 + lane, s = (size_t)tile * 64 + lane;
+    const size_t s = (size_t)tile * 64 + lane;
     double V[4], in[4];
-    for (int j = 0; j < 4; j++) V[j] = a.V[((size_t)node * 4 + j) * CS + ls];
-    int e = a.Vcnt[(size_t)node * CS + ls];
-    if (node >= a.L) {
-      for (int j = 0; j < 4; j++) in[j] = wa.partials[((size_t)(node - a.L) * 4 + j) * SP + s];
-      e += wa.counts[(size_t)(node - a.L) * SP + s];
-    } else {
-      nuc_leaf_vec(wa, (int)wa.codes[(size_t)node * SP + s], in);
-    }
-    const double sc = pattern_scale(a, (int)s, e);
+    int e, ecnt;
+    const int4 ce = nuc_branch_outside(wa, sl, bi, tile, lane, V, e);
+    nuc_child_vec(wa, ce, s, in, ecnt);
+    const double sc = pattern_scale(wa, sl, a, (int)s, e + ecnt);
     if (sc != 0.)
       for (int i = 0; i < 4; i++) {
         const double vi = V[i] * sc;
@@ -247,9 +213,7 @@ __global__ __launch_bounds__(64) void grad_accum_nuc_kernel(WalkArgs wa, GradArg
   }
   const bool cont = t_lo > seg * a.seg_tiles;
   for (int k = 0; k < 16; k++) {
-    double x = acc[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    const double x = wave_sum<64>(acc[k]);
     if (lane == 0) part[k] = cont ? part[k] + x : x;
   }
 }
@@ -471,39 +435,22 @@ __global__ __launch_bounds__(64) void frechet_adjoint4_kernel(FrechetArgs a) {
   a.status[m] = bad ? 1 : 0;
 }
 
-#define LAUNCH_NW_LDS(kernel, nw, grid, block, lds, stream, ...)                               \
-  switch (nw) {                                                                                \
-    case 1: hipLaunchKernelGGL(kernel<1>, grid, block, lds, stream, __VA_ARGS__); break;       \
-    case 2: hipLaunchKernelGGL(kernel<2>, grid, block, lds, stream, __VA_ARGS__); break;       \
-    case 3: hipLaunchKernelGGL(kernel<3>, grid, block, lds, stream, __VA_ARGS__); break;       \
-    default: hipLaunchKernelGGL(kernel<4>, grid, block, lds, stream, __VA_ARGS__); break;      \
-  }
-
 int launch_frechet(const FrechetArgs &a, hipStream_t stream) {
   if (a.D == 4) {
     hipLaunchKernelGGL(frechet_adjoint4_kernel, dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, stream, a);
     HIPCHK(hipGetLastError());
     return 0;
   }
-  // (hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of the function, as in launch_expm)
   static bool attr_done[64][5];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
   const int NW = (a.D + 15) / 16, DP = 16 * NW;
   const size_t lds = (size_t)(4 * DP * (DP + 2) + DP) * sizeof(double);
-  if (!attr_done[dev][NW]) {
-    switch (NW) {
-      case 1: HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(frechet_adjoint_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-      case 2: HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(frechet_adjoint_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-      case 3: HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(frechet_adjoint_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-      default: HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(frechet_adjoint_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); break;
-    }
-    attr_done[dev][NW] = true;
-  }
-  LAUNCH_NW_LDS(frechet_adjoint_kernel, NW, dim3((unsigned)a.n), dim3((unsigned)(64 * NW)), lds, stream, a);
+  LAUNCH_NW_DYN_LDS(frechet_adjoint_kernel, NW, attr_done, dev, dim3((unsigned)a.n), dim3((unsigned)(64 * NW)), lds, stream, a);
   HIPCHK(hipGetLastError());
   return 0;
 }
+
 // grad[m][k] = sum_{i != j} T_k[i][j] (S_m[i][j] - S_m[i][i]): one workgroup per matrix, a fixed-order tree per coefficient
 __global__ __launch_bounds__(256) void grad_contract_kernel(const double *__restrict__ S, const double *__restrict__ T, int D, int K,
                                                             double *__restrict__ out) {
@@ -556,27 +503,16 @@ int sensitivities(hyphy_hip_partition *p, const OutsideCall &oc, const double *w
     HIPCHK(blk.get(&Wd, (size_t)nb * C * DD));
     if (sc.get(p, oc, blk)) return -1;
     if (sc.upload(p, oc, s.stream)) return -1;
-    auto args = [&](const WalkArgs &a, const OutsideSlice &sl, dim3 grid) {
-      GradArgs ga;
-      ga.L = a.L, ga.S_pad = a.S_pad, ga.tile0 = sl.tile0, ga.ct = sl.ct, ga.nt = (int)grid.x;
-      ga.C = sl.C, ga.cls = sl.cls, ga.first = sl.first, ga.last = sl.last, ga.b0 = sl.b0;
-      ga.w = sl.w;
-      ga.branch = sl.branch, ga.V = sl.V, ga.Vcnt = sl.Vcnt, ga.freq = s.freq;
-      ga.Lm = Lm, ga.em = em, ga.live = live, ga.ginv = ginv, ga.tile_skip = tile_skip;
-      ga.seg_tiles = seg_tiles, ga.nseg = nseg, ga.D = D, ga.part = part;
-      return ga;
-    };
+    const GradArgs ga = {Lm, em, live, ginv, tile_skip, seg_tiles, nseg, D, part};
     auto weigh = [&](const WalkArgs &a, const OutsideSlice &sl, dim3 grid) {
       if (sl.b0) return;
-      const GradArgs ga = args(a, sl, grid);
-      if (nuc) hipLaunchKernelGGL(grad_weight_nuc_kernel, dim3(grid.x), dim3(64), 0, s.stream, a, ga);
-      else LAUNCH_NW(grad_weight_kernel, NW, dim3(grid.x), dim3(64), s.stream, a, ga);
+      if (nuc) hipLaunchKernelGGL(grad_weight_nuc_kernel, dim3(grid.x), dim3(64), 0, s.stream, a, sl, ga);
+      else LAUNCH_NW(grad_weight_kernel, NW, dim3(grid.x), dim3(64), s.stream, a, sl, ga);
     };
     auto accumulate = [&](const WalkArgs &a, const OutsideSlice &sl, dim3 grid) {
-      const GradArgs ga = args(a, sl, grid);
-      const unsigned segs = (unsigned)((ga.tile0 + ga.nt - 1) / seg_tiles - ga.tile0 / seg_tiles + 1);
-      if (nuc) hipLaunchKernelGGL(grad_accum_nuc_kernel, dim3(segs, grid.y), dim3(64), 0, s.stream, a, ga);
-      else LAUNCH_NW(grad_accum_kernel, NW, dim3(segs, grid.y), dim3((unsigned)(64 * NW)), s.stream, a, ga);
+      const unsigned segs = (unsigned)((sl.tile0 + sl.nt - 1) / seg_tiles - sl.tile0 / seg_tiles + 1);
+      if (nuc) hipLaunchKernelGGL(grad_accum_nuc_kernel, dim3(segs, grid.y), dim3(64), 0, s.stream, a, sl, ga);
+      else LAUNCH_NW(grad_accum_kernel, NW, dim3(segs, grid.y), dim3((unsigned)(64 * NW)), s.stream, a, sl, ga);
     };
     int walked;
     if (C == 1) {

@@ -8,11 +8,15 @@
 //   branch    a child's rescaled V and its exponent
 //   leaf      a leaf's U = P_l^T V_l (not rescaled), formed only when the sink's kLeafProduct is set
 // in two forms each, told apart by their arguments: (tile, lane, fragment vector) and (pattern, 4 values).  The marginal
-// reconstruction (marginal.hip) accumulates support in `node` / `leaf`; the branch trials (trials.hip) and the branch derivatives
-// (deriv.hip) store V in `branch`, through the OutsideStore sink and its two kernels at the end of this file, launched by the host
-// driver they share (outside_pass.h).  What all three do on the host before a launch is here too: check_pass_ready, begin_outside.
+// reconstruction (marginal.hip) accumulates support in `node` / `leaf`; the branch trials (trials.hip), the branch derivatives
+// (deriv.hip) and the gradient (grad.hip) store V in `branch`, through the OutsideStore sink and its two kernels, launched by the host
+// driver they share (outside_pass.h).  What all four do on the host before a launch is here too: check_pass_ready, begin_outside.
 // U, Ucnt, work and wcnt are indexed by (tile or pattern within the chunk, size of the chunk): a chunk that is the whole shard gives
-// the [I][ntiles][TILE] / [I][S_pad] shapes of the partials.  gfx950 only.
+// the [I][ntiles][TILE] / [I][S_pad] shapes of the partials.
+// The device side of those three passes' phase 2 is at the end of this file, once: OutsideSlice (what their kernels get by value beside
+// the WalkArgs), the branch prologue (branch_entry, branch_outside / nuc_branch_outside: the branch, its V and exponent from the chunk's blocks;
+// child_vec / nuc_child_vec: the conditional below it; edge_product, mat4_vec: its edge product), the record epilogue's wave sums
+// (wave_sum, wave_or) and align_exponents.  gfx950 only.
 #pragma once
 #include "devutil.h"
 #include "partition.h"
@@ -41,6 +45,20 @@ struct WalkArgs {  // what the walks read; "tile" below: 16 patterns (4 states: 
   int32_t *Ucnt;             // [I][chunk][16]                       (4 states: [I][chunk])
   double *work;              // [chunk][2 maxk][TILE]                (4 states: [2 maxk][4][chunk])
   int32_t *wcnt;             // [chunk][2 maxk][16]                  (4 states: [2 maxk][chunk])
+};
+
+// What phase 2 of a pass that keeps every branch's V (outside_pass.h) reads beside the WalkArgs: the chunk, the class and the slice of
+// the branch grid of one launch.  Here and not with the driver that fills it, because the branch prologue below reads it.
+struct OutsideSlice {
+  int tile0, ct, nt;            // first tile of the chunk, tiles V and Vcnt are shaped for, tiles of the chunk that exist
+  int C, cls, first, last, b0;  // classes, class of this launch, it is the first / the last one, first branch of the grid
+  double w;                     // weight of this class (1 when C == 1)
+  const int *branch;            // [branches with a request] node codes
+  const int *off, *idx;         // requests of branch k: idx[off[k] .. off[k + 1])
+  const double *V;              // phase 1's blocks of this chunk
+  const int32_t *Vcnt;
+  const double *freq;           // [S_pad] pattern frequencies
+  int part_stride;              // per-(request, tile) records: [n][part_stride]
 };
 
 struct WalkScratch {  // what a pass brings to the walk: the uploaded program and pi, and the blocks the walk writes
@@ -163,6 +181,28 @@ __device__ __forceinline__ void leaf_vec(const WalkArgs &a, int c, int g, double
   for (int kk = 0; kk < NKK; kk++) lv[kk] = c >= 0 ? (4 * kk + g == c ? 1. : 0.) : a.ambig[(size_t)(-c - 1) * DP + 4 * kk + g];
 }
 
+// ... one element of it, `state` of DP (leaf_vec keeps its own text: a call here moves instructions in marginal.hip's kernels)
+template <int DP>
+__device__ __forceinline__ double leaf_value(const WalkArgs &a, int c, int state) {
+  return c >= 0 ? (state == c ? 1. : 0.) : a.ambig[(size_t)(-c - 1) * DP + state];
+}
+
+// the conditional below child entry ce at this lane's states, `in`, and its exponent: stored partial or leaf vector; returns the
+// leaf's code (0 for an internal child)
+template <int NKK>
+__device__ __forceinline__ int child_vec(const WalkArgs &a, const int4 &ce, int tile, int lane, double (&in)[NKK], int &ecnt) {
+  const int sl = lane & 15;
+  ecnt = 0;
+  if (ce.z >= 0) {
+    ld_vec<NKK>(a.partials + ((size_t)ce.z * a.ntiles + tile) * (NKK * 64), lane, in);
+    ecnt = a.counts[(size_t)ce.z * a.S_pad + tile * 16 + sl];
+    return 0;
+  }
+  const int c = (int)a.codes_tile[((size_t)tile * a.L + ce.y) * 16 + sl];
+  leaf_vec<NKK>(a, c, lane >> 4, in);
+  return c;
+}
+
 // edge product E of child entry ce and its 2^64 exponent
 template <int NW>
 __device__ __forceinline__ void edge_product(const WalkArgs &a, const int4 &ce, int tile, int lane, double (&E)[4 * NW], int &ecnt) {
@@ -273,7 +313,30 @@ __device__ __forceinline__ void rescale4(double (&v)[4], int &cnt) {
 }
 
 __device__ __forceinline__ void nuc_leaf_vec(const WalkArgs &a, int c, double (&lv)[4]) {
-  for (int j = 0; j < 4; j++) lv[j] = c >= 0 ? (j == c ? 1. : 0.) : a.ambig[(size_t)(-c - 1) * 4 + j];
+  for (int j = 0; j < 4; j++) lv[j] = leaf_value<4>(a, c, j);
+}
+
+// 4 states: the conditional below child entry ce at pattern s and its exponent: stored partial or leaf vector
+__device__ __forceinline__ void nuc_child_vec(const WalkArgs &a, const int4 &ce, size_t s, double (&in)[4], int &ecnt) {
+  const size_t SP = a.S_pad;
+  ecnt = 0;
+  if (ce.z >= 0) {
+    for (int j = 0; j < 4; j++) in[j] = a.partials[((size_t)ce.z * 4 + j) * SP + s];
+    ecnt = a.counts[(size_t)ce.z * SP + s];
+  } else {
+    nuc_leaf_vec(a, (int)a.codes[(size_t)ce.y * SP + s], in);
+  }
+}
+
+// y = M x and y = M^T x of a row-major 4 x 4 matrix
+__device__ __forceinline__ void mat4_vec(const double *M, const double (&x)[4], double (&y)[4]) {
+  for (int i = 0; i < 4; i++) y[i] = M[4 * i] * x[0] + M[4 * i + 1] * x[1] + M[4 * i + 2] * x[2] + M[4 * i + 3] * x[3];
+}
+__device__ __forceinline__ void mat4t_vec(const double *M, const double (&x)[4], double (&y)[4]) {
+  for (int i = 0; i < 4; i++) y[i] = M[i] * x[0] + M[4 + i] * x[1] + M[8 + i] * x[2] + M[12 + i] * x[3];
+}
+__device__ __forceinline__ double dot4(const double (&x)[4], const double (&y)[4]) {
+  return (x[0] * y[0] + x[1] * y[1]) + (x[2] * y[2] + x[3] * y[3]);
 }
 
 // 4 states: the walk of one pattern (launch: 256 threads per workgroup, any grid that covers a.count)
@@ -281,7 +344,7 @@ template <typename Sink>
 __device__ __forceinline__ void outside_walk_nuc(const WalkArgs &a, Sink &sink) {
   const int ls = blockIdx.x * blockDim.x + threadIdx.x;
   if (ls >= a.count) return;
-  const size_t s = (size_t)a.first + ls, SP = a.S_pad, CS = (size_t)a.chunk;
+  const size_t s = (size_t)a.first + ls, CS = (size_t)a.chunk;
   for (int pc = 0; pc < a.n_prog;) {
     const int4 h = a.prog[pc];
     const int node = h.y, k = h.z;
@@ -295,16 +358,10 @@ __device__ __forceinline__ void outside_walk_nuc(const WalkArgs &a, Sink &sink) 
     }
     for (int i = 0; i < k; i++) {
       const int4 ce = a.prog[pc + 1 + i];
-      const double *P = a.Prow + (size_t)ce.y * 16;
       double in[4], E[4];
-      int ecnt = 0;
-      if (ce.z >= 0) {
-        for (int j = 0; j < 4; j++) in[j] = a.partials[((size_t)ce.z * 4 + j) * SP + s];
-        ecnt = a.counts[(size_t)ce.z * SP + s];
-      } else {
-        nuc_leaf_vec(a, (int)a.codes[(size_t)ce.y * SP + s], in);
-      }
-      for (int x = 0; x < 4; x++) E[x] = P[4 * x] * in[0] + P[4 * x + 1] * in[1] + P[4 * x + 2] * in[2] + P[4 * x + 3] * in[3];
+      int ecnt;
+      nuc_child_vec(a, ce, s, in, ecnt);
+      mat4_vec(a.Prow + (size_t)ce.y * 16, in, E);
       for (int j = 0; j < 4; j++) {
         a.work[((size_t)(2 * i) * 4 + j) * CS + ls] = pre[j];
         a.work[((size_t)(2 * i + 1) * 4 + j) * CS + ls] = E[j];
@@ -321,7 +378,6 @@ __device__ __forceinline__ void outside_walk_nuc(const WalkArgs &a, Sink &sink) 
     for (int i = k - 1; i >= 0; i--) {
       const int4 ce = a.prog[pc + 1 + i];
       if (ce.z >= 0 || sink.leaves()) {
-        const double *P = a.Prow + (size_t)ce.y * 16;
         double V[4];
         for (int j = 0; j < 4; j++) V[j] = a.work[((size_t)(2 * i) * 4 + j) * CS + ls] * suf[j];
         int vcnt = a.wcnt[(size_t)(2 * i) * CS + ls] + scnt;
@@ -329,7 +385,7 @@ __device__ __forceinline__ void outside_walk_nuc(const WalkArgs &a, Sink &sink) 
         sink.branch(a, ce.y, (size_t)ls, V, vcnt);
         if (ce.z >= 0 || Sink::kLeafProduct) {
           double U[4];
-          for (int y = 0; y < 4; y++) U[y] = P[y] * V[0] + P[4 + y] * V[1] + P[8 + y] * V[2] + P[12 + y] * V[3];
+          mat4t_vec(a.Prow + (size_t)ce.y * 16, V, U);
           if (ce.z >= 0) {
             rescale4(U, vcnt);
             for (int j = 0; j < 4; j++) a.U[((size_t)ce.z * 4 + j) * CS + ls] = U[j];
@@ -381,6 +437,58 @@ __global__ __launch_bounds__(64) void outside_store_kernel(WalkArgs a, OutsideSt
 }
 
 __global__ __launch_bounds__(256) void outside_store_nuc_kernel(WalkArgs a, OutsideStore o) { outside_walk_nuc(a, o); }
+
+// ---- what phase 2 of a pass that kept every branch's V starts from and ends with (trials.hip, deriv.hip, grad.hip) ----
+// branch bi of the slice as the child entry the program has for it (.y node code, .z internal index or -1)
+__device__ __forceinline__ int4 branch_entry(const WalkArgs &a, const OutsideSlice &sl, int bi) {
+  const int node = sl.branch[bi];
+  return make_int4(1, node, node >= a.L ? node - a.L : -1, 0);
+}
+// where phase 1 left branch `node` at `tile`: its block among the chunk's, V [..][TILE] and Vcnt [..][16] alike
+__device__ __forceinline__ size_t outside_index(const OutsideSlice &sl, int node, int tile) {
+  return (size_t)node * sl.ct + (tile - sl.tile0);
+}
+// the entry, V and its exponent of branch bi at `tile`
+template <int NKK>
+__device__ __forceinline__ int4 branch_outside(const WalkArgs &a, const OutsideSlice &sl, int bi, int tile, int lane, double (&V)[NKK],
+                                               int &vcnt) {
+  const int4 ce = branch_entry(a, sl, bi);
+  const size_t o = outside_index(sl, ce.y, tile);
+  ld_vec<NKK>(sl.V + o * (NKK * 64), lane, V);
+  vcnt = sl.Vcnt[o * 16 + (lane & 15)];
+  return ce;
+}
+// 4 states: pattern `lane` of the wave's 64
+__device__ __forceinline__ int4 nuc_branch_outside(const WalkArgs &a, const OutsideSlice &sl, int bi, int tile, int lane, double (&V)[4],
+                                                   int &vcnt) {
+  const int4 ce = branch_entry(a, sl, bi);
+  const size_t ls = (size_t)(tile - sl.tile0) * 64 + lane, CS = (size_t)sl.ct * 64;
+  for (int j = 0; j < 4; j++) V[j] = sl.V[((size_t)ce.y * 4 + j) * CS + ls];
+  vcnt = sl.Vcnt[(size_t)ce.y * CS + ls];
+  return ce;
+}
+
+// sum / OR over the W lanes around this one (16: the patterns of a tile within one state group; 64: the wave), xor-shuffles from W / 2 down
+template <int W, typename T>
+__device__ __forceinline__ T wave_sum(T x) {
+#pragma unroll
+  for (int off = W / 2; off > 0; off >>= 1) x += __shfl_xor(x, off);
+  return x;
+}
+template <int W>
+__device__ __forceinline__ int wave_or(int x) {
+#pragma unroll
+  for (int off = W / 2; off > 0; off >>= 1) x |= __shfl_xor(x, off);
+  return x;
+}
+
+// two values with 2^64 exponents e_old and e on the smaller exponent (the larger scale): that exponent and what each is multiplied by.
+// (what an exact zero does to the mix is the caller's rule)
+__device__ __forceinline__ int align_exponents(int e_old, int e, double &s_old, double &s_new) {
+  const int e_new = min(e_old, e);
+  s_old = ldexp(1.0, -64 * (e_old - e_new)), s_new = ldexp(1.0, -64 * (e - e_new));
+  return e_new;
+}
 
 }  // namespace
 }  // namespace hyhip

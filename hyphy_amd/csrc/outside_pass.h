@@ -1,10 +1,12 @@
-// The host side of the passes that keep every branch's outside vector (trials.hip, deriv.hip), once: behind outside.h's
+// The host side of the passes that keep every branch's outside vector (trials.hip, deriv.hip, grad.hip), once: behind outside.h's
 // check_pass_ready, what they refuse of their requests, then the per-shard scratch and the loop over chunks of tiles and rate classes.
 //   check_requests                      the refusals, in the order and with the words the entry points have always had
 //   begin_outside                       outside.h's (pending work finished, classes resident, program, pi), and the requests grouped
 //   OutsideScratch                      one shard's walk blocks and branch tables, from the call's Blocks
-//   outside_chunks                      per (chunk, class): WalkArgs, transposition, phase 1, then the caller's phase 2 per grid slice
+//   outside_chunks                      per (chunk, class): WalkArgs, transposition, phase 1, then the caller's phase 2 per grid slice,
+//                                       which gets the WalkArgs and the filled OutsideSlice (outside.h) to pass on to its kernel as they are
 //   download_rows                       [n][S_pad] on the device -> the caller's pattern order
+//   KeepForms                           the last reduce form and exponential kernel put back when the call returns (deriv.hip, grad.hip)
 // Tiles are independent in both phases, so phases 1-2 run over chunks of tiles that keep the V scratch ([B][tiles of the chunk][TILE]
 // doubles) within HYPHY_HIP_TRIALS_MB (default 1024, read at every call, never less than one tile).  4 states: a "tile" of the
 // chunking is one wave's 64 patterns.  (The marginal reconstruction needs none of this: its chunk is the whole shard and its scratch
@@ -17,7 +19,7 @@
 namespace hyhip {
 namespace {
 
-// n > 0 requests of one kind (`noun`: "trial", "derivative"), each naming a branch
+// n > 0 requests of one kind (`noun`: "trial", "derivative", "request"), each naming a branch
 inline int check_requests(const hyphy_hip_partition *p, const std::string &pre, const char *noun, int64_t n, const int64_t *nodes,
                           bool from_templates) {
   if (from_templates && !p->K) return fail(pre + "templates not set (hyphy_hip_set_q_templates)");
@@ -41,16 +43,15 @@ inline int begin_outside(hyphy_hip_partition *p, OutsideCall &oc, const int64_t 
   return 0;
 }
 
-// What phase 2 reads beside the WalkArgs: the chunk, the class and the slice of the branch grid of one launch.
-struct OutsideSlice {
-  int tile0, ct;                // first tile of the chunk, tiles V and Vcnt are shaped for
-  int C, cls, first, last, b0;  // classes, class of this launch, it is the first / the last one, first branch of the grid
-  double w;                     // weight of this class (1 when C == 1)
-  const int *branch;            // [branches with a request] node codes
-  const int *off, *idx;         // requests of branch k: idx[off[k] .. off[k + 1])
-  const double *V;              // phase 1's blocks of this chunk
-  const int32_t *Vcnt;
-  int part_stride;              // per-(request, tile) records: [n][part_stride]
+// hyphy_hip_last_reduce_form and hyphy_hip_last_expm_kernel answer behind the call what they answered before it
+struct KeepForms {
+  hyphy_hip_partition *p;
+  hyphy_hip_partition::ReduceForm reduce;
+  const char *expm;
+  ~KeepForms() {
+    p->last_reduce = reduce;
+    set_last_expm_kernel(expm);
+  }
 };
 
 struct OutsideScratch {  // one shard
@@ -120,8 +121,8 @@ inline int outside_chunks(const hyphy_hip_partition *p, const Shard &s, const Ou
       const int unit = p->nuc ? sc.TP : 1;  // (4 states: the walk counts patterns)
       a.first = tile0 * unit, a.count = nt * unit, a.chunk = sc.ct * unit;
       launch_outside_store(p, s, a, {sc.V, sc.Vcnt}, C > 1 || tile0 == 0 ? sc.PT : nullptr);
-      OutsideSlice sl = {tile0, sc.ct, C, c, c == 0, c == C - 1, 0, C > 1 ? weights[c] : 1.0, sc.d_branch, sc.d_off, sc.d_idx,
-                         sc.V, sc.Vcnt, sc.part_stride};
+      OutsideSlice sl = {tile0, sc.ct, nt, C, c, c == 0, c == C - 1, 0, C > 1 ? weights[c] : 1.0, sc.d_branch, sc.d_off, sc.d_idx,
+                         sc.V, sc.Vcnt, s.freq, sc.part_stride};
       for (; sl.b0 < n_branch; sl.b0 += 65535) phase2(a, sl, dim3((unsigned)nt, (unsigned)std::min(65535, n_branch - sl.b0)));
       HIPCHK(hipGetLastError());
     }

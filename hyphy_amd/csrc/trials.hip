@@ -16,9 +16,11 @@
 // Reduction (trials_reduce_kernel): one wave per trial, combine.h's fixed-order compensated sum over the partial sums.
 // Nothing here joins by order of arrival: two identical calls give identical bits.
 //
-// The refusals, the scratch of the walk and the loop over chunks of tiles and classes are outside_pass.h's, shared with deriv.hip; what
-// is here is the trials' own: their result blocks, the trial images, phase 2 and the reduction.  All scratch comes from the pool and
-// goes back before the call returns.  The partition's matrices, images, schedules and caches are not written.
+// The refusals, the scratch of the walk and the loop over chunks of tiles and classes are outside_pass.h's, shared with deriv.hip and
+// grad.hip; a phase-2 kernel gets (WalkArgs, OutsideSlice, TrialArgs) and starts from outside.h's branch prologue (branch_outside,
+// child_vec and their 4-state forms), mixes through align_exponents and ends in wave_sum / wave_or.  What is here is the trials' own:
+// their result blocks, the trial images (and the column gather from them), phase 2 and the reduction.  All scratch comes from the pool
+// and goes back before the call returns.  The partition's matrices, images, schedules and caches are not written.
 // 4 states: one thread per pattern over the plane layout and row-major matrices.
 #include "combine.h"
 #include "devutil.h"
@@ -30,35 +32,23 @@ using namespace hyhip;
 namespace hyhip {
 namespace {
 
-struct TrialArgs {
-  int NW, L, S_pad, ntiles, tile0, ct;  // (4 states: tiles of 64 patterns, ntiles unused)
-  int C, cls, first, last, b0;          // classes of a trial, class of this launch, it is the first / the last one, first branch of the grid
-  double w;                             // weight of this class (1 when C == 1)
-  const int *branch;                    // [branches with a trial] node codes
-  const int *tr_off, *tr_idx;           // trials of branch k: tr_idx[tr_off[k] .. tr_off[k + 1])
-  const double *img;                    // [n_trials][C] trial matrices: A-operand images (4 states: [16] row-major)
-  const double *V;                      // phase 1's blocks of this chunk
-  const int32_t *Vcnt;
-  const double *partials;               // this class
-  const int32_t *counts;
-  const int16_t *codes_tile, *codes;    // [ntiles][L][16] / (4 states) [L][S_pad]
-  const double *ambig, *freq;
-  double *lik;                          // [n_trials][S_pad] per pattern: classes mixed so far
+struct TrialArgs {      // the trials' own blocks, beside the WalkArgs and the OutsideSlice
+  const double *img;    // [n_trials][C] trial matrices: A-operand images (4 states: [16] row-major)
+  double *lik;          // [n_trials][S_pad] per pattern: classes mixed so far
   int32_t *cnt;
-  double *part_sum;                     // [n_trials][part_stride] per (trial, tile): sum_s f_s log l_s, sum_s f_s c_s, flags
+  double *part_sum;     // [n_trials][part_stride] per (trial, tile): sum_s f_s log l_s, sum_s f_s c_s, flags
   long long *part_cnt;
   int *part_flag;
-  int part_stride;
 };
 
 // this class's value (l, exponent e) of pattern q into the mix of the classes before it, aligned on the smaller exponent (the larger
 // scale), as MargSink::add of marginal.hip aligns its numerators
-__device__ __forceinline__ void mix_in(const TrialArgs &a, size_t q, double &l, int &e) {
-  l *= a.w;
-  if (a.first) return;
-  const int e_old = a.cnt[q], e_new = min(e_old, e);
-  l = a.lik[q] * ldexp(1.0, -64 * (e_old - e_new)) + l * ldexp(1.0, -64 * (e - e_new));
-  e = e_new;
+__device__ __forceinline__ void mix_in(const OutsideSlice &sl, const TrialArgs &a, size_t q, double &l, int &e) {
+  l *= sl.w;
+  if (sl.first) return;
+  double so, sn;
+  e = align_exponents(a.cnt[q], e, so, sn);
+  l = a.lik[q] * so + l * sn;
 }
 
 // the pattern's term of the trial's total (bc_eval_kernel's rule: 1 a zero likelihood, 2 not a number)
@@ -72,30 +62,35 @@ __device__ __forceinline__ void site_term(double l, int e, double f, double &wsu
   }
 }
 
-template <int NW>
-__global__ __launch_bounds__(64) void branch_trials_kernel(TrialArgs a) {
-  constexpr int NKK = 4 * NW, DP = 16 * NW, TILE = NKK * 64;
-  const int lane = threadIdx.x, g = lane >> 4, sl = lane & 15;
-  const int lt = blockIdx.x, tile = a.tile0 + lt, site = tile * 16 + sl;
-  const int bi = a.b0 + blockIdx.y, node = a.branch[bi];
-  double V[NKK], in[NKK];
-  ld_vec<NKK>(a.V + ((size_t)node * a.ct + lt) * TILE, lane, V);
-  int bcnt = a.Vcnt[((size_t)node * a.ct + lt) * 16 + sl];
-  int c = 0;
-  bool gather = false;
-  if (node >= a.L) {
-    ld_vec<NKK>(a.partials + ((size_t)(node - a.L) * a.ntiles + tile) * TILE, lane, in);
-    bcnt += a.counts[(size_t)(node - a.L) * a.S_pad + site];
-  } else {
-    c = (int)a.codes_tile[((size_t)tile * a.L + node) * 16 + sl];
-    gather = !__any(c < 0);
-#pragma unroll
-    for (int kk = 0; kk < NKK; kk++) in[kk] = c >= 0 ? (4 * kk + g == c ? 1. : 0.) : a.ambig[(size_t)(-c - 1) * DP + 4 * kk + g];
+// the record of (trial t, tile): the terms of its W lanes summed, written by lane 0
+template <int W>
+__device__ __forceinline__ void put_record(const OutsideSlice &sl, const TrialArgs &a, int t, int tile, int lane, double wsum,
+                                           long long wcnt, int wflag) {
+  wsum = wave_sum<W>(wsum), wcnt = wave_sum<W>(wcnt), wflag = wave_or<W>(wflag);
+  if (lane == 0) {
+    const size_t pq = (size_t)t * sl.part_stride + tile;
+    a.part_sum[pq] = wsum;
+    a.part_cnt[pq] = wcnt;
+    a.part_flag[pq] = wflag;
   }
-  const double f = a.freq[site];
-  for (int k = a.tr_off[bi]; k < a.tr_off[bi + 1]; k++) {
-    const int t = a.tr_idx[k];
-    const double *M = a.img + ((size_t)t * a.C + a.cls) * DP * DP;
+}
+
+template <int NW>
+__global__ __launch_bounds__(64) void branch_trials_kernel(WalkArgs wa, OutsideSlice sl, TrialArgs a) {
+  constexpr int NKK = 4 * NW, DP = 16 * NW, TILE = NKK * 64;
+  const int lane = threadIdx.x, g = lane >> 4;
+  const int tile = sl.tile0 + blockIdx.x, site = tile * 16 + (lane & 15);
+  const int bi = sl.b0 + blockIdx.y;
+  double V[NKK], in[NKK];
+  int bcnt, ecnt;
+  const int4 ce = branch_outside<NKK>(wa, sl, bi, tile, lane, V, bcnt);
+  const int c = child_vec<NKK>(wa, ce, tile, lane, in, ecnt);
+  bcnt += ecnt;
+  const bool gather = ce.z < 0 && !__any(c < 0);
+  const double f = sl.freq[site];
+  for (int k = sl.off[bi]; k < sl.off[bi + 1]; k++) {
+    const int t = sl.idx[k];
+    const double *M = a.img + ((size_t)t * sl.C + sl.cls) * DP * DP;
     double E[NKK];
     if (gather) {  // column M[.][code] out of the A-operand image: M[r][c] sits in row block r >> 4 at k-step c >> 2, lane (c & 3) * 16 + (r & 15)
 #pragma unroll
@@ -113,74 +108,44 @@ __global__ __launch_bounds__(64) void branch_trials_kernel(TrialArgs a) {
     long long wcnt = 0;
     int wflag = 0;
     if (g == 0) {
-      const size_t q = (size_t)t * a.S_pad + site;
+      const size_t q = (size_t)t * wa.S_pad + site;
       int e = bcnt;
-      mix_in(a, q, s, e);
+      mix_in(sl, a, q, s, e);
       a.lik[q] = s;
       a.cnt[q] = e;
-      if (a.last) site_term(s, e, f, wsum, wcnt, wflag);
+      if (sl.last) site_term(s, e, f, wsum, wcnt, wflag);
     }
-    if (a.last) {
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) {
-        wsum += __shfl_xor(wsum, off);
-        wcnt += __shfl_xor(wcnt, off);
-        wflag |= __shfl_xor(wflag, off);
-      }
-      if (lane == 0) {
-        const size_t pq = (size_t)t * a.part_stride + tile;
-        a.part_sum[pq] = wsum;
-        a.part_cnt[pq] = wcnt;
-        a.part_flag[pq] = wflag;
-      }
-    }
+    if (sl.last) put_record<16>(sl, a, t, tile, lane, wsum, wcnt, wflag);
   }
 }
 
 // 4 states: one thread per pattern, one wave per (branch, 64 patterns)
-__global__ __launch_bounds__(64) void branch_trials_nuc_kernel(TrialArgs a) {
-  const int lane = threadIdx.x;
-  const int lt = blockIdx.x, tile = a.tile0 + lt;
-  const size_t ls = (size_t)lt * 64 + lane, s = (size_t)tile * 64 + lane, CS = (size_t)a.ct * 64, SP = a.S_pad;
-  const int bi = a.b0 + blockIdx.y, node = a.branch[bi];
+__global__ __launch_bounds__(64) void branch_trials_nuc_kernel(WalkArgs wa, OutsideSlice sl, TrialArgs a) {
+  const int lane = threadIdx.x, tile = sl.tile0 + blockIdx.x;
+  const size_t s = (size_t)tile * 64 + lane;
+  const int bi = sl.b0 + blockIdx.y;
   double V[4], in[4];
-  for (int j = 0; j < 4; j++) V[j] = a.V[((size_t)node * 4 + j) * CS + ls];
-  int bcnt = a.Vcnt[(size_t)node * CS + ls];
-  if (node >= a.L) {
-    for (int j = 0; j < 4; j++) in[j] = a.partials[((size_t)(node - a.L) * 4 + j) * SP + s];
-    bcnt += a.counts[(size_t)(node - a.L) * SP + s];
-  } else {
-    const int c = (int)a.codes[(size_t)node * SP + s];
-    for (int j = 0; j < 4; j++) in[j] = c >= 0 ? (j == c ? 1. : 0.) : a.ambig[(size_t)(-c - 1) * 4 + j];
-  }
-  const double f = a.freq[s];
-  for (int k = a.tr_off[bi]; k < a.tr_off[bi + 1]; k++) {
-    const int t = a.tr_idx[k];
-    const double *M = a.img + ((size_t)t * a.C + a.cls) * 16;
-    double l = 0.;
-    for (int x = 0; x < 4; x++) l += V[x] * (M[4 * x] * in[0] + M[4 * x + 1] * in[1] + M[4 * x + 2] * in[2] + M[4 * x + 3] * in[3]);
-    const size_t q = (size_t)t * SP + s;
+  int bcnt, ecnt;
+  const int4 ce = nuc_branch_outside(wa, sl, bi, tile, lane, V, bcnt);
+  nuc_child_vec(wa, ce, s, in, ecnt);
+  bcnt += ecnt;
+  const double f = sl.freq[s];
+  for (int k = sl.off[bi]; k < sl.off[bi + 1]; k++) {
+    const int t = sl.idx[k];
+    double E[4], l = 0.;
+    mat4_vec(a.img + ((size_t)t * sl.C + sl.cls) * 16, in, E);
+    for (int x = 0; x < 4; x++) l += V[x] * E[x];
+    const size_t q = (size_t)t * wa.S_pad + s;
     int e = bcnt;
-    mix_in(a, q, l, e);
+    mix_in(sl, a, q, l, e);
     a.lik[q] = l;
     a.cnt[q] = e;
-    if (a.last) {
+    if (sl.last) {
       double wsum = 0.;
       long long wcnt = 0;
       int wflag = 0;
       site_term(l, e, f, wsum, wcnt, wflag);
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        wsum += __shfl_xor(wsum, off);
-        wcnt += __shfl_xor(wcnt, off);
-        wflag |= __shfl_xor(wflag, off);
-      }
-      if (lane == 0) {
-        const size_t pq = (size_t)t * a.part_stride + tile;
-        a.part_sum[pq] = wsum;
-        a.part_cnt[pq] = wcnt;
-        a.part_flag[pq] = wflag;
-      }
+      put_record<64>(sl, a, t, tile, lane, wsum, wcnt, wflag);
     }
   }
 }
@@ -254,21 +219,10 @@ int trials_common(const char *what, hyphy_hip_partition *p, int64_t n_trials, co
     launch_expm(ea, s.stream);
     set_last_expm_kernel(expm_before);
     HIPCHK(hipGetLastError());
+    const TrialArgs ta = {img, lik, cnt, part_sum, part_cnt, part_flag};
     const int walked = outside_chunks(p, s, oc, sc, weights, [&](const WalkArgs &a, const OutsideSlice &sl, dim3 grid) {
-      TrialArgs ta;
-      ta.NW = NW, ta.L = a.L, ta.S_pad = a.S_pad, ta.ntiles = a.ntiles, ta.tile0 = sl.tile0, ta.ct = sl.ct;
-      ta.C = sl.C, ta.cls = sl.cls, ta.first = sl.first, ta.last = sl.last, ta.b0 = sl.b0;
-      ta.w = sl.w;
-      ta.branch = sl.branch, ta.tr_off = sl.off, ta.tr_idx = sl.idx;
-      ta.img = img;
-      ta.V = sl.V, ta.Vcnt = sl.Vcnt;
-      ta.partials = a.partials, ta.counts = a.counts;
-      ta.codes_tile = a.codes_tile, ta.codes = a.codes;
-      ta.ambig = a.ambig, ta.freq = s.freq;
-      ta.lik = lik, ta.cnt = cnt;
-      ta.part_sum = part_sum, ta.part_cnt = part_cnt, ta.part_flag = part_flag, ta.part_stride = sl.part_stride;
-      if (nuc) hipLaunchKernelGGL(branch_trials_nuc_kernel, grid, dim3(64), 0, s.stream, ta);
-      else LAUNCH_NW(branch_trials_kernel, NW, grid, dim3(64), s.stream, ta);
+      if (nuc) hipLaunchKernelGGL(branch_trials_nuc_kernel, grid, dim3(64), 0, s.stream, a, sl, ta);
+      else LAUNCH_NW(branch_trials_kernel, NW, grid, dim3(64), s.stream, a, sl, ta);
     });
     if (walked) return -1;
     hipLaunchKernelGGL(trials_reduce_kernel, dim3((unsigned)n_trials), dim3(64), 0, s.stream, part_sum, part_cnt, part_flag, sc.ntiles,
