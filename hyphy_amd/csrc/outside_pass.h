@@ -1,4 +1,4 @@
-// The host side of the passes that keep every branch's outside vector (trials.hip, deriv.hip, grad.hip), once: behind outside.h's
+// The host side of the passes that keep every branch's outside vector (trials.hip, nni.hip, deriv.hip, grad.hip), once: behind outside.h's
 // check_pass_ready, what they refuse of their requests, then the per-shard scratch and the loop over chunks of tiles and rate classes.
 //   check_requests                      the refusals, in the order and with the words the entry points have always had
 //   begin_outside                       outside.h's (pending work finished, classes resident, program, pi), and the requests grouped

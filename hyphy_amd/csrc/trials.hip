@@ -18,62 +18,21 @@
 //
 // The refusals, the scratch of the walk and the loop over chunks of tiles and classes are outside_pass.h's, shared with deriv.hip and
 // grad.hip; a phase-2 kernel gets (WalkArgs, OutsideSlice, TrialArgs) and starts from outside.h's branch prologue (branch_outside,
-// child_vec and their 4-state forms), mixes through align_exponents and ends in wave_sum / wave_or.  What is here is the trials' own:
-// their result blocks, the trial images (and the column gather from them), phase 2 and the reduction.  All scratch comes from the pool
+// child_vec and their 4-state forms), mixes through align_exponents and ends in wave_sum / wave_or.  The per-pattern mix, the records
+// and the reduction are site_mix.h's, shared with nni.hip.  What is here is the trials' own: the trial images (and the column gather
+// from them) and phase 2.  All scratch comes from the pool
 // and goes back before the call returns.  The partition's matrices, images, schedules and caches are not written.
 // 4 states: one thread per pattern over the plane layout and row-major matrices.
 #include "combine.h"
 #include "devutil.h"
 #include "outside_pass.h"
 #include "partition.h"
+#include "site_mix.h"
 
 using namespace hyhip;
 
 namespace hyhip {
 namespace {
-
-struct TrialArgs {      // the trials' own blocks, beside the WalkArgs and the OutsideSlice
-  const double *img;    // [n_trials][C] trial matrices: A-operand images (4 states: [16] row-major)
-  double *lik;          // [n_trials][S_pad] per pattern: classes mixed so far
-  int32_t *cnt;
-  double *part_sum;     // [n_trials][part_stride] per (trial, tile): sum_s f_s log l_s, sum_s f_s c_s, flags
-  long long *part_cnt;
-  int *part_flag;
-};
-
-// this class's value (l, exponent e) of pattern q into the mix of the classes before it, aligned on the smaller exponent (the larger
-// scale), as MargSink::add of marginal.hip aligns its numerators
-__device__ __forceinline__ void mix_in(const OutsideSlice &sl, const TrialArgs &a, size_t q, double &l, int &e) {
-  l *= sl.w;
-  if (sl.first) return;
-  double so, sn;
-  e = align_exponents(a.cnt[q], e, so, sn);
-  l = a.lik[q] * so + l * sn;
-}
-
-// the pattern's term of the trial's total (bc_eval_kernel's rule: 1 a zero likelihood, 2 not a number)
-__device__ __forceinline__ void site_term(double l, int e, double f, double &wsum, long long &wcnt, int &wflag) {
-  if (f == 0.) return;
-  if (l != l || isinf(l)) wflag |= 2;
-  else if (l <= 0.) wflag |= 1;
-  else {
-    wsum += log(l) * f;
-    wcnt += (long long)e * (long long)f;
-  }
-}
-
-// the record of (trial t, tile): the terms of its W lanes summed, written by lane 0
-template <int W>
-__device__ __forceinline__ void put_record(const OutsideSlice &sl, const TrialArgs &a, int t, int tile, int lane, double wsum,
-                                           long long wcnt, int wflag) {
-  wsum = wave_sum<W>(wsum), wcnt = wave_sum<W>(wcnt), wflag = wave_or<W>(wflag);
-  if (lane == 0) {
-    const size_t pq = (size_t)t * sl.part_stride + tile;
-    a.part_sum[pq] = wsum;
-    a.part_cnt[pq] = wcnt;
-    a.part_flag[pq] = wflag;
-  }
-}
 
 template <int NW>
 __global__ __launch_bounds__(64) void branch_trials_kernel(WalkArgs wa, OutsideSlice sl, TrialArgs a) {
@@ -147,22 +106,6 @@ __global__ __launch_bounds__(64) void branch_trials_nuc_kernel(WalkArgs wa, Outs
       site_term(l, e, f, wsum, wcnt, wflag);
       put_record<64>(sl, a, t, tile, lane, wsum, wcnt, wflag);
     }
-  }
-}
-
-// log-L of trial blockIdx.x = sum_s f_s log l_s - 64 ln2 sum_s f_s c_s from its per-tile partial sums: one wave, fixed order, compensated
-__global__ __launch_bounds__(64) void trials_reduce_kernel(double *part_sum, long long *part_cnt, int *part_flag, int n, int stride,
-                                                           double *__restrict__ out) {
-  const size_t o = (size_t)blockIdx.x * stride;
-  double sum, comp;
-  long long c;
-  int fl;
-  combine_range(part_sum + o, part_cnt + o, part_flag + o, n, 0, n, (int)threadIdx.x, sum, comp, c, fl);
-  if (threadIdx.x == 0) {
-    double r = (sum - comp) - kLogScaler * (double)c;
-    if (fl & 2) r = NAN;
-    else if (fl & 1) r = -INFINITY;
-    out[blockIdx.x] = r;
   }
 }
 

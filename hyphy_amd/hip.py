@@ -28,6 +28,7 @@ EXPORTS = [
     "hyphy_hip_xch_open", "hyphy_hip_xch_sum", "hyphy_hip_xch_close", "hyphy_hip_last_error", "hyphy_hip_last_expm_kernel",
     "hyphy_hip_evaluate_categories_mixture", "hyphy_hip_evaluate_categories_mixture_built",
     "hyphy_hip_hmm_set_sites", "hyphy_hip_hmm_logl", "hyphy_hip_hmm_viterbi", "hyphy_hip_evaluate_categories_hmm", "hyphy_hip_evaluate_categories_built_hmm", "hyphy_hip_plan_hmm", "hyphy_hip_hmm_host",
+    "hyphy_hip_nni_scores", "hyphy_hip_plan_nni", "hyphy_hip_check_nni",
     "hyphy_hip_version",
 ]
 
@@ -179,6 +180,12 @@ def load():
         fn.argtypes = [vp, C.c_int64, lp, dp, dp, dp, lp]
     lib.hyphy_hip_expm_frechet_adjoint_batch.restype = C.c_int
     lib.hyphy_hip_expm_frechet_adjoint_batch.argtypes = [C.c_int64, C.c_int64, dp, dp, dp]
+    lib.hyphy_hip_nni_scores.restype = C.c_int
+    lib.hyphy_hip_nni_scores.argtypes = [vp, C.c_int64, lp, dp, dp, dp, lp]
+    lib.hyphy_hip_plan_nni.restype = C.c_int64
+    lib.hyphy_hip_plan_nni.argtypes = [C.c_int64, C.c_int64, lp, lp, C.c_int64]
+    lib.hyphy_hip_check_nni.restype = C.c_int
+    lib.hyphy_hip_check_nni.argtypes = [C.c_int64, C.c_int64, lp, C.c_int64, lp]
     lib.hyphy_hip_plan_marginal.restype = C.c_int64
     lib.hyphy_hip_plan_marginal.argtypes = [C.c_int64, C.c_int64, lp, lp, C.c_int64]
     lib.hyphy_hip_plan_trunk_walk.restype = C.c_int64
@@ -382,6 +389,33 @@ def plan_marginal(flat_parents, L: int) -> dict:
         raise HipError("plan_marginal: " + lib.hyphy_hip_last_error().decode())
     ne = int(out[0])
     return {"entries": [tuple(int(x) for x in out[2 + 4 * k: 6 + 4 * k]) for k in range(ne)], "maxk": int(out[1])}
+
+
+def plan_nni(flat_parents, L: int) -> np.ndarray:
+    """Host-only: every nearest-neighbour interchange of a tree as rows (x, y), [n, 2], in ascending (c, y, x): c = parent(x) is an
+    internal node other than the root and y a sibling of c; the move exchanges the parents of x and y (``HipPartition.nni_scores``,
+    ``hyphy_amd.nni.apply_nni``)."""
+    lib = load()
+    par = np.ascontiguousarray(flat_parents, dtype=np.int64)
+    I = len(par) - int(L)
+    out = np.zeros(1, dtype=np.int64)
+    n = lib.hyphy_hip_plan_nni(int(L), I, _l(par), _l(out), 1)            # (one word is enough for a tree without a move)
+    if n < -1:
+        out = np.zeros(-n, dtype=np.int64)
+        n = lib.hyphy_hip_plan_nni(int(L), I, _l(par), _l(out), len(out))
+    if n < 0:
+        raise HipError("plan_nni: " + lib.hyphy_hip_last_error().decode())
+    return out[1: 1 + 2 * int(out[0])].reshape(-1, 2).copy()
+
+
+def check_nni(flat_parents, L: int, moves) -> None:
+    """Host-only: raise ``HipError`` naming the first pair of ``moves`` ([n, 2]: x, y) that is not a move of the tree, in the words
+    ``HipPartition.nni_scores`` refuses it with; return None when every pair is one."""
+    lib = load()
+    par = np.ascontiguousarray(flat_parents, dtype=np.int64)
+    mv = np.ascontiguousarray(moves, dtype=np.int64).reshape(-1, 2)
+    if lib.hyphy_hip_check_nni(int(L), len(par) - int(L), _l(par), len(mv), _l(mv)) < 0:
+        raise HipError(lib.hyphy_hip_last_error().decode())
 
 
 def plan_nucgen(flat_parents, L: int, leaf_has_ambig=None, compile_it: bool = True, small: bool = False):
@@ -1124,6 +1158,23 @@ class HipPartition:
         K = int(np.asarray(coeffs).shape[-1])
         nd, co, w, ll, sl, sc = self._trial_args(nodes, coeffs, (K,), weights, per_site)
         _check(self._lib.hyphy_hip_branch_trials_built(self._h, len(nd), _l(nd), _d(co), _d(w), _d(ll), _d(sl), _l(sc)))
+        return (ll, sl, sc) if per_site else ll
+
+    # -- every nearest-neighbour interchange's log-L from one outside pass ---------------------------
+    def nni_scores(self, moves, weights=None, per_site: bool = False):
+        """log-L [n] of the trees in which ``moves[t] = (x, y)`` exchange parents (c = parent(x) internal and not the root, y a sibling
+        of c; ``plan_nni`` lists every such pair), every branch keeping its matrix and everything else as at the last evaluation of
+        every class: one outside pass serves every move of the call.  ``weights``: class weights when C > 1.  ``per_site``: also the
+        per-pattern values and 2^64 exponents, [n, S] each.  Nothing on the device changes."""
+        mv = np.ascontiguousarray(moves, dtype=np.int64).reshape(-1, 2)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            assert w.shape == (self.C,)
+        ll = np.zeros(len(mv))
+        sl = np.zeros((len(mv), self.S)) if per_site else None
+        sc = np.zeros((len(mv), self.S), dtype=np.int64) if per_site else None
+        _check(self._lib.hyphy_hip_nni_scores(self._h, len(mv), _l(mv), _d(w), _d(ll), _d(sl), _l(sc)))
         return (ll, sl, sc) if per_site else ll
 
     # -- first and second log-L derivatives of any number of branches from one outside pass --------

@@ -518,6 +518,43 @@ int hyphy_hip_branch_trials_built(hyphy_hip_partition *p, int64_t n_trials, cons
                                   const double *weights /* [C] or NULL */, double *logl_out, double *site_lik_out,
                                   int64_t *site_scaler_out);
 
+/* ---- every nearest-neighbour interchange's log-likelihood from one outside pass -------------------------------
+ * Replaces the one rebuilt tree and full evaluation per swap of the reference's doNNISwap.bf / branchSwappingFunctions.bf.  A move is
+ * a pair of node codes (x, y): c = parent(x) must be an internal node other than the root, y a sibling of c (parent(y) ==
+ * parent(c) == p, y != c).  The neighbour tree is the one in which x and y exchange parents; every branch keeps its own matrix
+ * (P_x travels with x, P_y with y, P_c stays on the edge c -> p).  Only the child sets of c and p change, so with E_k = P_k in_k the
+ * edge product of child k and U_n the outside vector at node n (U_root = pi), per pattern and class
+ *   R     = U_p * prod E_k   over the children k of p other than c and y
+ *   inner = E_y * prod E_k   over the children k of c other than x
+ *   l     = sum_i R[i] E_x[i] (P_c inner)[i],      2^64 exponent = exponent(R) + exponent(E_x) + exponent(inner).
+ * Nothing assumes binary nodes; on a binary tree every internal non-root branch has two moves.
+ *   moves   [n][2]               x, y; any order, repeats allowed
+ *   weights [C] (NULL when C == 1) class weights; the classes of a move are mixed by weight as hyphy_hip_branch_trials mixes them
+ *   logl_out [n]                 what hyphy_hip_evaluate (C == 1) / hyphy_hip_evaluate_categories (C > 1) would return on the neighbour
+ *                                tree with everything else as at the last evaluation of each class; -INFINITY when the move makes a
+ *                                pattern of positive frequency impossible, NaN where one has a NaN
+ *   site_lik_out / site_scaler_out [n][S] or NULL: per pattern (l, c) in the caller's pattern order, meaning as in hyphy_hip_evaluate
+ * Call after an evaluation of every class.  Leaves no state behind, as hyphy_hip_branch_derivatives: the device's matrices and images,
+ * the schedules, the tuner's state, the class tables, the branch-cache slots, hyphy_hip_last_expm_kernel and
+ * hyphy_hip_last_reduce_form are what they were (persisted copies are restored first if the last full pass kept them on chip).  Two
+ * identical calls give identical bits: fixed-order compensated sums per shard, combined over shards as the log-likelihoods are.
+ * Chunks of tiles and scratch as hyphy_hip_branch_trials, under the same budget (HYPHY_HIP_TRIALS_MB).  4-state partitions are served.
+ * Returns < 0 for a NULL partition, move list or output, an active pin, a class never evaluated, C > 1 without weights, or a pair that
+ * is not a move (hyphy_hip_last_error names it: its index, the pair and the rule it breaks); the partition stays usable.  n == 0
+ * returns 0 and writes nothing.
+ * Out of scope: subtree pruning and regrafting, trial matrices for the central branch, re-fitting inside the call. */
+int hyphy_hip_nni_scores(hyphy_hip_partition *p, int64_t n, const int64_t *moves /* [n][2]: x, y */,
+                         const double *weights /* [C] or NULL */, double *logl_out /* [n] */,
+                         double *site_lik_out, int64_t *site_scaler_out /* [n][S] or NULL, caller's pattern order */);
+/* Host-only: every move of a tree in ascending (c, y, x).  flat_parents [L+I] as hyphy_hip_create takes it.
+ * out[0] = moves n, then n pairs x, y.  Returns the words written (1 + 2 n), -(words needed) when cap is too small (out may be NULL),
+ * -1 on bad arguments.  (A tree without a move needs one word: ask with cap >= 1 to tell it from bad arguments.) */
+int64_t hyphy_hip_plan_nni(int64_t L, int64_t I, const int64_t *flat_parents, int64_t *out, int64_t cap);
+/* Host-only: the refusal of hyphy_hip_nni_scores without a partition.  0 when every pair of moves [n][2] is a move of the tree; < 0
+ * with hyphy_hip_last_error naming the first that is not, in the words hyphy_hip_nni_scores uses ("move t (x, y): ..."), or on bad
+ * arguments.  One function holds the rule: this entry point and hyphy_hip_nni_scores refuse by it, hyphy_hip_plan_nni lists by it. */
+int hyphy_hip_check_nni(int64_t L, int64_t I, const int64_t *flat_parents, int64_t n, const int64_t *moves /* [n][2]: x, y */);
+
 /* ---- every branch's first and second log-L derivatives from one outside pass ---------------------------------
  * The exact derivatives an optimiser moves branch lengths with, all branches in one call and without an exponential.  With V the
  * outside vector of branch b and E = P_b in_b its edge product (both exactly what the pass above forms), per pattern and class
