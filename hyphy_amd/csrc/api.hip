@@ -609,7 +609,12 @@ int prepare_schedule(hyphy_hip_partition *p, int cat, const int64_t *update_node
   const bool requested_full = full;
   bool persist_all = true;
   const std::vector<char> &res = p->mode == 1 ? p->rep_resident : p->resident;  // (each view keeps its own copies)
-  if (!full && !res[cat]) full = true;  // a partial update needs current persisted copies: promote to a persisting full pass
+  // a partial update needs current persisted copies of EVERY class it walks: promote to a persisting full pass.  (A class batch is
+  // keyed on class 0, but after a lazy batched full pass a one-class update restores that class's copies alone: the batch that
+  // follows must not take class 0's word for the others.)
+  bool stale = false;
+  for (int c = cat; c < cat + n_classes && c < (int)res.size(); c++) stale = stale || !res[c];
+  if (!full && stale) full = true;
   else if (full && p->initialized[cat] && p->cache_policy == 1 && p->last_full[cat] && !force_persist)
     persist_all = false;
   p->sched_full = full;
@@ -914,6 +919,7 @@ int checked_partition(const CreateInput &in, int device_first, int device_count,
   p->bc_node.assign(C, -1);
   p->bc_use_pi.assign(C, 0);
   p->resident.assign(C, 0);
+  p->pin_left.assign(C, std::vector<int64_t>());
   p->last_full.assign(C, 0);
   p->cache_policy = sw::cache_always() ? 0 : 1;
   p->leaf_has_ambig.assign(L, 0);
@@ -1308,6 +1314,28 @@ int finish_pending_async(hyphy_hip_partition *p) {
   return 0;
 }
 
+// What class c's stored conditionals and per-pattern values hold of a pin after the evaluation just enqueued (partition.h: pin_left).
+// A pin sits in the conditional of the pinned internal node, or of the pinned leaf's parent.  The evaluation recomputed that node — and
+// with it everything above — when it was a full pass or listed anything below it as dirty (build_schedule recomputes every ancestor of a
+// listed node); a node it recomputed without the pin is clean again, the pinned one is not.
+static void note_pins(hyphy_hip_partition *p, int64_t c, const int64_t *update_nodes, int64_t n_update) {
+  std::vector<int64_t> &left = p->pin_left[(size_t)c];
+  if (left.empty() && p->pin_node < 0) return;
+  const auto recomputed = [&](int64_t n) {
+    if (p->sched_full) return true;
+    const int64_t at = n < p->L ? p->parents[(size_t)n] : n - p->L;  // internal index of the node whose conditional holds the pin
+    for (int64_t k = 0; k < n_update; k++) {
+      const int64_t u = update_nodes[k];
+      if (u < 0 || u >= p->B) continue;
+      for (int64_t a = p->parents[(size_t)u]; a >= 0 && a <= at; a = p->parents[(size_t)(p->L + a)])
+        if (a == at) return true;  // (children are numbered before parents: the walk stops once it is past the node)
+    }
+    return false;
+  };
+  left.erase(std::remove_if(left.begin(), left.end(), [&](int64_t n) { return n != p->pin_node && recomputed(n); }), left.end());
+  if (p->pin_node >= 0 && std::find(left.begin(), left.end(), p->pin_node) == left.end()) left.push_back(p->pin_node);
+}
+
 int eval_common(hyphy_hip_partition *p, const EvalRequest &rq) {
   int64_t cat = rq.cat, n_update = rq.n_update;  // (rewritten below: class batching, new root frequencies)
   const int64_t *update_nodes = rq.update_nodes, *const q_nodes = rq.q_nodes;
@@ -1417,6 +1445,7 @@ int eval_common(hyphy_hip_partition *p, const EvalRequest &rq) {
   if (!res_other.empty()) res_other[cat] = 0;
   if (batch) std::fill(p->pi_stale.begin(), p->pi_stale.end(), 0);  // (every pass reaches the root)
   else p->pi_stale[cat] = 0;
+  for (int64_t c = batch ? 0 : cat; c < (batch ? p->C : cat + 1); c++) note_pins(p, c, update_nodes, n_update);
   return 0;  // (coefficients staged by hyphy_hip_build_q stay valid — and pending — until the next hyphy_hip_build_q)
 }
 

@@ -376,6 +376,12 @@ int hmm_check(const hyphy_hip_partition *p, const double *transition, const doub
   if (p->hmm_n_sites <= 0 || !p->shards[0].hmm_sites) return fail(pre + "no site list (hyphy_hip_hmm_set_sites)");
   if (check_unpinned(p, pre)) return -1;
   if (need_evaluated && check_evaluated(p, pre)) return -1;
+  // (the per-pattern values of a class carry the root frequencies of that class's own last evaluation: one class evaluated alone
+  //  under new frequencies leaves the others' values behind, and the chain would mix the two)
+  for (size_t c = 0; need_evaluated && c < p->pi_stale.size(); c++)
+    if (p->pi_stale[c])
+      return fail(pre + "the per-pattern values of rate class " + std::to_string(c) +
+                  " were combined under other root frequencies than the last evaluation's (evaluate that class again)");
   return 0;
 }
 

@@ -351,6 +351,10 @@ struct hyphy_hip_partition {
   bool rr_active = false;                    // the current schedule is a re-rooted one
   std::vector<int64_t> perm;                 // internal pattern j = caller's pattern perm[j] (empty: identity); see sort_patterns()
   int64_t pin_node = -1;                     // node code whose states are pinned for the evaluations that follow (-1: none)
+  // per class: the nodes whose pin the class's persisted conditionals and per-pattern values still hold — the active one after an
+  // evaluation under it, and a removed one until an evaluation recomputes the node (eval_common: a full pass, or a partial one that
+  // lists anything below the node that carries the pin).  The passes over those values refuse while a list is not empty (check_unpinned).
+  std::vector<std::vector<int64_t>> pin_left;
   std::vector<int64_t> bc_node;              // per rate class: branch whose outside vector is resident (-1: none)
   std::vector<int> bc_use_pi;                // ... hangs off the root (frequencies applied at evaluation)
   int variant = 0;                           // pruning kernel variant (common.h PruneArgs::variant)
@@ -415,7 +419,13 @@ inline int twin_slot0(const hyphy_hip_partition *p) { return (int)(p->B + (p->I 
 // ---- shared by the passes over the resident conditionals (marginal.hip, trials.hip, deriv.hip, joint.hip, sample.hip) -----
 // what they refuse (`pre`: the entry point's name and ": "; `used`: the classes the call reads, nullptr: all)
 inline int check_unpinned(const hyphy_hip_partition *p, const std::string &pre) {
-  return p->pin_node >= 0 ? fail(pre + "a node's states are pinned (clear the pin first)") : 0;
+  if (p->pin_node >= 0) return fail(pre + "a node's states are pinned (clear the pin first)");
+  for (size_t c = 0; c < p->pin_left.size(); c++)
+    if (!p->pin_left[c].empty())
+      return fail(pre + "rate class " + std::to_string(c) + " was last evaluated with node " + std::to_string(p->pin_left[c].front()) +
+                  " pinned: its conditionals and per-pattern values still hold the pin (evaluate again with the node's path among "
+                  "update_nodes first, see hyphy_hip_set_pinned_states)");
+  return 0;
 }
 inline int check_evaluated(const hyphy_hip_partition *p, const std::string &pre, const std::vector<char> *used = nullptr) {
   for (int64_t c = 0; c < p->C; c++)

@@ -457,7 +457,17 @@ int hyphy_hip_set_timing_detail(hyphy_hip_partition *p, int on);
  * node `node` (node code: leaf l -> l, internal i -> L + i, the root included) fixed to states[pattern] in
  * [0, D).  node < 0 or states == NULL removes the pin.  The caller lists the node (and, after removing the pin,
  * lists it again) among update_nodes, as RecoverAncestralSequencesMarginal does with
- * AddBranchToForcedRecomputeList (src/core/likefunc2.cpp:932-1040). */
+ * AddBranchToForcedRecomputeList (src/core/likefunc2.cpp:932-1040): the node itself and its ancestors' branches, and for an
+ * internal node its children (a node is recomputed when one of its children is listed).
+ * A pin left behind: removing the pin changes nothing on the device, so the persisted conditionals and per-pattern values of every
+ * class evaluated under it still hold it until an evaluation of that class without the pin recomputes the node that carries it (the
+ * pinned internal node, or the pinned leaf's parent): a full pass, or a partial one that lists anything below that node among
+ * update_nodes (a partial evaluation recomputes every ancestor of a listed node).  Until then every pass over those values
+ * (hyphy_hip_marginal_ancestral, _joint_ancestral, _sample_ancestral, _branch_trials*, _branch_derivatives*, _branch_sensitivities,
+ * _branch_gradient*, _nni_scores, _hmm_logl, _hmm_viterbi) returns < 0 and names the class and the node; evaluations are never
+ * refused for it.  "The last evaluation of each class" in the descriptions of those passes is therefore never a pinned one.
+ * NOT covered: hyphy_hip_branch_cache_build and hyphy_hip_download_partials read the same conditionals and are served as they stand
+ * (a download is how a caller looks at a pinned evaluation's conditionals); the caller re-evaluates the path before a cache build. */
 int hyphy_hip_set_pinned_states(hyphy_hip_partition *p, int64_t node, const int64_t *states /* [S] */);
 
 /* ---- marginal ancestral reconstruction in one pass --------------------------------------------------------
@@ -476,7 +486,7 @@ int hyphy_hip_set_pinned_states(hyphy_hip_partition *p, int64_t node, const int6
  * the mix of the other classes by their shares of the pattern's likelihood, whatever 2^64 exponent the zero class carries.  (In a
  * leaf row this leaves out such a class's L_s(leaf = x) at the states x that the leaf's own data exclude.)  A pattern that is
  * impossible under every class gets NaN in all D entries of each of its rows, map_state -1 and map_support NaN; the call succeeds.
- * Returns < 0 when a pin is active, a class was never evaluated, or C > 1 without weights.  Leaves no state behind: later
+ * Returns < 0 when a pin is active or left behind, a class was never evaluated, or C > 1 without weights.  Leaves no state behind: later
  * evaluations, partial updates and a branch cache built before the call give what they give without it. */
 int hyphy_hip_marginal_ancestral(hyphy_hip_partition *p, int64_t which, const double *weights /* [C] or NULL */,
                                  double *support_out, int64_t *map_state_out, double *map_support_out);
@@ -509,7 +519,7 @@ int64_t hyphy_hip_plan_marginal(int64_t L, int64_t I, const int64_t *flat_parent
  * first if the last full pass kept them on chip, as before a marginal reconstruction).  Two identical calls give identical bits.
  * The outside vectors take B x tiles x 16 DP doubles: the pass runs over chunks of tiles that keep them within HYPHY_HIP_TRIALS_MB
  * (default 1024, read at every call, at least one tile); all scratch comes from the pool and is returned before the call returns.
- * Returns < 0 when a pin is active, a class was never evaluated, C > 1 without weights, a node code is out of range or the root's,
+ * Returns < 0 when a pin is active or left behind, a class was never evaluated, C > 1 without weights, a node code is out of range or the root's,
  * or a trial matrix cannot be exponentiated; n_trials == 0 returns 0 and writes nothing. */
 int hyphy_hip_branch_trials(hyphy_hip_partition *p, int64_t n_trials, const int64_t *nodes, const double *q_dense,
                             int q_is_probability, const double *weights /* [C] or NULL */, double *logl_out,
@@ -539,7 +549,7 @@ int hyphy_hip_branch_trials_built(hyphy_hip_partition *p, int64_t n_trials, cons
  * hyphy_hip_last_reduce_form are what they were (persisted copies are restored first if the last full pass kept them on chip).  Two
  * identical calls give identical bits: fixed-order compensated sums per shard, combined over shards as the log-likelihoods are.
  * Chunks of tiles and scratch as hyphy_hip_branch_trials, under the same budget (HYPHY_HIP_TRIALS_MB).  4-state partitions are served.
- * Returns < 0 for a NULL partition, move list or output, an active pin, a class never evaluated, C > 1 without weights, or a pair that
+ * Returns < 0 for a NULL partition, move list or output, a pin active or left behind, a class never evaluated, C > 1 without weights, or a pair that
  * is not a move (hyphy_hip_last_error names it: its index, the pair and the rule it breaks); the partition stays usable.  n == 0
  * returns 0 and writes nothing.
  * Out of scope: subtree pruning and regrafting, trial matrices for the central branch, re-fitting inside the call. */
@@ -582,7 +592,7 @@ int hyphy_hip_check_nni(int64_t L, int64_t I, const int64_t *flat_parents, int64
  * first if the last full pass kept them on chip, as before a marginal reconstruction); hyphy_hip_last_reduce_form is what it was
  * too.  Two identical calls give identical bits: the totals are fixed-order compensated sums per shard, combined over shards as
  * the log-likelihoods are.  Chunks of tiles and scratch as hyphy_hip_branch_trials, under the same budget (HYPHY_HIP_TRIALS_MB).
- * Returns < 0 for a NULL partition or output, an active pin, a class never evaluated, C > 1 without weights, a node code out of
+ * Returns < 0 for a NULL partition or output, a pin active or left behind, a class never evaluated, C > 1 without weights, a node code out of
  * range or the root's, templates not set (_built); n == 0 returns 0 and writes nothing. */
 int hyphy_hip_branch_derivatives(hyphy_hip_partition *p, int64_t n, const int64_t *nodes, const double *g_dense,
                                  const double *weights /* [C] or NULL */, double *d1_out, double *d2_out, int64_t *skipped_out,
@@ -626,7 +636,7 @@ int hyphy_hip_branch_derivatives_built(hyphy_hip_partition *p, int64_t n, const 
  * shard order; the order may depend on the budget, the allowances do not.  (L_s is formed at the requested branch of lowest node code:
  * calls that request different sets of branches may differ in the last bits of a branch they share.)  Chunks of tiles and scratch as hyphy_hip_branch_trials,
  * under the same budget (HYPHY_HIP_TRIALS_MB); with C > 1 the walk runs twice (the mixed L_s must be complete before any class's sum).
- * 4-state partitions are served; there is no "unsupported" return.  Returns < 0 for a NULL partition or output, an active pin, a class
+ * 4-state partitions are served; there is no "unsupported" return.  Returns < 0 for a NULL partition or output, a pin active or left behind, a class
  * never evaluated, C > 1 without weights, a node code out of range or the root's, templates not set (_built); n == 0 returns 0 and
  * writes nothing.
  * Out of scope: the derivatives in the class weights and in the root frequencies (the host has both from the per-class per-pattern
@@ -661,7 +671,7 @@ int hyphy_hip_expm_frechet_adjoint_batch(int64_t D, int64_t n, const double *q_d
  * in, and leaves no state behind.  Scratch (about I x 16 x DP x 9 bytes per 16-pattern tile) comes from the pool and is returned
  * before the call returns; the pass runs over chunks of tiles that keep it within HYPHY_HIP_JOINT_MB (default 1024, read at every
  * call, at least one tile).  Two identical calls give identical arrays.
- * Returns < 0 on a NULL partition or output, an active pin, a class id out of range, or a referenced class never evaluated. */
+ * Returns < 0 on a NULL partition or output, a pin active or left behind, a class id out of range, or a referenced class never evaluated. */
 int hyphy_hip_joint_ancestral(hyphy_hip_partition *p, int do_leaves, const int64_t *class_of_pattern /* [S] or NULL */,
                               int64_t *states_out /* [I (+ L)][S] */);
 
@@ -692,7 +702,7 @@ int hyphy_hip_joint_ancestral(hyphy_hip_partition *p, int do_leaves, const int64
  * identical calls give identical arrays.  Scratch (a byte, and with `uniforms` a double, per draw) comes from the pool and is
  * returned before the call returns; the pass runs over chunks (replicates x 16-pattern tiles) that keep it within
  * HYPHY_HIP_SAMPLE_MB (default 1024, read at every call, at least one tile x one replicate).
- * Returns < 0 on a NULL partition or output, an active pin, a pattern or class index out of range, a referenced class never
+ * Returns < 0 on a NULL partition or output, a pin active or left behind, a pattern or class index out of range, a referenced class never
  * evaluated, or a supplied uniform outside [0, 1); n_rep == 0 or n_sites == 0 returns 0 and writes nothing. */
 int hyphy_hip_sample_ancestral(hyphy_hip_partition *p, int64_t n_rep, int64_t n_sites,
                                const int64_t *pattern_of_site /* [n_sites] or NULL */,
@@ -782,7 +792,11 @@ int hyphy_hip_simulate_uniforms(uint64_t seed, int64_t n_rep, int64_t n_nodes, i
  * The parenthesisation depends on (n_sites, C) alone (hyphy_hip_plan_hmm): two identical calls give identical bits, whatever
  * HYPHY_HIP_TUNE says.  Host and device results are NOT bit-identical (-ffp-contract=fast contracts differently on the two sides).
  * Returns: 0; 1 "use the CPU path" for C == 1 or C > 8; < 0 (hyphy_hip_last_error): a NULL argument, a negative or infinite entry of
- * transition / initial, no site list, an active pin (hyphy_hip_set_pinned_states), a class that has never been evaluated.
+ * transition / initial, no site list, a pin active or left behind (hyphy_hip_set_pinned_states), a class that has never been evaluated,
+ * or (hmm_logl, hmm_viterbi) a class whose last evaluation ran under other root frequencies than the partition's last one: its
+ * per-pattern values still carry the old frequencies (one class evaluated alone under new ones leaves the others behind).  The
+ * rule is kept per change, not per value: ANY evaluation under other frequencies than the one before marks every other class, also
+ * when it returns to frequencies those classes were combined under; evaluating them again (no matrices needed) clears it.
  * The calls leave no state behind: matrices, images, schedules, tuner state, class tables, branch-cache slots, lazy-persistence flags,
  * the mixed per-pattern values, the cached weights and hyphy_hip_last_expm_kernel are what they were; scratch comes from the pool and
  * is back before the call returns.  A multi-shard partition brings every shard's values to shard 0 by device-to-device copies behind

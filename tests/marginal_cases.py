@@ -31,6 +31,19 @@ MAP_MARGIN = 1e-6      # MAP states are compared with the reference where its tw
 MAP_LEFT_OUT = 1e-3    # and the margin may leave out at most this share of the (row, pattern) entries
 
 
+def pin_update_list(fp, L, code):
+    """The update list of an evaluation with node ``code`` pinned, and of the one that puts the path back after the pin is removed:
+    the node's own path, and the children of an internal node (the node itself is recomputed when one of its children is listed)."""
+    from hyphy_amd import tree
+    flat = tree.flat_from_parents(fp, L)
+    out = set()
+    if int(flat.flat_parents[code]) >= 0:
+        out.update(int(x) for x in flat.path_update_nodes(int(code)))
+    if code >= L:
+        out.update(int(c) for c in flat.children_of(code - L))
+    return np.array(sorted(out), dtype=np.int64)
+
+
 def hold_support(what, got, ref, sums_to_one=False):
     """``got`` [rows, S', D] against the reference's ``ref``: finite wherever the reference is; |got - ref| <= RTOL x ref for every
     entry with ref >= FLOOR and <= RTOL x FLOOR below it; rows summing to 1 within 1e-12 (internal rows).  Returns the largest

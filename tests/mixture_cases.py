@@ -293,6 +293,25 @@ def enclosure(cs, state, pinned=None, conditionals=False):
     return out
 
 
+def hold_enclosure(what, got, r):
+    """got = (log-L, likelihoods, exponents) of an evaluation with per_site=True against an enclosure ``r``: every pattern and the total
+    inside [lo, hi] widened by the allowance of tests/hold.py; returns the largest (got - mid) / (half width + that allowance)."""
+    from tests.hold import ATOL, RTOL, _site
+    ll, lik, sc = got
+    assert sc.dtype == np.int64 and np.all(np.abs(sc) < 4096), (what, sc)
+    assert np.all(np.isfinite(lik)) and np.all(lik > 0), (what, lik)
+    site = _site(lik, sc)
+    t = RTOL * np.abs(r["mid"]) + ATOL
+    ratio = np.abs(site - r["mid"]) / (0.5 * r["width"] + t)
+    tt = RTOL * abs(r["mid_total"]) + ATOL
+    rtot = abs(ll - r["mid_total"]) / (0.5 * (r["hi_total"] - r["lo_total"]) + tt)
+    worst = max(float(ratio.max()), rtot)
+    print(f"{what}: largest (got - mid) / (half width + t) = {worst:.4f}; log-L {ll!r} in [{r['lo_total']!r}, {r['hi_total']!r}]")
+    assert np.all(site >= r["lo"] - t) and np.all(site <= r["hi"] + t), (what, int(np.argmax(ratio)), float(ratio.max()))
+    assert r["lo_total"] - tt <= ll <= r["hi_total"] + tt, (what, ll, r["lo_total"], r["hi_total"])
+    return worst
+
+
 # ---- the one call sequence -----------------------------------------------------------------------------------------------------------
 
 class Scenario:

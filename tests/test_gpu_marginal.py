@@ -32,15 +32,7 @@ def _Q(fx):
     return fx["Q"] if "Q" in fx else common.fixture_Q(fx)
 
 
-def _pin_update_list(fp, L, code):
-    from hyphy_amd import tree
-    flat = tree.flat_from_parents(fp, L)
-    out = set()
-    if int(flat.flat_parents[code]) >= 0:
-        out.update(int(x) for x in flat.path_update_nodes(int(code)))
-    if code >= L:
-        out.update(int(c) for c in flat.children_of(code - L))
-    return np.array(sorted(out), dtype=np.int64)
+_pin_update_list = mc.pin_update_list
 
 
 def _oracle_support(fx, Ps, weights, codes_nodes):

@@ -86,20 +86,9 @@ def _site(lik, sc):
 
 def _hold(what, form, got, r):
     """got = (log-L, likelihoods, exponents) against an enclosure; returns the exponents."""
-    ll, lik, sc = got
-    assert sc.dtype == np.int64 and np.all(np.abs(sc) < 4096), (what, sc)
-    assert np.all(np.isfinite(lik)) and np.all(lik > 0), (what, lik)
-    site = _site(lik, sc)
-    t = RTOL * np.abs(r["mid"]) + ATOL
-    ratio = np.abs(site - r["mid"]) / (0.5 * r["width"] + t)
-    tt = RTOL * abs(r["mid_total"]) + ATOL
-    rtot = abs(ll - r["mid_total"]) / (0.5 * (r["hi_total"] - r["lo_total"]) + tt)
-    worst = max(float(ratio.max()), rtot)
+    worst = mc.hold_enclosure(what, got, r)
     _worst[form] = max(_worst.get(form, 0.0), worst)
-    print(f"{what}: largest (got - mid) / (half width + t) = {worst:.4f}; log-L {ll!r} in [{r['lo_total']!r}, {r['hi_total']!r}]")
-    assert np.all(site >= r["lo"] - t) and np.all(site <= r["hi"] + t), (what, int(np.argmax(ratio)), float(ratio.max()))
-    assert r["lo_total"] - tt <= ll <= r["hi_total"] + tt, (what, ll, r["lo_total"], r["hi_total"])
-    return sc
+    return got[2]
 
 
 def _mix(part, cs, state, branches, entry, cat=-1, update=None):

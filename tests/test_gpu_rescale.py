@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from tests import scalefree as sf
-from tests.hold import _hold, _site  # noqa: F401
+from tests.hold import _hold, _site, hold_download  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -269,12 +269,4 @@ def test_downloaded_conditionals_and_counts(name, kernel, monkeypatch):
     with _mk(cs) as part:
         _full(cs, part, per_site=False)
         cache, counts = part.download_partials()
-    top = cache.max(axis=2)
-    zero = ~(ref["cond"].max(axis=2) > 0)
-    assert np.array_equal(top == 0, zero)
-    norm = cache / np.where(top > 0, top, 1.0)[:, :, None]
-    assert np.allclose(norm, ref["cond"], rtol=1e-9, atol=1e-12)
-    with np.errstate(divide="ignore"):
-        mag = np.log(top) - LOG_SCALER * counts
-    ok = ~zero
-    assert np.all(np.abs(mag[ok] - ref["log_mag"][ok]) <= RTOL * np.abs(ref["log_mag"][ok]) + ATOL)
+    hold_download(f"{name} {kernel}", cache, counts, ref["cond"], ref["log_mag"])
