@@ -469,14 +469,14 @@ int EvalCtx::stage_prune_nuc() {
     na.leaf_tab = s.rep_leaf;
     na.gtab = s.rep_tab + (size_t)cat * s.rep_rows * 4, na.gcnt = s.rep_cnt + (size_t)cat * s.rep_rows;
   }
-  n_wg = prune_nuc_grid(na);
-  if (sw::fused_reduce() != 0 && p->mode == 0 && fused_combine_allowed() &&
-      (use_gen ? p->nucgen_small : prune_nuc_fuses_reduce(na, have_folded)))
+  const PruneForm nf = prune_nuc_form(na, have_folded);
+  n_wg = nf.n_wg;
+  if (sw::fused_reduce() != 0 && p->mode == 0 && fused_combine_allowed() && (use_gen ? p->nucgen_small : (n_ops > 0 && nf.can_fuse)))
     wire_fused_combine(na, s.wg_flag + (size_t)p->C * s.wg_cap + 3);  // (the spare words behind the flags; zeroed at creation)
   const ExpmArgs *folded = have_folded ? &folded_expm : nullptr;
   if (!(use_gen && nucgen_launch(p->nucgen_key, na, s.stream, p->nucgen_small, (int)p->B, folded))) {
     if (use_gen) return fail("internal: the generated 4-state kernel could not be launched");
-    launch_prune_nuc(na, s.stream, folded);
+    if (launch_prune_nuc(na, s.stream, folded)) return fail("internal: no 4-state pruning kernel for this launch form");
   }
   s.last_nucgen = use_gen;
   if (folded && folded->templates && guard_coeff_slot()) return -1;  // (the ring slot is read by THIS launch)
@@ -522,15 +522,16 @@ int EvalCtx::dump_timeline(const Timeline &tl) {
 int EvalCtx::stage_prune_mfma() {
   PruneArgs pa = prune_args_current(p, s, cat, n_cat_batch);
   const size_t tl_waves = (size_t)s.ntiles * std::max(1, n_cat_batch) * std::max<size_t>(1, p->programs.size());
-  Timeline tl{sw::timeline(), p->variant == 1, tl_waves,
-              p->variant == 1 ? tl_waves * 24 : (size_t)kTraceWG * p->NW * std::max(1, n_ops) * 4, nullptr};
+  const bool per_wave = prune_form(pa).inst.family == PruneFamily::wave;  // (the kernel that will write the trace buffer: the timeline does not change the family)
+  Timeline tl{sw::timeline(), per_wave, tl_waves, per_wave ? tl_waves * 24 : (size_t)kTraceWG * p->NW * std::max(1, n_ops) * 4, nullptr};
   Blocks tl_blk;  // (back to the pool behind the dump)
   if (tl.path && n_ops > 0 && s.T == 1) {
     HIPCHK(tl_blk.get(&tl.buf, tl.n));
     HIPCHK(hipMemsetAsync(tl.buf, 0, tl.n * sizeof(long long), s.stream));
     pa.timeline = tl.buf;
   }
-  n_wg = prune_mfma_grid(pa);
+  const PruneForm pf = prune_form(pa);  // (with the timeline, before the combine's target: can_fuse says whether to set one)
+  n_wg = pf.n_wg;
   // The fused combine saves 1.5-3 us per evaluation of a small shard (below two tiles per CU; 64 x 1 250: 69.1 -> 67.7 us, 32 x 5 000:
   // 79.8 -> 77.0); at the headline size the gain shrinks to ~1 us while the pruning kernel's own duration grows by the 3-4 us of the
   // serial tail, so larger shards keep the separate kernel.  HYPHY_HIP_FUSED_REDUCE=0/1 forces either.
@@ -538,7 +539,7 @@ int EvalCtx::stage_prune_mfma() {
   const bool walk = trunk_walk_applies(p, s) && !pa.timeline && n_ops > 0;  // (the trunk as one row-split walk per tile, repeats.hip)
   const bool fuse_on = fuse_forced >= 0 ? fuse_forced != 0 : s.ntiles <= 2 * s.cus;  // (the walk at the headline: 90.0 / 89.8 us fused, 88.3 / 89.5 not)
   if (fuse_on && fused_combine_allowed() && !pa.timeline &&
-      (walk ? (trunk_walk_fuses_reduce(p) && !sw::walk_timeline()) : prune_fuses_reduce(pa))) {
+      (walk ? (trunk_walk_fuses_reduce(p) && !sw::walk_timeline()) : pf.can_fuse)) {
     wire_fused_combine(pa, s.frag_ctr + (size_t)p->C * (p->I + 2) * s.ntiles - 1);  // (a word of the arrival counters no schedule indexes; zero between launches)
     pa.red_n = n_wg;
   }

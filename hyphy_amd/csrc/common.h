@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+#include "prune_form.h"
+
 namespace hyhip {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -171,7 +173,6 @@ struct PruneArgs {
   size_t cs_gtab = 0, cs_gcnt = 0;  // class strides
 };
 constexpr int kTraceWG = 8;
-constexpr int kNucParkSlots = 4;  // LDS parking slots of the 4-state kernel (nodes whose parent is not the next entry)
 
 constexpr int kCoefInline = 400;  // coefficients that fit the kernel-argument block (n * K doubles)
 struct CoefInline {
@@ -372,7 +373,12 @@ struct PruneDispatch {
   bool on_chain = false;    // row-split kernel: the chain-schedule instantiation
 };
 const PruneDispatch &last_prune_dispatch();
-void launch_prune_nuc(const NucArgs &a, hipStream_t stream, const ExpmArgs *ex = nullptr);  // ex: matrix exponentials folded into the launch
+// what launch_prune_mfma / launch_prune_nuc will launch for these arguments (prune_form.h); the predicates below are fields of it.
+// prune_form reads no switch (its grid is padded as if HYPHY_HIP_XCD_PAD were on: the launcher's business); prune_nuc_form reads them
+PruneForm prune_form(const PruneArgs &a);
+PruneForm prune_nuc_form(const NucArgs &a, bool folded);
+// ex: matrix exponentials folded into the launch; -1: no instantiation serves this launch form (nothing launched)
+int launch_prune_nuc(const NucArgs &a, hipStream_t stream, const ExpmArgs *ex = nullptr);
 bool prune_nuc_folds_expm(int L, int S_pad, int n_ops);
 bool prune_nuc_fuses_reduce(const NucArgs &a, bool folded);  // launch_prune_nuc will run the instantiation that carries the fused final combine
 void launch_site_export(const double *lik, const int32_t *cnt, const int32_t *inv, int S, double *out_lik, long long *out_cnt,

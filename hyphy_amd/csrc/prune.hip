@@ -191,7 +191,7 @@ __global__ __launch_bounds__(64 * NW, (T == 1 ? HYPHY_OCC : 1)) void prune_mfma_
   extern __shared__ __align__(16) int16_t codes_lds[];  // CLDS: [L][T*16] leaf codes
 
   if constexpr (CHAIN) {
-    if ((int)blockIdx.x >= a.ntiles) return;  // (tile dimension padded to a multiple of 8: launch_prune_T)
+    if ((int)blockIdx.x >= a.ntiles) return;  // (tile dimension padded to a multiple of 8: select_prune_form)
   }
   const int lane = threadIdx.x & 63, g = lane >> 4, sl = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave index in an SGPR: scalar bases
@@ -681,10 +681,6 @@ __global__ __launch_bounds__(64 * NW, (T == 1 ? HYPHY_OCC : 1)) void prune_mfma_
 // parent is not the next schedule entry are parked in a wave-private LDS slot (NP of them) or re-read
 // from their persisted copy.  Workgroup = one wave; the grid is (tiles, classes, fragments).
 // ---------------------------------------------------------------------------------------------
-#ifndef HYPHY_OCC3
-#define HYPHY_OCC3 2
-#endif
-
 // TRACE (HYPHY_HIP_TIMELINE, a separate diagnostic instantiation): per wave [start, prologue done, source program done,
 // end] in 100 MHz ticks, trunk levels walked (+100 per prefetched join, +1000 per join won after depositing), how it
 // ended (0 deposited and retired, 1 reached the root, 2 retired at a fragment hand-off), HW_ID and XCC_ID; it also honours
@@ -723,15 +719,12 @@ __global__ __launch_bounds__(64 * NW, (T == 1 ? HYPHY_OCC : 1)) void prune_mfma_
 // LB: the node finalised last lives in the wave's LDS tile (`stage`) instead of 32 registers (frees registers; the next
 //     product reads its B operand from LDS like a parked node's).  OCC: waves per SIMD the instantiation is compiled for.
 // PRE: a sibling's deposit is streamed into registers under the wave's own product (32 registers).
-// APF: the first A-operand chunk of the NEXT edge product is requested during the last k-step of the current one (the
-//      schedule names it), so that an edge does not start with an exposed L2 round trip.
 // REP: the tree is the TRUNK of a class-compressed partition (repeats.hip): a leaf of the schedule may be a generalised leaf —
 //      its columns are rows of a class table (gathered by class id instead of state code) and carry a 2^64 exponent.
-template <int NW, int NP, bool CLDS, bool TRACE = false, bool LB = false, int OCC = HYPHY_OCC3, bool PRE = true, bool APF = false, bool FUSE = false,
-          bool REP = false>
+template <int NW, int NP, bool CLDS, bool TRACE = false, bool LB = false, int OCC = HYPHY_OCC3, bool PRE = true, bool REP = false>
 __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restrict__ ops, const int4 *__restrict__ prog,
                                                                              const int4 *__restrict__ jn, PruneArgs a) {
-  if (a.chain && (int)blockIdx.x >= a.ntiles) return;  // (tile dimension padded to a multiple of 8: launch_prune_T)
+  if (a.chain && (int)blockIdx.x >= a.ntiles) return;  // (tile dimension padded to a multiple of 8: select_prune_form)
   [[maybe_unused]] long long tr_t[3] = {0, 0, 0};
   [[maybe_unused]] int tr_levels = 0;
   // TRACE: shader cycles (s_memtime) in [0] internal edge products, [1] their number, [2] leaf entries, [3] leaves,
@@ -844,9 +837,7 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
   [[maybe_unused]] bool abl_after_edge = false;  // (HYPHY_ABL & 16: the first leaf behind an edge product is free)
   [[maybe_unused]] const int abl_mask = (a.ablate & 4096) ? 0 : -1;  // (HYPHY_ABL == 1 builds only)
   int polled = 0;  // (lane 0) arrival counter sampled near the end of an edge product, see the trunk loop
-  [[maybe_unused]] f64x2 Apre[NW];   // APF: first A chunk of branch `apre_branch`, requested under the previous product
-  [[maybe_unused]] int apre_branch = -1;
-  auto edge_product = [&](int branch, auto bsrc, const double *pre, const int *poll = nullptr, int next_branch = -1) {
+  auto edge_product = [&](int branch, auto bsrc, const double *pre, const int *poll = nullptr) {
     HYPHY_TR(12)
     const double *pf = a.Pfrag + (size_t)((HYPHY_ABL & 1) ? (branch & abl_mask) : branch) * NW * TILE;  // uniform
     const __amdgpu_buffer_rsrc_t pfr = agent_rsrc(pf);
@@ -856,13 +847,8 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
     for (int w = 0; w < NW; w++) D[w] = zeros;
     f64x2 Ac[NW], An[NW], bc, bn;
     [[maybe_unused]] f64x2 dq[NKK / 2];  // deposit chunks in flight (three at a time)
-    if (APF && apre_branch == branch) {
 #pragma unroll
-      for (int w = 0; w < NW; w++) Ac[w] = Apre[w];
-    } else {
-#pragma unroll
-      for (int w = 0; w < NW; w++) Ac[w] = ld16_buf(pfr, lane16, (unsigned)(w * TILE * 8));
-    }
+    for (int w = 0; w < NW; w++) Ac[w] = ld16_buf(pfr, lane16, (unsigned)(w * TILE * 8));
     bc = bsrc(0);
 #pragma unroll
     for (int k2 = 0; k2 < NKK / 2; k2++) {
@@ -874,11 +860,6 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
       if (pre) {
         dq[k2] = ld16_agent(pre, (unsigned)(k2 * 64 + lane) * 16u);
         if (k2 >= 2) acc[(k2 - 2) >> 1][((k2 - 2) & 1) * 2] *= dq[k2 - 2][0], acc[(k2 - 2) >> 1][((k2 - 2) & 1) * 2 + 1] *= dq[k2 - 2][1];
-      }
-      if (APF && k2 == NKK / 2 - 1 && next_branch >= 0) {
-        const double *pn = a.Pfrag + (size_t)next_branch * NW * TILE;  // uniform
-#pragma unroll
-        for (int w = 0; w < NW; w++) Apre[w] = ld16(pn, (unsigned)((w * TILE + lane * 2) * 8));
       }
       if (poll && k2 == NKK / 2 - 2 && lane == 0) polled = __hip_atomic_load(poll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __builtin_amdgcn_sched_barrier(0);
@@ -899,7 +880,6 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
 #pragma unroll
     for (int w = 0; w < NW; w++) acc[w] *= D[w];
     if (HYPHY_ABL & 16) abl_after_edge = true;
-    if (APF) apre_branch = next_branch;
     if constexpr (TRACE) {
       asm volatile("" ::"v"(acc[0][0]));  // (the stamp waits for the product)
       tr_ph[1]++;
@@ -909,21 +889,13 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
 
   // Interpreter of one run of schedule entries.  `own`: (trunk nodes of a chain schedule) internal index of the child
   // whose edge product this wave holds in `acc` already; `have_pre`: the deposit of the first OTHER child is in dreg.
-  auto run_ops = [&](const int4 *__restrict__ pops, int n_ops, int own, bool have_pre, int pre_cnt, int last_next = -1) {
+  auto run_ops = [&](const int4 *__restrict__ pops, int n_ops, int own, bool have_pre, int pre_cnt) {
   int4 op = pops[0];
   for (int oi = 0; oi < n_ops; oi++) {
     const int4 nxt = pops[oi + 1];
     const int kind = op.x & 3;
     if constexpr (TRACE) asm volatile("" ::"s"(kind));
     HYPHY_TR(8)
-    // APF: the edge after this one, when the schedule's next entry is an internal edge (or, behind the run's last entry,
-    // the caller's hint: the first trunk edge above a source)
-    int nb = -1;
-    if (APF) {
-      const int nk = nxt.x & 3;
-      if (oi + 1 < n_ops) nb = (nk == OPK_INTERNAL || nk == OPK_INTERNAL_GLOBAL) ? nxt.z : -1;
-      else nb = last_next;
-    }
     if (kind == OPK_LEAF) {
       const int nl = (op.x >> 8) & 0x3f;
       if (nl == 0) {
@@ -985,7 +957,7 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
         edge_product(op.z, [&](int k2) -> f64x2 {
           if constexpr (LB) return *reinterpret_cast<const f64x2 *>(stage + (k2 * 64 + lane) * 2);
           else return (f64x2){bch[k2 >> 1][(k2 & 1) * 2], bch[k2 >> 1][(k2 & 1) * 2 + 1]};
-        }, nullptr, nullptr, nb);
+        }, nullptr);
         cnt += bcnt;
       } else {
         const double *src = park + (slot - 2) * TILE;
@@ -994,7 +966,7 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
         for (int q = 1; q < NP; q++) ccnt = (slot - 2 == q) ? pcnt[q] : ccnt;
         edge_product(op.z, [&](int k2) -> f64x2 {
           return *reinterpret_cast<const f64x2 *>(src + (k2 * 64 + lane) * 2);
-        }, nullptr, nullptr, nb);
+        }, nullptr);
         cnt += ccnt;
       }
     } else if (kind == OPK_DEP) {
@@ -1045,9 +1017,9 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
 #pragma unroll
         for (int k2 = 0; k2 < NKK / 2; k2++) *reinterpret_cast<f64x2 *>(stage + (k2 * 64 + lane) * 2) = gq[k2];
         edge_product(op.z, [&](int k2) -> f64x2 { return *reinterpret_cast<const f64x2 *>(stage + (k2 * 64 + lane) * 2); },
-                     nullptr, nullptr, nb);
+                     nullptr);
       } else {
-        edge_product(op.z, [&](int k2) -> f64x2 { return gq[k2]; }, nullptr, nullptr, nb);
+        edge_product(op.z, [&](int k2) -> f64x2 { return gq[k2]; }, nullptr);
       }
       cnt += ccnt;
     }
@@ -1124,7 +1096,7 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
  int4 prg;
  for (;;) {  // chained fragments: run program `cur`, then possibly its parent program
   prg = prog[cur];  // (scalar load: uniform control flow, schedule entries in SGPRs)
-  run_ops(ops + prg.x, prg.y, -1, false, 0, (a.chain && jn[prg.w].x >= 0) ? (jn[prg.w].x >> 16) : -1);
+  run_ops(ops + prg.x, prg.y, -1, false, 0);
   if (a.chain || prg.z < 0) break;  // a chain source / the root program (or a stand-alone one)
   // arrival at the parent program: the wave that completes the parent's last child fragment (for this
   // tile) continues with the parent; every other wave retires.  Payload stores were write-through.
@@ -1184,7 +1156,7 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
       edge_product(jc.x >> 16, [&](int k2) -> f64x2 {
         if constexpr (LB) return *reinterpret_cast<const f64x2 *>(stage + (k2 * 64 + lane) * 2);
         else return (f64x2){bch[k2 >> 1][(k2 & 1) * 2], bch[k2 >> 1][(k2 & 1) * 2 + 1]};
-      }, pre, last ? nullptr : ctr, jp.x >= 0 ? (jp.x >> 16) : -1);
+      }, pre, last ? nullptr : ctr);
       cnt = bcnt;
       bool deposited = false;  // (uniform)
       if (!last) {
@@ -1297,7 +1269,7 @@ __global__ __launch_bounds__(64, OCC) void prune_wave_kernel(const int4 *__restr
       wcnt += __shfl_xor(wcnt, off);
       wflag |= __shfl_xor(wflag, off);
     }
-    publish_partial<FUSE>(a, tile0, wsum, wcnt, wflag, lane);
+    publish_partial<false>(a, tile0, wsum, wcnt, wflag, lane);
   }
   HYPHY_TRACE_FINISH(1)
 }
@@ -2166,139 +2138,52 @@ __global__ void unpack_partials_kernel(const double *__restrict__ partials, int 
   out[idx] = partials[((size_t)node * ntiles + tile) * TILE + within];
 }
 
-// What the launcher below dispatched, written down at the branch that picks the instantiation (host side only: the kernels and
-// PruneArgs know nothing of it).  hyphy_hip_last_prune_form reports it, so that a launch that quietly took another instantiation
-// than the one asked for can be seen.
+// What the launcher below dispatched, copied from the form it launched (host side only: the kernels and PruneArgs know nothing
+// of it).  hyphy_hip_last_prune_form reports it, so that a launch that quietly took another instantiation than the one asked
+// for can be seen.
 thread_local PruneDispatch g_dispatch;
-void note_wave_dispatch(int NW, int park, const char *inst) { g_dispatch = PruneDispatch{"prune_wave_kernel", NW, 1, park, inst, false}; }
-void note_team_dispatch(int NW, int T, bool on_chain, const char *inst) { g_dispatch = PruneDispatch{"prune_mfma_kernel", NW, T, -1, inst, on_chain}; }
 
-template <int NW, bool CLDS>
-int launch_prune_T(const PruneArgs &a, hipStream_t stream) {
-  // Chain grids (tiles, classes, sources): workgroup b runs on XCD b mod 8 and the grid is linearised x-fastest, so with the
-  // tile dimension padded to a multiple of 8 (the surplus workgroups retire at once) every chain of a tile — and so every
-  // join of its trunk — sits on ONE XCD: deposits and arrival counters are then L2 hits instead of trips to memory.
-  // (HYPHY_HIP_XCD_PAD=0: the bare tile count.)
-  const int gx_chain = (a.chain && a.T == 1 && sw::xcd_pad() && !a.timeline) ? ((a.ntiles + 7) & ~7) : a.ntiles / a.T;
-  const dim3 grid(a.chain ? gx_chain : a.ntiles / a.T, a.n_cat > 0 ? a.n_cat : 1, a.n_prog > 0 ? a.n_prog : 1), block(64 * NW);
-  const size_t lds = CLDS ? (size_t)a.L * a.T * 16 * sizeof(int16_t) : 0;
-  const dim3 gridw = a.chain ? dim3(gx_chain, a.n_cat > 0 ? a.n_cat : 1, a.n_prog > 0 ? a.n_prog : 1)   // chains: source-major
-                             : dim3(a.n_prog > 0 ? a.n_prog : 1, a.n_cat > 0 ? a.n_cat : 1, a.ntiles);  // fragments: tile-major
-  if (a.variant == 1 && a.T == 1) {  // wave-per-tile kernel: one wave per workgroup
-    const dim3 block1(64);
-    const size_t lds1 = CLDS ? (size_t)a.L * 16 * sizeof(int16_t) : 0;
-    if (a.leaf_tab && a.timeline && NW == 4 && CLDS) {  // tracing build of the trunk (HYPHY_HIP_TIMELINE with HYPHY_HIP_REPEATS=1)
-      note_wave_dispatch(4, a.n_slots <= 3 ? 1 : 2, "occ2 trace trunk");
-      if (a.n_slots <= 3) hipLaunchKernelGGL((prune_wave_kernel<4, 1, true, true, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      else hipLaunchKernelGGL((prune_wave_kernel<4, 2, true, true, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      return 0;
-    }
-    if (a.leaf_tab && NW == 4 && CLDS && (a.wave_variant == 2 || a.wave_variant == 3) && a.n_slots <= 2) {  // three waves per SIMD, see below
-      note_wave_dispatch(4, 0, a.wave_variant == 2 ? "occ3 trunk" : "occ3+pre trunk");
-      if (a.wave_variant == 2) hipLaunchKernelGGL((prune_wave_kernel<4, 0, true, false, true, 3, false, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      else hipLaunchKernelGGL((prune_wave_kernel<4, 0, true, false, true, 3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      return 0;
-    }
-    if (a.leaf_tab) {  // the trunk of a class-compressed partition
-      note_wave_dispatch(NW, a.n_slots <= 2 ? 0 : (a.n_slots == 3 ? 1 : 2), "occ2 trunk");
-      if (a.n_slots <= 2) hipLaunchKernelGGL((prune_wave_kernel<NW, 0, CLDS, false, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      else if (a.n_slots == 3) hipLaunchKernelGGL((prune_wave_kernel<NW, 1, CLDS, false, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      else hipLaunchKernelGGL((prune_wave_kernel<NW, 2, CLDS, false, false, HYPHY_OCC3, true, false, false, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      return 0;
-    }
-    if (a.timeline && NW == 4 && CLDS) {  // tracing build (HYPHY_HIP_TIMELINE)
-      note_wave_dispatch(4, a.n_slots <= 3 ? 1 : 2, "occ2 trace");
-      if (a.n_slots <= 3) hipLaunchKernelGGL((prune_wave_kernel<4, 1, true, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      else hipLaunchKernelGGL((prune_wave_kernel<4, 2, true, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      return 0;
-    }
-    // three waves per SIMD (the tuner's second stage): finalised node in LDS instead of 32 registers, no parking slot; 2 without,
-    // 3 with the deposit prefetch
-    if (NW == 4 && CLDS && a.wave_variant == 2 && a.n_slots <= 2) {
-      note_wave_dispatch(4, 0, "occ3");
-      hipLaunchKernelGGL((prune_wave_kernel<4, 0, true, false, true, 3, false>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      return 0;
-    }
-    if (NW == 4 && CLDS && a.wave_variant == 3 && a.n_slots <= 2) {
-      note_wave_dispatch(4, 0, "occ3+pre");
-      hipLaunchKernelGGL((prune_wave_kernel<4, 0, true, false, true, 3, true>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-      return 0;
-    }
-    // production: two waves per SIMD, 0 / 1 / 2 parking slots in LDS (the schedule was compiled for a.n_slots - 2 of them)
-    note_wave_dispatch(NW, a.n_slots <= 2 ? 0 : (a.n_slots == 3 ? 1 : 2), "occ2");
-    if (a.n_slots <= 2) hipLaunchKernelGGL((prune_wave_kernel<NW, 0, CLDS>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-    else if (a.n_slots == 3) hipLaunchKernelGGL((prune_wave_kernel<NW, 1, CLDS>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-    else hipLaunchKernelGGL((prune_wave_kernel<NW, 2, CLDS>), gridw, block1, lds1, stream, a.ops, a.prog, a.jn, a);
-    return 0;
-  }
-  if (a.leaf_tab && a.variant != 1) {  // the trunk of a class-compressed partition under the row-split workgroup kernel (r06)
-    if constexpr (NW == 4 && CLDS) {
-      if (a.T == 1) note_team_dispatch(4, 1, a.chain != 0, "trunk");
-      if (a.T == 1 && a.chain) {
-        hipLaunchKernelGGL((prune_mfma_kernel<4, 1, true, false, 0, true, false, true>), grid, block, lds, stream, a.ops, a);
-        return 0;
-      }
-      if (a.T == 1) {
-        hipLaunchKernelGGL((prune_mfma_kernel<4, 1, true, false, 0, false, false, true>), grid, block, lds, stream, a.ops, a);
-        return 0;
-      }
-    }
-    return -1;  // (no other form of this mode exists: the caller reports it — a skipped launch would leave the trunk stale)
-  }
-  if (a.variant == 2 && a.chain && a.T == 1) {  // row-split workgroups on a chain schedule: grid = (tiles, classes, sources)
-    note_team_dispatch(NW, 1, true, "");
-    if constexpr (NW == 4 && CLDS) {
-      if (a.red_out) {
-        hipLaunchKernelGGL((prune_mfma_kernel<4, 1, true, false, 0, true, true>), grid, block, lds, stream, a.ops, a);
-        return 0;
-      }
-    }
-    hipLaunchKernelGGL((prune_mfma_kernel<NW, 1, CLDS, false, 0, true>), grid, block, lds, stream, a.ops, a);
-    return 0;
-  }
-  if (a.timeline) {  // tracing build of the kernel (HYPHY_HIP_TIMELINE), T = 1 only
-    note_team_dispatch(NW, 1, false, "trace");
-    hipLaunchKernelGGL((prune_mfma_kernel<NW, 1, CLDS, true>), grid, block, lds, stream, a.ops, a);
-    return 0;
-  }
-  note_team_dispatch(NW, a.T <= 3 ? a.T : 4, false, "");
-  if (NW == 4 && CLDS && a.T == 1 && a.ablate) {  // diagnostic ablation builds (results invalid)
-#define ABL_CASE(v)                                                                                     \
-  case v:                                                                                               \
-    hipLaunchKernelGGL((prune_mfma_kernel<4, 1, true, false, v>), grid, block, lds, stream, a.ops, a); \
-    return 0;
-    switch (a.ablate) {
-      ABL_CASE(1) ABL_CASE(2) ABL_CASE(4) ABL_CASE(16) ABL_CASE(62) ABL_CASE(63) ABL_CASE(127)
-      default: break;
-    }
-#undef ABL_CASE
-  }
-  switch (a.T) {
-    case 1:
-      if constexpr (NW == 4 && CLDS) {
-        if (a.red_out) {
-          hipLaunchKernelGGL((prune_mfma_kernel<4, 1, true, false, 0, false, true>), grid, block, lds, stream, a.ops, a);
-          break;
-        }
-      }
-      hipLaunchKernelGGL((prune_mfma_kernel<NW, 1, CLDS, false>), grid, block, lds, stream, a.ops, a);
-      break;
-    case 2:
-      hipLaunchKernelGGL((prune_mfma_kernel<NW, 2, CLDS, false>), grid, block, lds, stream, a.ops, a);
-      break;
-    case 3:
-      hipLaunchKernelGGL((prune_mfma_kernel<NW, 3, CLDS, false>), grid, block, lds, stream, a.ops, a);
-      break;
-    default:
-      hipLaunchKernelGGL((prune_mfma_kernel<NW, 4, CLDS, false>), grid, block, lds, stream, a.ops, a);
-      break;
-  }
-  return 0;
+// The launch table: every compiled instantiation of the pruning kernels, from the list of prune_form.h and from nothing else
+#define HYPHY_W(NW, CLDS, NP, TRACE, LB, OCC, PRE, REP) \
+  {wave_inst(NW, CLDS, NP, TRACE, LB, OCC, PRE, REP), reinterpret_cast<const void *>(prune_wave_kernel<NW, NP, CLDS, TRACE, LB, OCC, PRE, REP>)}
+#define HYPHY_M(NW, CLDS, T, TRACE, ABL, CHAIN, FUSE, REP) \
+  {team_inst(NW, CLDS, T, TRACE, ABL, CHAIN, FUSE, REP), reinterpret_cast<const void *>(prune_mfma_kernel<NW, T, CLDS, TRACE, ABL, CHAIN, FUSE, REP>)}
+#define HYPHY_N1(PIN, REP) {nuc_inst(PIN, REP), reinterpret_cast<const void *>(prune_nuc_kernel<PIN, REP>)}
+#define HYPHY_N2(NP, PIN, FOLD, LP) {nuc2_inst(NP, PIN, FOLD, LP), reinterpret_cast<const void *>(prune_nuc2_kernel<NP, PIN, FOLD, LP>)}
+const struct PruneEntry {
+  PruneInst inst;
+  const void *fn;
+} kPruneTable[] = {HYPHY_PRUNE_FORMS(HYPHY_W, HYPHY_M, HYPHY_N1, HYPHY_N2)};
+const void *compiled(const PruneInst &inst) {  // nullptr: not in the table (PruneFamily::none never is).  (40-70 ns a search on the host)
+  for (const PruneEntry &e : kPruneTable)
+    if (e.inst == inst) return e.fn;
+  return nullptr;
 }
 
-template <int NW>
-int launch_prune_NW(const PruneArgs &a, hipStream_t stream) {
-  return a.codes_in_lds ? launch_prune_T<NW, true>(a, stream) : launch_prune_T<NW, false>(a, stream);
+// 20 to 64 states: the key of select_prune_form from a launch's arguments and HYPHY_HIP_XCD_PAD (only the launcher reads it: the
+// switch decides the padding of the grid and nothing else)
+PruneKey prune_key(const PruneArgs &a, bool xcd_pad = true) {
+  PruneKey k;
+  k.NW = a.NW, k.T = a.T, k.variant = a.variant, k.wave_variant = a.wave_variant, k.n_slots = a.n_slots, k.chain = a.chain;
+  k.ablate = a.ablate, k.ntiles = a.ntiles, k.n_cat = a.n_cat, k.n_prog = a.n_prog, k.L = a.L, k.codes_in_lds = a.codes_in_lds != 0;
+  k.leaf_tab = a.leaf_tab != nullptr, k.timeline = a.timeline != nullptr, k.target = a.red_out != nullptr, k.xcd_pad = xcd_pad;
+  return k;
+}
+// 4 states: the key of select_nuc_form from a launch's arguments, the switches and the device's CU count
+NucKey nuc_key(const NucArgs &a, bool folded, int *device = nullptr) {
+  static int cus_n[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (!cus_n[dev]) {
+    hipDeviceProp_t pr;
+    cus_n[dev] = (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
+  }
+  if (device) *device = dev;
+  NucKey k;
+  k.L = a.L, k.S_pad = a.S_pad, k.n_ops = a.n_ops, k.root_inode = a.root_inode;
+  k.PT = a.PT != nullptr, k.leaf_tab = a.leaf_tab != nullptr, k.pinned = a.pin_leaf >= 0 || a.pin_inode >= 0, k.folded = folded;
+  k.nuc = sw::nuc(), k.nuc_lp = sw::nuc_lp(), k.cus = cus_n[dev];
+  return k;
 }
 
 }  // namespace
@@ -2307,122 +2192,52 @@ const PruneDispatch &last_prune_dispatch() { return g_dispatch; }
 
 int launch_prune_mfma(const PruneArgs &a, hipStream_t stream) {
   if (a.n_ops <= 0) return 0;
-  switch (a.NW) {
-    case 1: return launch_prune_NW<1>(a, stream);
-    case 2: return launch_prune_NW<2>(a, stream);
-    case 3: return launch_prune_NW<3>(a, stream);
-    default: return launch_prune_NW<4>(a, stream);
-  }
+  const PruneForm f = select_prune_form(prune_key(a, sw::xcd_pad()));
+  const void *fn = compiled(f.inst);
+  if (!fn) return -1;  // (no instantiation serves this form: the caller reports it; a neighbour is never launched)
+  const bool wave = f.inst.family == PruneFamily::wave;
+  void *wave_args[] = {(void *)&a.ops, (void *)&a.prog, (void *)&a.jn, (void *)&a}, *team_args[] = {(void *)&a.ops, (void *)&a};
+  hipLaunchKernel(fn, dim3(f.grid[0], f.grid[1], f.grid[2]), dim3(f.block), wave ? wave_args : team_args, f.lds, stream);
+  g_dispatch = PruneDispatch{wave ? "prune_wave_kernel" : "prune_mfma_kernel", f.inst.NW, f.disp_T, f.park, f.label, f.on_chain};
+  return 0;
 }
 
-// prune_nuc2_kernel: NP patterns per thread while the leaf matrices (128 bytes each) and the parking slots fit LDS
-static int nuc_forced() { return sw::nuc(); }  // 0: r02 kernel, 1 / 2: patterns per thread
-bool prune_nuc_takes_leaf_pairs(int L) { return nuc_forced() != 0 && L <= 256; }
-static int nuc2_np(const NucArgs &a) {
-  const int forced = nuc_forced();
-  if (!prune_nuc_takes_leaf_pairs(a.L) || !a.PT) return 0;
-  if (forced == 1 || a.S_pad % 512 != 0) return 1;
-  if (forced == 2) return 2;
-  return 1;  // (measured: one pattern per thread and four workgroups per CU beat two patterns and two workgroups at every size)
+static NucKey nuc_key_of(int L, int S_pad, int n_ops) {  // (what a caller knows before it has a NucArgs; PT present, no trunk)
+  NucKey k;
+  k.L = L, k.S_pad = S_pad, k.n_ops = n_ops, k.PT = true, k.nuc = sw::nuc();
+  return k;
 }
-static size_t nuc2_lds(const NucArgs &a, int np, bool lp = false) {
-  return (size_t)(lp ? a.L + a.root_inode : a.L) * 16 * sizeof(double) +
-         (size_t)kNucParkSlots * np * 256 * (4 * sizeof(double) + sizeof(int)) + (lp ? (size_t)(a.n_ops + 4) * sizeof(int4) : 0);
-}
-
-static bool nuc_uses_lp(const NucArgs &a, int np, bool folded, int dev) {
-  static int cus_n[64];
-  if (!cus_n[dev]) {
-    hipDeviceProp_t pr;
-    cus_n[dev] = (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-  }
-  const int lp_forced = sw::nuc_lp();
-  (void)folded;
-  return np == 1 && (lp_forced >= 0 ? lp_forced != 0 : a.S_pad / 256 <= 2 * cus_n[dev]) && nuc2_lds(a, 1, true) <= (size_t)(112 * 1024);
-}
-
-// true when launch_prune_nuc can take the evaluation's matrix exponentials along (ex != nullptr): the r03 kernel on a shard of
-// at most two workgroups per CU
-bool prune_nuc_folds_expm(int L, int S_pad, int n_ops) {
-  // (late r03: on by default — with the Paterson-Stockmeyer 4 x 4 exponential and the coefficients in the kernel-argument block the
-  //  folded launch is 41 us per step at 50 000 sites against 42.5-43 with a launch of its own; HYPHY_HIP_NUC_FOLD=0 turns it off)
-  return sw::nuc_fold() && n_ops > 0 && prune_nuc_takes_leaf_pairs(L) && nuc_forced() != 2 && S_pad % 256 == 0 && S_pad / 256 <= 512;
-}
-
+bool prune_nuc_takes_leaf_pairs(int L) { return select_nuc_form(nuc_key_of(L, 0, 0)).leaf_pairs; }
+// true when launch_prune_nuc can take the evaluation's matrix exponentials along (ex != nullptr); HYPHY_HIP_NUC_FOLD=0 turns it off
+bool prune_nuc_folds_expm(int L, int S_pad, int n_ops) { return sw::nuc_fold() && nuc_may_fold(nuc_key_of(L, S_pad, n_ops)); }
 // true when launch_prune_nuc will pick the LDS-schedule instantiation (LP) — the one that can also carry the fused final
 // combine (NucArgs::red_out) — for this launch
-bool prune_nuc_fuses_reduce(const NucArgs &a, bool folded) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  return a.n_ops > 0 && nuc_uses_lp(a, nuc2_np(a), folded, dev);
-}
+PruneForm prune_nuc_form(const NucArgs &a, bool folded) { return select_nuc_form(nuc_key(a, folded)); }
+bool prune_nuc_fuses_reduce(const NucArgs &a, bool folded) { return a.n_ops > 0 && prune_nuc_form(a, folded).can_fuse; }
 
-void launch_prune_nuc(const NucArgs &a, hipStream_t stream, const ExpmArgs *ex) {
-  if (a.n_ops <= 0) return;
-  const bool pin = a.pin_leaf >= 0 || a.pin_inode >= 0;
-  const int np = nuc2_np(a);
-  if (a.leaf_tab) {  // the trunk of a class-compressed partition (no pinned states in that mode)
-    hipLaunchKernelGGL((prune_nuc_kernel<false, true>), dim3((a.S_pad + 255) / 256), dim3(256), 0, stream, a.ops, a.P, a);
-    return;
-  }
-  if (np == 0) {
-    if (pin) hipLaunchKernelGGL(prune_nuc_kernel<true>, dim3((a.S_pad + 255) / 256), dim3(256), 0, stream, a.ops, a.P, a);
-    else hipLaunchKernelGGL(prune_nuc_kernel<false>, dim3((a.S_pad + 255) / 256), dim3(256), 0, stream, a.ops, a.P, a);
-    return;
-  }
-  static bool attr_done[64];
-  constexpr int cap_bytes = 112 * 1024;
+int launch_prune_nuc(const NucArgs &a, hipStream_t stream, const ExpmArgs *ex) {
+  if (a.n_ops <= 0) return 0;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_done[dev]) {  // (2 patterns per thread: 74 KiB of parking + up to 32 KiB of leaf matrices)
-    const int cap = cap_bytes;
-    hipFuncSetAttribute(reinterpret_cast<const void *>(prune_nuc2_kernel<1, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(prune_nuc2_kernel<1, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(prune_nuc2_kernel<1, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(prune_nuc2_kernel<1, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(prune_nuc2_kernel<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(prune_nuc2_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(prune_nuc2_kernel<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(prune_nuc2_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(prune_nuc2_kernel<1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(prune_nuc2_kernel<1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
+  const PruneForm f = select_nuc_form(nuc_key(a, ex && ex->n > 0, &dev));
+  const void *fn = compiled(f.inst);
+  if (!fn) return -1;
+  static bool attr_done[64];
+  if (f.inst.family == PruneFamily::nuc2 && !attr_done[dev]) {
+    for (const auto &e : kPruneTable)
+      if (e.inst.family == PruneFamily::nuc2) hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNucLdsCap);
     attr_done[dev] = true;
   }
-  const dim3 grid(a.S_pad / (256 * np)), block(256);
-  const size_t lds = nuc2_lds(a, np);
-  ExpmArgs none;
-  none.n = 0;
-  CoefInline ci;          // (contents only matter to the folded launches, which fill it below; copied into the kernel arguments at launch)
-  ExpmArgs exb;
-  if (ex && ex->n > 0) {
+  ExpmArgs exb;   // (n = 0: nothing folded)
+  CoefInline ci;  // (contents only matter to the folded launches; copied into the kernel arguments at launch)
+  CoefNone none{0};
+  if (f.inst.FOLD) {
     exb = *ex;
     fill_coef_inline(exb, ci);
   }
-  // schedule words + every branch's matrix from LDS (LP): shards of at most two workgroups per CU
-  const bool lp = nuc_uses_lp(a, np, ex && ex->n > 0, dev);
-  if (lp) {
-    const size_t ldl = nuc2_lds(a, 1, true);
-    if (ex && ex->n > 0) {  // (with this evaluation's exponentials folded in)
-      if (pin) hipLaunchKernelGGL((prune_nuc2_kernel<1, true, true, true>), grid, block, ldl, stream, a.ops, a.PT, a, exb, ci);
-      else hipLaunchKernelGGL((prune_nuc2_kernel<1, false, true, true>), grid, block, ldl, stream, a.ops, a.PT, a, exb, ci);
-      return;
-    }
-    if (pin) hipLaunchKernelGGL((prune_nuc2_kernel<1, true, false, true>), grid, block, ldl, stream, a.ops, a.PT, a, none, CoefNone{0});
-    else hipLaunchKernelGGL((prune_nuc2_kernel<1, false, false, true>), grid, block, ldl, stream, a.ops, a.PT, a, none, CoefNone{0});
-    return;
-  }
-  if (ex && ex->n > 0 && np == 1) {
-    if (pin) hipLaunchKernelGGL((prune_nuc2_kernel<1, true, true>), grid, block, lds, stream, a.ops, a.PT, a, exb, ci);
-    else hipLaunchKernelGGL((prune_nuc2_kernel<1, false, true>), grid, block, lds, stream, a.ops, a.PT, a, exb, ci);
-    return;
-  }
-  if (np == 2) {
-    if (pin) hipLaunchKernelGGL((prune_nuc2_kernel<2, true>), grid, block, lds, stream, a.ops, a.PT, a, none, CoefNone{0});
-    else hipLaunchKernelGGL((prune_nuc2_kernel<2, false>), grid, block, lds, stream, a.ops, a.PT, a, none, CoefNone{0});
-  } else {
-    if (pin) hipLaunchKernelGGL((prune_nuc2_kernel<1, true>), grid, block, lds, stream, a.ops, a.PT, a, none, CoefNone{0});
-    else hipLaunchKernelGGL((prune_nuc2_kernel<1, false>), grid, block, lds, stream, a.ops, a.PT, a, none, CoefNone{0});
-  }
+  // prune_nuc_kernel(ops, P, a); prune_nuc2_kernel(ops, PT, a, exponentials, their coefficients)
+  void *args[] = {(void *)&a.ops, (void *)(f.inst.family == PruneFamily::nuc ? &a.P : &a.PT), (void *)&a, &exb, f.inst.FOLD ? (void *)&ci : (void *)&none};
+  hipLaunchKernel(fn, dim3(f.grid[0]), dim3(f.block), args, f.lds, stream);
+  return 0;
 }
 
 // Per-pattern results in the CALLER's order straight into host-mapped pinned memory (posted writes, 512 contiguous bytes per wave):
@@ -2469,17 +2284,11 @@ const char *launch_wg_reduce(const double *wg_sum, const long long *wg_cnt, cons
   return "wave";
 }
 
-int prune_mfma_grid(const PruneArgs &a) { return a.ntiles / a.T; }
-
-// true when launch_prune_mfma has an instantiation with the fused final combine for this launch form (PruneArgs::red_out):
-// 49-64 states with the leaf codes in LDS, one tile per workgroup, the row-split kernels (workgroup per tile, team)
-bool prune_fuses_reduce(const PruneArgs &a) {
-  // (not the wave-per-tile kernel: at 231 VGPRs the combine's registers push 15 spill instructions into its main loop —
-  //  what the fusion saves on a small shard, the spills cost)
-  if (a.NW != 4 || !a.codes_in_lds || a.T != 1 || a.timeline || a.ablate) return false;
-  if (a.leaf_tab) return false;  // (the trunk of a class-compressed partition: its instantiations carry no fused combine)
-  return a.variant == 0 || (a.variant == 2 && a.chain);
-}
+PruneForm prune_form(const PruneArgs &a) { return select_prune_form(prune_key(a)); }
+int prune_mfma_grid(const PruneArgs &a) { return prune_form(a).n_wg; }
+// true when launch_prune_mfma takes an instantiation with the fused final combine once PruneArgs::red_out is set (the rule, and why
+// the wave-per-tile kernel has no such instantiation: select_prune_form)
+bool prune_fuses_reduce(const PruneArgs &a) { return prune_form(a).can_fuse; }
 
 void launch_transpose_frag(const double *src_image, double *dst_image, const double *row_scale, int NW, hipStream_t stream) {
   hipLaunchKernelGGL(transpose_frag_kernel, dim3(1), dim3(256), 0, stream, src_image, dst_image, row_scale, NW);
@@ -2487,10 +2296,7 @@ void launch_transpose_frag(const double *src_image, double *dst_image, const dou
 void launch_bc_eval(const BcArgs &a, hipStream_t stream) {
   LAUNCH_NW(bc_eval_kernel, a.NW, dim3(a.ntiles), dim3(64), stream, a);
 }
-int prune_nuc_grid(const NucArgs &a) {
-  const int np = nuc2_np(a);
-  return np ? a.S_pad / (256 * np) : (a.S_pad + 255) / 256;
-}
+int prune_nuc_grid(const NucArgs &a) { return prune_nuc_form(a, false).n_wg; }
 
 void launch_mix_categories(const double *site_lik, const int32_t *site_cnt, const double *weights_dev, int C,
                            int S_pad, double *mixed_lik, int32_t *mixed_cnt, hipStream_t stream) {
